@@ -310,3 +310,23 @@ def test_spawned_ranks_die_with_a_killed_launcher(tmp_path):
                 pass
         time.sleep(0.1)
     assert not alive, f"rank processes {alive} outlived their launcher"
+
+
+def test_dump_output_is_a_fixed_float32_sample(tmp_path):
+    # --dump-outputs: float32, the first and the last element and the same seeded positions in
+    # every run; a buffer within the limit is written whole; the limit is shared by the ranks
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(bench.DUMP_ELEMENTS + 12345, dtype=torch.float64)
+    bench.dump_output(torch, str(tmp_path / "x"), "a", big)
+    bench.dump_output(torch, str(tmp_path / "y"), "a", big.clone())
+    x, y = np.load(tmp_path / "x" / "a.npy"), np.load(tmp_path / "y" / "a.npy")
+    assert x.dtype == np.float32 and x.shape == (bench.DUMP_ELEMENTS,) and x.nbytes <= 64 << 20
+    assert np.array_equal(x, y) and x[0] == 0.0 and x[-1] == np.float32(big[-1].item()) and (np.diff(x) >= 0).all()
+    small = torch.arange(1000, dtype=torch.float32).to(torch.bfloat16)
+    bench.dump_output(torch, str(tmp_path / "x"), "s", small)
+    assert np.array_equal(np.load(tmp_path / "x" / "s.npy"), small.float().numpy())
+    bench.dump_output(torch, str(tmp_path / "x"), "recv_rank0", big, n=8)
+    assert np.load(tmp_path / "x" / "recv_rank0.npy").shape == (bench.DUMP_ELEMENTS // 8,)

@@ -1079,8 +1079,8 @@ def test_bench_self_launch_two_ranks(dev):
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(GW.ROOT, "bench.py"), "--gpus", "2", "--same-device", "--no-sweep",
-                        "--no-cpu-baseline", "--core-only", "--count", str(16 << 20), "--steps", "5", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(GW.ROOT, "bench.py"), "--gpus", "2", "--same-device", "--full",
+                        "--no-sweep", "--no-cpu-baseline", "--core-only", "--count", str(16 << 20), "--steps", "5", "--warmup", "2"],
                        capture_output=True, text=True, timeout=280, env=env, cwd=GW.ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
