@@ -16,6 +16,14 @@
  *                        written past its end; mncclCommGetInfo writes the pre-300 prefix).
  *   mncclCommSetAlgo     choose the schedule for later calls (same association order).
  *   mncclCommLinkProbe   measure the xGMI write bandwidth the schedules are bound by.
+ *
+ * and the two halves of the all-reduce under NCCL's names and signatures, so that an NCCL / RCCL
+ * caller that shards its state recompiles unchanged (the reference has neither: mini_nccl_api.h
+ * stays its six entry points):
+ *
+ *   ncclReduceScatter    recv = chunk `rank` of what ncclAllReduce would produce over send's
+ *                        nranks * recvcount elements, bit for bit.
+ *   ncclAllGather        recv = every rank's send, rank q's at element q * sendcount.
  */
 #ifndef MINI_NCCL_EXT_H_
 #define MINI_NCCL_EXT_H_
@@ -43,7 +51,8 @@ extern "C" {
    byte budget on retired same-GPU imports (MINI_NCCL_RETIRED_MB; mncclCommInfo_t grew, same
    prefix: retired_bytes, retired_budget, budget_refusals, window_fast, run_pipelines), window calls carry the
    schedule choice in their signature and skip the host rendezvous only when no two ranks share a
-   GPU (MINI_NCCL_WINDOW_RENDEZVOUS) */
+   GPU (MINI_NCCL_WINDOW_RENDEZVOUS); still 600: ncclReduceScatter and ncclAllGather were added
+   without a change to anything above -- a caller detects them by symbol */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -159,6 +168,27 @@ typedef struct {
                                             together (CUs x 4 SIMDs x 2 waves / ranks on the most
                                             crowded GPU) */
 } mncclCommInfo_t;
+
+/* The all-reduce's two halves, NCCL's signatures.  ncclReduceScatter: sendbuff holds nranks *
+ * recvcount elements; rank r's recvbuff gets elements [r * recvcount, (r + 1) * recvcount) of what
+ * ncclAllReduce would produce over them, bit for bit (the reference ring's association), so
+ * ncclReduceScatter followed by ncclAllGather gives exactly ncclAllReduce's bits.  ncclAllGather:
+ * recvbuff holds nranks * sendcount elements, rank q's sendbuff at [q * sendcount, (q + 1) *
+ * sendcount), on every rank.  Datatypes and ops as ncclAllReduce (anything else: ncclInternalError);
+ * argument checks, blocking mode, stream ordering, sticky errors and the watchdog as ncclAllReduce.
+ * In place as NCCL defines it -- recvbuff == sendbuff + rank * recvcount elements, sendbuff ==
+ * recvbuff + rank * sendcount elements; any other overlap of the two buffers is
+ * ncclInvalidArgument (nothing is launched, the communicator stays usable).  Schedules: the read
+ * schedule wherever ncclAllReduce's larger calls would run it (device buffers every rank can
+ * share), else the ring's halves (the reduce-scatter with one extra hop, n instead of n - 1, to
+ * land chunk r on rank r in the all-reduce's association); mncclCommInfo_t.last_algo reports
+ * mncclAlgoRead or mncclAlgoRing.  No one-shot, grid or registered-window form: a call whose
+ * buffers lie in windows is negotiated like any other.  Each GPU's memory moves n + 1 chunks per
+ * call against the all-reduce's 2n. */
+ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount, ncclDataType_t datatype,
+                               ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);
+ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype,
+                           ncclComm_t comm, hipStream_t stream);
 
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream);

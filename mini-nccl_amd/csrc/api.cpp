@@ -120,6 +120,46 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
 }
 
 // ------------------------------------------------------------------ extensions
+// The all-reduce's two halves under NCCL's names and argument order (mini_nccl_ext.h): the same
+// checks in the same order as ncclAllReduce above.
+ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount, ncclDataType_t datatype,
+                               ncclRedOp_t op, ncclComm_t comm, hipStream_t stream) {
+  if (!comm || !sendbuff || !recvbuff) return ncclInvalidArgument;
+  if (recvcount == 0) return ncclSuccess;
+  RoctxRange range("mini_ncclReduceScatter");
+  if (!dtype_ok(datatype) || !op_ok(op)) {
+    fprintf(stderr, "[Mini-NCCL] ReduceScatter Internal Error: unsupported %s\n", dtype_ok(datatype) ? "RedOp" : "DataType");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->reduce_scatter(sendbuff, recvbuff, recvcount, (int)datatype, (int)op, stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] ReduceScatter Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
+ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype,
+                           ncclComm_t comm, hipStream_t stream) {
+  if (!comm || !sendbuff || !recvbuff) return ncclInvalidArgument;
+  if (sendcount == 0) return ncclSuccess;
+  RoctxRange range("mini_ncclAllGather");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] AllGather Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->all_gather(sendbuff, recvbuff, sendcount, (int)datatype, stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] AllGather Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream) {
   if (!out || !local || !incoming) return ncclInvalidArgument;

@@ -579,12 +579,16 @@ void Comm::wait_previous_call() {
 
 void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, int dtype, int op, hipStream_t stream,
                   uint32_t seq, bool vec, const char* const* psend, const char* const* precv,
-                  size_t tail_bytes, uint64_t sig) {
+                  size_t tail_bytes, uint64_t sig, int coll) {
   const int n = nranks_;
   CollParams p;
   memset(&p, 0, sizeof p);
   p.send = (const char*)send;
   p.recv = (char*)recv;
+  p.coll = coll;
+  // the one-chunk buffer of a half, shifted so that chunk `rank` of it is the buffer itself
+  if (coll == kCollReduceScatter) p.recv -= (size_t)rank_ * chunk_bytes;
+  if (coll == kCollAllGather) p.send -= (size_t)rank_ * chunk_bytes;
   p.chunk_bytes = chunk_bytes;
   // C: the pipelines this call may launch (run_pipes_, <= the layout's wave_channels())
   const int C = run_pipes();
@@ -625,9 +629,12 @@ void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, in
   // mncclAlgoReadGrid: the push form's large calls as start / grid fold / done (the same on every
   // rank: the schedule, the push form, vec and the size are rank-uniform)
   // (and auto's: schedule.h read_grid_form)
-  const bool grid = algo == 2 && read_grid_form(algo_ == 4, auto_, vec, chunk_bytes, n,
-                                                 cfg_.grid_min);
+  // (the all-reduce's alone: its halves have the persistent form only)
+  const bool grid = algo == 2 && coll == kCollAllReduce && read_grid_form(algo_ == 4, auto_, vec, chunk_bytes, n,
+                                                                          cfg_.grid_min);
   hipError_t e = grid        ? launch_read_grid(dtype, op, p, stream, cfg_.grid_vectors)
+                 : algo == 2 && coll == kCollReduceScatter ? launch_scatter_fold(dtype, op, vec, wg, nt, p, stream)
+                 : algo == 2 && coll == kCollAllGather     ? launch_gather_push(dtype, vec, wg, nt, p, stream)
                  : algo == 2 ? launch_read(dtype, op, vec, wg, nt, p, stream)
                  : algo == 3 ? launch_oneshot(dtype, op, vec, wg, nt, p, stream)
                              : launch_ring(dtype, op, vec, wg, nt, p, stream);
@@ -636,11 +643,33 @@ void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, in
   if (grid) ++read_grid_calls_;
 }
 
-ncclResult_t Comm::allreduce(const void* send, void* recv, size_t count, int dtype, int op, hipStream_t stream) {
+// The call path of ncclAllReduce (coll 0: `count` elements in send and in recv) and of its halves
+// (schedule.h Coll; `count` per rank): ncclReduceScatter's send and ncclAllGather's recv hold
+// n * count elements, the other buffer one chunk of `count`.
+ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
+                              hipStream_t stream) {
   if (sticky_ != ncclSuccess) return sticky_;
   if (check_status() != ncclSuccess) return sticky_;
   const int esz = dtype_size(dtype);
-  const size_t bytes = count * (size_t)esz;
+  const bool half = coll != kCollAllReduce;
+  const char* const coll_name = coll == kCollReduceScatter ? "ncclReduceScatter"
+                                : coll == kCollAllGather   ? "ncclAllGather"
+                                                           : "ncclAllReduce";
+  // bytes: the larger buffer's (the all-reduce's: both)
+  const size_t bytes = count * (size_t)esz * (half ? (size_t)nranks_ : 1);
+  if (half) {
+    // in place as NCCL defines it (the one-chunk buffer is chunk `rank` of the other); any other
+    // overlap of the two byte ranges is the caller's error: nothing launched, nothing negotiated
+    const size_t cb = count * (size_t)esz;
+    const uintptr_t s0 = (uintptr_t)send, r0 = (uintptr_t)recv;
+    const size_t sb = coll == kCollReduceScatter ? bytes : cb, rb = coll == kCollReduceScatter ? cb : bytes;
+    const bool in_place = coll == kCollReduceScatter ? r0 == s0 + (size_t)rank_ * cb : s0 == r0 + (size_t)rank_ * cb;
+    if (!in_place && s0 < r0 + rb && r0 < s0 + sb) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: send and recv overlap and the call is not in place\n", rank_,
+              coll_name);
+      return ncclInvalidArgument;
+    }
+  }
   int cur_dev = -1;
   hip_check(hipGetDevice(&cur_dev), "hipGetDevice");
   if (cur_dev != device_) hip_check(hipSetDevice(device_), "hipSetDevice");
@@ -667,12 +696,13 @@ ncclResult_t Comm::allreduce(const void* send, void* recv, size_t count, int dty
 
   const int n = nranks_;
   uint32_t seq = 0;  // this call's kernel (0: the call launches none)
-  const size_t chunk = n > 0 ? count / (size_t)n : 0;  // mini_nccl.cu:69
+  const size_t chunk = half ? count : n > 0 ? count / (size_t)n : 0;  // mini_nccl.cu:69
   const size_t chunk_bytes = chunk * (size_t)esz;
   if (n == 1 || chunk == 0) {
     // nRanks == 1 returns after the copy (mini_nccl.cu:66); chunk == 0 moves no slice
     if (send != recv) hip_check(hipMemcpyAsync(recv, send, bytes, hipMemcpyDefault, stream), "copy");
   } else {
+    const size_t mine = (size_t)rank_ * chunk_bytes;  // a half's chunk of this rank in the larger buffer
     // Where the kernel reads and writes: device memory as is; pinned / registered host
     // memory through its device mapping (the kernel then streams it over PCIe itself,
     // pipelined slice by slice -- what the reference's kernels did with its
@@ -689,8 +719,9 @@ ncclResult_t Comm::allreduce(const void* send, void* recv, size_t count, int dty
     // still wins at 8 ranks, profiles/r4_small_calls.txt, so auto keeps read first).  A pure
     // function of the call's size and the rank-uniform config up to the read rendezvous, which
     // all ranks decide alike.
-    const bool oneshot = algo_ == 3 && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), true);
-    const bool small = auto_ && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), false);
+    // (the halves have no one-shot form: read where an all-reduce's larger calls would, else the ring)
+    const bool oneshot = !half && algo_ == 3 && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), true);
+    const bool small = !half && auto_ && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), false);
     // (auto, and a forced one-shot's larger calls, only where the topology allows the read
     // schedule: classify_topology; MINI_NCCL_ALGO=read forces it anywhere)
     const bool read_sched = !oneshot &&
@@ -698,7 +729,8 @@ ncclResult_t Comm::allreduce(const void* send, void* recv, size_t count, int dty
                             pbuf_.available();
     // registered windows: the read schedule with no host rendezvous (no record to wait for, no
     // pointer query) -- every rank promised the same windows and offsets, the kernel checks it
-    const Window* win_s = read_sched && window_fast_ && !windows_.empty() ? find_window(send, bytes) : nullptr;
+    // (all-reduce only: a half whose buffers lie in windows is negotiated like any other call)
+    const Window* win_s = !half && read_sched && window_fast_ && !windows_.empty() ? find_window(send, bytes) : nullptr;
     const Window* win_r = win_s ? find_window(recv, bytes) : nullptr;
     if (win_s && win_r) {
       const uint64_t os = (uint64_t)((const char*)send - win_s->base), orv = (uint64_t)((char*)recv - win_r->base);
@@ -751,17 +783,24 @@ ncclResult_t Comm::allreduce(const void* send, void* recv, size_t count, int dty
         return ncclInvalidUsage;
       }
       ensure_stage(bytes, stream);
+      // a half is staged in its in-place layout: the one-chunk buffer is chunk `rank` of the stage
+      const size_t s_off = coll == kCollAllGather ? mine : 0, r_off = coll == kCollReduceScatter ? mine : 0;
       if (rs == Reach::kStaged) {
-        hip_check(hipMemcpyAsync(stage_, send, bytes, hipMemcpyDefault, stream), "stage in");
-        ksend = stage_;
+        hip_check(hipMemcpyAsync(stage_ + s_off, send, coll == kCollAllGather ? chunk_bytes : bytes, hipMemcpyDefault,
+                                 stream), "stage in");
+        ksend = stage_ + s_off;
       }
-      if (rr == Reach::kStaged) krecv = stage_;  // also in place when send is staged too
+      if (rr == Reach::kStaged) krecv = stage_ + r_off;  // also in place when send is staged too
     }
+    // the ring's all-gather moves the peers' chunks only: this rank's own chunk reaches its recv by
+    // a stream-ordered copy before the launch, when the call is not in place (after the read
+    // rendezvous below has decided: gather_push stores it itself)
+    const bool ag_own_copy = coll == kCollAllGather && (const char*)ksend != (const char*)krecv + mine;
     // elements past n*chunk keep this rank's own input (the reference copies the whole
     // buffer and never touches the tail, api.cpp:173-175 + mini_nccl.cu:69); the kernels
     // write every other element of recv and copy the tail themselves (kernels.hip copy_tail)
     const size_t body = chunk_bytes * (size_t)n;
-    const size_t tail = ksend != krecv && bytes > body ? bytes - body : 0;
+    const size_t tail = !half && ksend != krecv && bytes > body ? bytes - body : 0;
     // 16-byte vector path whenever every message's local base is dword-aligned (vectors may
     // straddle 16-byte boundaries on the local side; each message's last len % 16 bytes go
     // element by element); element-wise path otherwise (2-byte types with odd chunks)
@@ -782,14 +821,16 @@ ncclResult_t Comm::allreduce(const void* send, void* recv, size_t count, int dty
         // (the schedule choice rides along: ranks that differ in it -- mncclCommSetAlgo is per rank
         // -- would launch different kernel forms, so they fail the call as a mismatch)
         d = pbuf_.negotiate(send, recv, eligible, count, dtype, op, cfg_.timeout_ms / 1000.0 + 2.0,
-                            [this] { wait_previous_call(); }, psend, precv, &vec_all, auto_ ? -1 : algo_);
+                            [this] { wait_previous_call(); }, psend, precv, &vec_all,
+                            // (with the collective: ranks that call different ones get kMismatch)
+                            half ? ((auto_ ? 0xff : algo_) | coll << 8) : auto_ ? -1 : algo_);
       } catch (const PeerGaveUp& e) {
         return rendezvous_failed(e, true, cur_dev);
       } catch (const std::exception& e) {
         return rendezvous_failed(e, false, cur_dev);
       }
       if (d == PeerBuffers::kWindowPeer) {
-        fprintf(stderr, "[Mini-NCCL] rank %d: a peer ran this all-reduce on registered windows, this rank's buffers "
+        fprintf(stderr, "[Mini-NCCL] rank %d: a peer ran this call on registered windows, this rank's buffers "
                 "are not in them (every rank must pass buffers of the same windows); communicator is no longer "
                 "usable\n", rank_);
         sticky_ = ncclInvalidUsage;
@@ -798,8 +839,8 @@ ncclResult_t Comm::allreduce(const void* send, void* recv, size_t count, int dty
         return sticky_;
       }
       if (d == PeerBuffers::kMismatch) {
-        fprintf(stderr, "[Mini-NCCL] rank %d: ranks called ncclAllReduce with different count / datatype / op / "
-                "schedule (mncclCommSetAlgo)\n", rank_);
+        fprintf(stderr, "[Mini-NCCL] rank %d: ranks called %s with different count / datatype / op / schedule "
+                "(mncclCommSetAlgo), or different collectives\n", rank_, coll_name);
         if (cur_dev != device_) hipSetDevice(cur_dev);
         return ncclInvalidUsage;
       }
@@ -811,8 +852,12 @@ ncclResult_t Comm::allreduce(const void* send, void* recv, size_t count, int dty
     if (algo == 0 && small) algo = 3;
     seq = ++call_seq_;
     if (seq == 0) seq = ++call_seq_;  // 0 = "no kernel" (wait_for)
-    launch(algo, ksend, krecv, chunk_bytes, dtype, op, stream, seq, vec, psend, precv, tail);
-    if (rr == Reach::kStaged) hip_check(hipMemcpyAsync(recv, stage_, bytes, hipMemcpyDefault, stream), "stage out");
+    if (ag_own_copy && algo == 0)
+      hip_check(hipMemcpyAsync((char*)krecv + mine, ksend, chunk_bytes, hipMemcpyDefault, stream), "own chunk");
+    launch(algo, ksend, krecv, chunk_bytes, dtype, op, stream, seq, vec, psend, precv, tail, 0, coll);
+    if (rr == Reach::kStaged)
+      hip_check(hipMemcpyAsync(recv, krecv, coll == kCollReduceScatter ? chunk_bytes : bytes, hipMemcpyDefault, stream),
+                "stage out");
   }
   if (!capturing) {
     hip_check(hipEventRecord(order_ev_, stream), "order event");

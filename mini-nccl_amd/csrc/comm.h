@@ -27,7 +27,21 @@ class Comm {
   Comm& operator=(const Comm&) = delete;
 
   // The hot path: returns an ncclResult_t; throws only on HIP runtime errors.
-  ncclResult_t allreduce(const void* send, void* recv, size_t count, int dtype, int op, hipStream_t stream);
+  ncclResult_t allreduce(const void* send, void* recv, size_t count, int dtype, int op, hipStream_t stream) {
+    return collective(kCollAllReduce, send, recv, count, dtype, op, stream);
+  }
+  // The all-reduce's two halves (NCCL's ncclReduceScatter / ncclAllGather; `count` per rank): send
+  // holds n * count elements and recv gets chunk `rank` of their all-reduce, bit for bit; recv holds
+  // n * count elements, rank q's send at [q * count, (q + 1) * count).  The read schedule
+  // (kernels.hip scatter_fold / gather_push) where an all-reduce would run it, else the ring's
+  // halves (schedule.h coll_op); no one-shot, no grid form, no registered windows.  In place as
+  // NCCL defines it; any other overlap of the two buffers is ncclInvalidArgument.
+  ncclResult_t reduce_scatter(const void* send, void* recv, size_t count, int dtype, int op, hipStream_t stream) {
+    return collective(kCollReduceScatter, send, recv, count, dtype, op, stream);
+  }
+  ncclResult_t all_gather(const void* send, void* recv, size_t count, int dtype, hipStream_t stream) {
+    return collective(kCollAllGather, send, recv, count, dtype, kSum, stream);
+  }
 
   int rank() const { return rank_; }
   int nranks() const { return nranks_; }
@@ -87,9 +101,14 @@ class Comm {
   Reach reach(const void* p, const void** kernel_ptr, bool* local) const;
   void ensure_stage(size_t bytes, hipStream_t stream);
   // algo: 0 ring, 2 read (psend / precv: every rank's buffers mapped here), 3 one-shot
+  // coll (schedule.h Coll): a reduce-scatter's recv and an all-gather's send hold one chunk; the
+  // kernels get them shifted by rank * chunk_bytes and keep the all-reduce's index math
   void launch(int algo, const void* send, void* recv, size_t chunk_bytes, int dtype, int op, hipStream_t stream,
               uint32_t seq, bool vec, const char* const* psend = nullptr, const char* const* precv = nullptr,
-              size_t tail_bytes = 0, uint64_t sig = 0);
+              size_t tail_bytes = 0, uint64_t sig = 0, int coll = kCollAllReduce);
+  // the one call path of the three collectives; count: the all-reduce's, else per rank
+  ncclResult_t collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
+                          hipStream_t stream);
   // one rendezvous failure of the read schedule, reported like the kernel's (sticky, peers aborted)
   ncclResult_t rendezvous_failed(const std::exception& e, bool peer_gave_up, int cur_dev);
   struct Window {

@@ -29,6 +29,10 @@ struct CollParams {
   const uint32_t* host_abort;  // host-mapped abort request
   uint32_t* started;       // host-mapped start word: the kernel writes call_seq when it begins
   uint32_t call_seq;       // this launch's sequence number (Comm::wait_for's deadline starts here)
+  int32_t coll;            // schedule.h Coll: 0 all-reduce, 1 reduce-scatter (recv holds one chunk: the
+                           // host passes recv - rank * chunk_bytes), 2 all-gather (send holds one
+                           // chunk: the host passes send - rank * chunk_bytes).  In what was padding:
+                           // the struct's size and every other offset are the all-reduce's
   uint64_t timeout_ticks;  // s_memrealtime ticks (100 MHz)
   int32_t sys_fence;       // system-scope release fence before each ready flag
   int32_t pipes;           // the communicator's pipelines (mailbox / scratch / counter layout);
@@ -60,6 +64,13 @@ hipError_t launch_read(int dtype, int op, bool vec, int channels, int threads,
                        const CollParams& p, hipStream_t stream);
 hipError_t launch_oneshot(int dtype, int op, bool vec, int channels, int threads,
                           const CollParams& p, hipStream_t stream);
+// the read schedule's two halves as collectives of their own (p.coll 1 / 2, the persistent form
+// and protocol of launch_read): scatter_fold folds chunk `rank` of every peer's send into recv;
+// gather_push stores send into chunk `rank` of every rank's recv (by element size: no arithmetic)
+hipError_t launch_scatter_fold(int dtype, int op, bool vec, int channels, int threads,
+                               const CollParams& p, hipStream_t stream);
+hipError_t launch_gather_push(int dtype, bool vec, int channels, int threads,
+                              const CollParams& p, hipStream_t stream);
 // the read schedule's push form for large calls as three launches (start, grid fold, done):
 // schedule.h read_grid_fits(p.chunk_bytes, p.n, kReadGridFloor) (2 <= n <= 8, whole 16-byte vectors), p.go set
 // vectors: 0 = schedule.h read_grid_vectors; 1 / 2 / 4 (MINI_NCCL_GRID_VECTORS) for fp32 Sum only

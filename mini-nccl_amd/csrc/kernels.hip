@@ -11,6 +11,11 @@
 //  read_kernel    the default: same association order, no scratch -- each rank loads its
 //                 peers' send buffers over the links and pushes its results into their recv
 //                 buffers (mapped by Comm per allocation).
+//  scatter_fold / gather_push   the read schedule's two halves as collectives of their own
+//                 (ncclReduceScatter / ncclAllGather): read_kernel's fold without its pushes, and
+//                 its pushes without a fold; the same protocol, so calls of any kind follow each
+//                 other on one communicator.  Their fallback is ring_kernel with the op table of
+//                 one half (schedule.h coll_op).
 //  read_start / read_grid / read_done   the read schedule's push form as three launches (the
 //                 runtime form mncclAlgoReadGrid, for large calls): a grid of one-batch workgroups
 //                 between a one-wave START and a one-wave DONE.
@@ -500,12 +505,15 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) ring_kernel(Col
   u64* tx_ctr = p.tx_seq + (u64)next * C + w;
   u64* rx_ctr = p.rx_seq + (u64)prev * C + w;
   const u64 tx_base = *tx_ctr, rx_base = *rx_ctr;
-  const int mpi = ring_msgs_per_iter(n);
+  // the op table of the call's collective (schedule.h coll_op: the all-reduce's ring, or one of
+  // its halves for ncclReduceScatter / ncclAllGather)
+  const int coll = p.coll;
+  const int mpi = coll_msgs_per_iter(coll, n);
   const u64* my_ready = p.mbox + mbox_ready(C, prev, w);
   const u64* my_credit = p.mbox + mbox_credit(n, C, next, w);
   u64* out_ready = p.peer_mbox[next] + mbox_ready(C, r, w);
   u64* out_credit = p.peer_mbox[prev] + mbox_credit(n, C, r, w);
-  const int nops = ring_num_ops(n);
+  const int nops = coll_num_ops(coll, n);
 
   for (uint32_t it = 0; it < p.iters; ++it) {
     const u64 s = (u64)it * A + w;
@@ -513,7 +521,7 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) ring_kernel(Col
     const u64 soff = s * p.slice_bytes;
     const u64 itoff = (u64)it * mpi;
     for (int k = 0; k < nops; ++k) {
-      const RingOp o = ring_op(n, r, k);
+      const RingOp o = coll_op(coll, n, r, k);
       const u64 rseq = rx_base + itoff + (u64)o.recv_msg, sseq = tx_base + itoff + (u64)o.send_msg;
       bool ok = true;
       if (o.recv_msg >= 0) ok = wave_wait_ge(my_ready, rseq + 1, ctl, lane);
@@ -665,7 +673,8 @@ __device__ __forceinline__ void st_own16(rsrc_t r, uint32_t off, v4u v) {
   else st_slot16(r, off, v);
 }
 
-template <typename T, int OPC, int G, int V>
+// PUSH = false (scatter_fold, ncclReduceScatter): the same fold stored into this rank's recv only.
+template <typename T, int OPC, int G, int V, bool PUSH = true>
 __device__ __forceinline__ void read_fold_all(const CollParams& p, uint64_t coff, uint32_t nvec, int lane) {
   constexpr uint32_t step = 64 * V;
   const int n = p.n, r = p.rank, w = wave_id().w;
@@ -676,9 +685,9 @@ __device__ __forceinline__ void read_fold_all(const CollParams& p, uint64_t coff
   for (int g = 0; g < G; ++g) in[g] = make_rsrc(p.peer_send[direct_peer(n, r, 1 + (g + 1 < n ? g : 0))] + coff, vb);
   // the result also goes to the same offset of every peer's recv (pipeline w starts at peer
   // w mod n-1, so a rank's pipelines spread their pushes over all links)
-  rsrc_t pout[G];
+  rsrc_t pout[PUSH ? G : 1];
 #pragma unroll
-  for (int g = 0; g < G; ++g)
+  for (int g = 0; g < (PUSH ? G : 0); ++g)
     pout[g] = make_rsrc(p.peer_recv[direct_peer(n, r, 1 + (g + 1 < n ? (g + w) % (n - 1) : 0))] + coff, vb);
   v4u xa[G][V], aa[V], xb[G][V], ab[V];
   auto load = [&](v4u(&x)[G][V], v4u(&a)[V], uint32_t b) {
@@ -701,7 +710,7 @@ __device__ __forceinline__ void read_fold_all(const CollParams& p, uint64_t coff
 #pragma unroll
     for (int u = 0; u < V; ++u) st_own16(out, (b + (uint32_t)(u * 64 + lane)) * 16, a[u]);
 #pragma unroll
-    for (int g = 0; g < G; ++g)
+    for (int g = 0; g < (PUSH ? G : 0); ++g)
       if (g + 1 < n) {
 #pragma unroll
         for (int u = 0; u < V; ++u) st_slot16(pout[g], (b + (uint32_t)(u * 64 + lane)) * 16, a[u]);
@@ -725,8 +734,9 @@ __device__ __forceinline__ void read_fold_all(const CollParams& p, uint64_t coff
   }
 }
 
-// Returns the leading bytes of the slice whose result it also pushed to the peers.
-template <typename T, int OPC, bool VEC>
+// Returns the leading bytes of the slice whose result it also pushed to the peers (PUSH = false:
+// nothing is pushed and the value means nothing).
+template <typename T, int OPC, bool VEC, bool PUSH = true>
 __device__ __forceinline__ uint32_t read_fold(const CollParams& p, uint64_t coff, uint32_t nbytes, int lane) {
   if (!VEC) {
     read_fold_scalar<T, OPC>(p, coff, nbytes, lane, 0);
@@ -739,10 +749,10 @@ __device__ __forceinline__ uint32_t read_fold(const CollParams& p, uint64_t coff
     // variants within 256 registers without spilling)
     constexpr int h = sizeof(T) == 2 ? 1 : 0;
     if (!nvec) {
-    } else if (n == 2) read_fold_all<T, OPC, 1, 12 - 4 * h>(p, coff, nvec, lane);
-    else if (n == 3) read_fold_all<T, OPC, 2, 8 - 2 * h>(p, coff, nvec, lane);
-    else if (n <= 5) read_fold_all<T, OPC, 4, 4 - h>(p, coff, nvec, lane);
-    else read_fold_all<T, OPC, 7, 3 - h>(p, coff, nvec, lane);
+    } else if (n == 2) read_fold_all<T, OPC, 1, 12 - 4 * h, PUSH>(p, coff, nvec, lane);
+    else if (n == 3) read_fold_all<T, OPC, 2, 8 - 2 * h, PUSH>(p, coff, nvec, lane);
+    else if (n <= 5) read_fold_all<T, OPC, 4, 4 - h, PUSH>(p, coff, nvec, lane);
+    else read_fold_all<T, OPC, 7, 3 - h, PUSH>(p, coff, nvec, lane);
     if (nbytes & 15u) read_fold_scalar<T, OPC>(p, coff, nbytes, lane, nvec * 16);
     return nvec * 16;
   }
@@ -867,6 +877,174 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) read_kernel(Col
 aborted:
   if (lane == 0)
     for (int k = 1; k < n; ++k) st_sys(p.peer_mbox[direct_peer(n, r, k)] + mbox_abort(n, C), abort_word(p, seen));
+}
+
+// ---------------------------------------------------------------- the read schedule's two halves
+// ncclReduceScatter (scatter_fold) and ncclAllGather (gather_push) on device buffers every rank
+// can share: read_kernel's fold without its pushes, and its pushes without a fold.  Both run
+// read_kernel's protocol message for message -- one pipeline per wave; START to every peer, wait
+// for theirs, the slices, drain, DONE with the credits, wait for theirs; the counters advance by
+// read_msgs_per_call(iters) -- so calls of any collective and schedule follow each other on one
+// communicator, and a give-up ends as there (bounded waits, the peers' ABORT words).  Negotiated
+// calls only (no registered windows): no signature to compare.  read_kernel keeps its own copy of
+// the protocol: its fold sits at the 256-register bound and must compile to what it was.
+// body(coff, len, lane): the slice at byte coff = r * chunk_bytes + s * slice_bytes, len bytes long.
+template <typename Body>
+__device__ __forceinline__ void read_half(const CollParams& p, u64 (*s_tx)[kMaxRanks], u64 (*s_rx)[kMaxRanks],
+                                          const Body& body) {
+  signal_start(p);
+  const WaveId id = wave_id();
+  const int lane = id.lane, w = id.w, C = p.pipes, A = id.C;
+  const int n = p.n, r = p.rank;
+  u64* tx = s_tx[id.wv];
+  u64* rx = s_rx[id.wv];
+  const Ctl ctl{p.status, p.host_abort, p.mbox + mbox_abort(n, C), p.timeout_ticks, p.mbox, p.claim};
+  const uint32_t iters = p.iters;
+  const u64 mpc = read_msgs_per_call(iters);
+  if (lane < n) {
+    tx[lane] = p.tx_seq[(u64)lane * C + w];
+    rx[lane] = p.rx_seq[(u64)lane * C + w];
+  }
+  __builtin_amdgcn_wave_barrier();
+  // START: my send is readable and my recv writable (the call began on my stream); lane q speaks
+  // for peer q.  (Control flow and expressions as in read_kernel: a shared `peer` flag and an `ok`
+  // result carried over the slices cost the float fold 8 spilled registers at the 256 bound.)
+  if (lane < n && lane != r) st_sys(p.peer_mbox[lane] + mbox_ready(C, r, w), tx[lane] + 1);
+  if (!wave_wait_peers(p.mbox + mbox_ready(C, lane, w), rx[lane < n ? lane : 0] + 1, lane < n && lane != r, ctl, lane,
+                       true))
+    goto aborted;
+  acquire_sys(p.sys_fence);
+  for (uint32_t j = 0; j < iters; ++j) {
+    const u64 s = (u64)j * A + w;
+    const uint32_t len = (uint32_t)slice_len(p.chunk_bytes, p.slice_bytes, s);
+    const u64 coff = (u64)r * p.chunk_bytes + s * p.slice_bytes;
+    if (len) body(coff, len, lane);
+  }
+  // DONE: every load of a peer's send has returned and every push into a peer's recv has landed
+  drain_stores();
+  if (p.sys_fence && lane == 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  if (lane < n && lane != r) {
+    st_sys(p.peer_mbox[lane] + mbox_credit(n, C, r, w), rx[lane] + mpc);
+    st_sys(p.peer_mbox[lane] + mbox_ready(C, r, w), tx[lane] + mpc);
+  }
+  if (!wave_wait_peers(p.mbox + mbox_ready(C, lane, w), rx[lane < n ? lane : 0] + mpc, lane < n && lane != r, ctl, lane,
+                       false))
+    goto aborted;
+  if (lane < n && lane != r) {
+    p.tx_seq[(u64)lane * C + w] = tx[lane] + mpc;
+    p.rx_seq[(u64)lane * C + w] = rx[lane] + mpc;
+  }
+  return;
+aborted:
+  if (lane == 0)
+    for (int k = 1; k < n; ++k) st_sys(p.peer_mbox[direct_peer(n, r, k)] + mbox_abort(n, C), abort_word(p));
+}
+
+// Reduce-scatter: rank r folds slice s of chunk r from every rank's send in ring order (the
+// all-reduce's bits for that chunk) and stores it at the same slice offset of its recv -- p.recv is
+// recv - r * chunk_bytes (Comm::launch), so the fold helpers address both with one offset; the
+// shifted pointer is never dereferenced below recv.  Each GPU's HBM moves n + 1 chunks per call.
+// In place (recv == send + r * chunk_bytes): only rank r reads chunk r of anyone's send, and it
+// stores a batch after that batch's loads.
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scatter_fold(CollParams p) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, OPC, VEC, false>(p, coff, len, lane); });
+}
+
+// All-gather, 16-byte vectors of one slice: V vectors per lane per batch, loaded non-temporal from
+// this rank's send, stored into its own recv and pushed into every peer's recv at chunk r with the
+// sc0 sc1 stores whose visibility to the owner's later kernels the all-reduce's pushes rely on
+// (file header).  Two batches in flight per wave: the next batch's loads leave before this one is
+// stored -- unconditionally, for the vmcnt reason read_fold_all explains; past the slice they fall
+// outside the buffer resource, return 0 and touch nothing.  Pipeline w starts its pushes at peer
+// w mod n-1, so a rank's pipelines spread over all links.  own = false (in place): the own store's
+// resource is empty and drops it.  G peer slots up to 8 ranks (their descriptors stay in SGPRs);
+// G = 0: any rank count, the peers in a loop.
+constexpr int kGatherV = 8;
+
+template <int G, int V>
+__device__ __forceinline__ void gather_push_vec(const CollParams& p, uint64_t coff, uint32_t nvec, int lane, bool own) {
+  constexpr uint32_t step = 64 * V;
+  constexpr int GS = G > 0 ? G : 1;
+  const int n = p.n, r = p.rank, w = wave_id().w;
+  const uint32_t vb = nvec * 16;
+  const rsrc_t src = make_rsrc(p.send + coff, vb), out = make_rsrc(p.recv + coff, own ? vb : 0u);
+  rsrc_t pout[GS];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+    pout[g] = make_rsrc(p.peer_recv[direct_peer(n, r, 1 + (g + 1 < n ? (g + w) % (n - 1) : 0))] + coff, vb);
+  v4u xa[V], xb[V];
+  auto load = [&](v4u(&x)[V], uint32_t b) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) x[u] = ld_nt16(src, (b + (uint32_t)(u * 64 + lane)) * 16);
+  };
+  auto store = [&](v4u(&x)[V], uint32_t b) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) st_own16(out, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+    if (G > 0) {
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+        if (g + 1 < n) {
+#pragma unroll
+          for (int u = 0; u < V; ++u) st_slot16(pout[g], (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+        }
+    } else {
+      for (int k = 0; k + 1 < n; ++k) {
+        const rsrc_t po = make_rsrc(p.peer_recv[direct_peer(n, r, 1 + (k + w) % (n - 1))] + coff, vb);
+#pragma unroll
+        for (int u = 0; u < V; ++u) st_slot16(po, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+      }
+    }
+  };
+  uint32_t b = 0;
+  load(xa, b);
+  for (;;) {
+    load(xb, b + step);
+    store(xa, b);
+    if ((b += step) >= nvec) break;
+    load(xa, b + step);
+    store(xb, b);
+    if ((b += step) >= nvec) break;
+  }
+}
+
+// slice `nbytes` at byte `coff` of every recv (chunk r), from the same offset of p.send (send -
+// r * chunk_bytes, Comm::launch); the last nbytes % 16 bytes, and everything without VEC, element
+// by element
+template <int ESZ, bool VEC>
+__device__ __forceinline__ void gather_slice(const CollParams& p, uint64_t coff, uint32_t nbytes, int lane) {
+  const int n = p.n, r = p.rank;
+  const bool own = p.send != p.recv;  // in place: this rank's chunk already is in its recv
+  uint32_t done = 0;
+  if (VEC) {
+    const uint32_t nvec = nbytes >> 4;
+    if (!nvec) {
+    } else if (n == 2) gather_push_vec<1, kGatherV>(p, coff, nvec, lane, own);
+    else if (n == 3) gather_push_vec<2, kGatherV>(p, coff, nvec, lane, own);
+    else if (n <= 5) gather_push_vec<4, kGatherV>(p, coff, nvec, lane, own);
+    else if (n <= 8) gather_push_vec<7, kGatherV>(p, coff, nvec, lane, own);
+    else gather_push_vec<0, kGatherV>(p, coff, nvec, lane, own);
+    done = nvec * 16;
+  }
+  if (done == nbytes) return;
+  typedef Scal<ESZ> S;
+  const rsrc_t src = make_rsrc(p.send + coff, nbytes), out = make_rsrc(p.recv + coff, own ? nbytes : 0u);
+  const uint32_t ne = nbytes / ESZ;
+  for (uint32_t i = done / ESZ + (uint32_t)lane; i < ne; i += 64) {
+    const typename S::U v = S::ld(src, i * (uint32_t)ESZ);
+    S::st(out, i * (uint32_t)ESZ, v);
+    for (int k = 1; k < n; ++k) S::st(make_rsrc(p.peer_recv[direct_peer(n, r, k)] + coff, nbytes), i * (uint32_t)ESZ, v);
+  }
+}
+
+// All-gather: no arithmetic, so by element size only.  Only rank q ever writes chunk q of any recv,
+// and nobody reads a recv inside the call.  Each GPU's HBM moves n + 1 chunks per call (one read,
+// n writes landing in it).
+template <int ESZ, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) gather_push(CollParams p) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { gather_slice<ESZ, VEC>(p, coff, len, lane); });
 }
 
 // ---------------------------------------------------------------- read schedule, grid form
@@ -1279,6 +1457,43 @@ hipError_t launch_read(int dtype, int op, bool vec, int C, int nt, const CollPar
 #define M(T) return read_for_t<T>(op, vec, C, nt, p, st)
   MNCCL_DISPATCH_T(dtype, M)
 #undef M
+}
+
+template <typename T>
+static hipError_t scatter_for_t(int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
+#define SCATTER_CASE(OPC)                                                                        \
+  case OPC:                                                                                      \
+    if (vec) hipLaunchKernelGGL((scatter_fold<T, OPC, true>), dim3(C), dim3(nt), 0, st, p);     \
+    else hipLaunchKernelGGL((scatter_fold<T, OPC, false>), dim3(C), dim3(nt), 0, st, p);        \
+    break;
+  switch (op) {
+    SCATTER_CASE(kSum) SCATTER_CASE(kProd) SCATTER_CASE(kMax) SCATTER_CASE(kMin)
+    default: return hipErrorInvalidValue;
+  }
+#undef SCATTER_CASE
+  return hipGetLastError();
+}
+
+hipError_t launch_scatter_fold(int dtype, int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
+  if (p.coll != kCollReduceScatter) return hipErrorInvalidValue;
+#define M(T) return scatter_for_t<T>(op, vec, C, nt, p, st)
+  MNCCL_DISPATCH_T(dtype, M)
+#undef M
+}
+
+hipError_t launch_gather_push(int dtype, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
+  if (p.coll != kCollAllGather) return hipErrorInvalidValue;
+#define GATHER_CASE(ESZ)                                                                         \
+  case ESZ:                                                                                      \
+    if (vec) hipLaunchKernelGGL((gather_push<ESZ, true>), dim3(C), dim3(nt), 0, st, p);         \
+    else hipLaunchKernelGGL((gather_push<ESZ, false>), dim3(C), dim3(nt), 0, st, p);            \
+    break;
+  switch (dtype_size(dtype)) {
+    GATHER_CASE(2) GATHER_CASE(4) GATHER_CASE(8)
+    default: return hipErrorInvalidValue;
+  }
+#undef GATHER_CASE
+  return hipGetLastError();
 }
 
 template <typename T>

@@ -21,6 +21,10 @@
 // (acc = op(x_q, acc): the visited rank's value is the LEFT/local operand exactly as at rank q
 // of the ring) and pushes the result into every peer's recv (kernels.hip read_kernel).
 //
+// The two halves (ncclReduceScatter / ncclAllGather): the read schedule's fold without the pushes,
+// its pushes without a fold (kernels.hip scatter_fold / gather_push), and the ring's two phases as
+// op tables of their own (coll_op below).
+//
 // One-shot (small calls the read schedule cannot take): every rank stores its pieces into every
 // peer's scratch and folds each piece of the result from all n ranks in that same order
 // (kernels.hip oneshot_kernel; geometry below).
@@ -80,6 +84,48 @@ MNCCL_HD RingOp ring_op(int n, int r, int k) {
     o.chunk = mod_n(r - j, n);
     o.send_msg = (j < n - 2) ? k : -1;
     o.recv_msg = k - 1;
+  }
+  return o;
+}
+
+// The ring's two halves as collectives of their own (ncclReduceScatter / ncclAllGather on the
+// fallback path; ring_kernel picks the table by CollParams::coll at run time).  coll 0 is the
+// all-reduce above, unchanged.
+//   Reduce-scatter (n + 1 ops, n messages per iteration and link): chunk c starts at rank c, is
+//   folded as op(local, incoming) at c+1, ..., c-1 -- the all-reduce's association -- and is then
+//   handed one more hop to its owner c, whose recv holds only that chunk (the host passes
+//   recv - r * chunk_bytes, so the index math stays the all-reduce's):
+//     op 0       : send the raw chunk r
+//     op 1..n-1  : receive chunk (r-k) mod n, reduce, forward
+//     op n       : receive the finished chunk r, store it
+//   All-gather (n ops, n - 1 messages): the all-reduce's second phase starting from the raw chunk
+//   (the host passes send - r * chunk_bytes; the own chunk reaches the own recv by a device copy
+//   before the launch when the call is not in place):
+//     op 0       : send chunk r
+//     op 1..n-2  : receive chunk (r-k) mod n, store, forward
+//     op n-1     : receive chunk (r+1) mod n, store
+enum Coll : int { kCollAllReduce = 0, kCollReduceScatter = 1, kCollAllGather = 2 };
+
+MNCCL_HD int coll_num_ops(int coll, int n) {
+  return coll == kCollReduceScatter ? n + 1 : coll == kCollAllGather ? n : ring_num_ops(n);
+}
+MNCCL_HD int coll_msgs_per_iter(int coll, int n) {
+  return coll == kCollReduceScatter ? n : coll == kCollAllGather ? n - 1 : ring_msgs_per_iter(n);
+}
+MNCCL_HD RingOp coll_op(int coll, int n, int r, int k) {
+  if (coll != kCollReduceScatter && coll != kCollAllGather) return ring_op(n, r, k);
+  RingOp o;
+  const int last = coll_num_ops(coll, n) - 1;
+  if (k == 0) {
+    o.kind = kSend; o.chunk = r; o.send_msg = 0; o.recv_msg = -1;
+  } else if (k < last) {
+    o.kind = coll == kCollReduceScatter ? kReduceSend : kCopySend;
+    o.chunk = mod_n(r - k, n);
+    o.send_msg = k; o.recv_msg = k - 1;
+  } else {
+    o.kind = kCopy;
+    o.chunk = coll == kCollReduceScatter ? r : mod_n(r + 1, n);
+    o.send_msg = -1; o.recv_msg = k - 1;
   }
   return o;
 }

@@ -5,6 +5,9 @@
 //   * the data each rank ends with (compared by the tests against oracle/ring_oracle.c),
 //   * deadlock freedom for the given (n, channels, slots, sizes): no progress => -1,
 //   * that the per-channel sequence bases carried across calls keep flags consistent.
+// mnccl_sim_collective runs sequences of all-reduce / reduce-scatter / all-gather calls on one
+// such state (the halves: schedule.h coll_op on the ring, kernels.hip scatter_fold / gather_push on
+// the read schedule).
 // fp32 only (the schedule does not depend on the element type); ops as reference
 // mini_nccl.cu:38-41 with a = local, b = incoming.
 #include <stdint.h>
@@ -29,6 +32,9 @@ float apply(int op, float a, float b) {
 
 struct World {
   int n, C, K, op, algo;
+  int coll = kCollAllReduce;  // the current call's collective (schedule.h Coll); for a half, the
+                              // one-chunk buffer's pointer is shifted as Comm::launch shifts it
+  std::vector<char> own;      // all-gather: per rank, whether the read kernel stores the own chunk
   int A = 0;  // pipelines the current call runs (schedule.h call_pipelines)
   uint64_t slice, slot_bytes, chunk_bytes, nslices;  // payload per message, slot stride
   uint32_t iters;
@@ -77,12 +83,12 @@ bool ring_step(World& W, Prog& P) {
   const int n = W.n, r = P.r, w = P.w, K = W.K;
   const int prev = mod_n(r - 1, n), next = mod_n(r + 1, n);
   const uint64_t tx_base = W.tx_seq[r][(size_t)next * W.C + w], rx_base = W.rx_seq[r][(size_t)prev * W.C + w];
-  const int mpi = ring_msgs_per_iter(n);
+  const int mpi = coll_msgs_per_iter(W.coll, n);
   const uint64_t s = (uint64_t)P.it * W.A + w;  // slice s on pipeline s mod A (kernels.hip ring_kernel)
   const uint64_t len = slice_len(W.chunk_bytes, W.slice, s);
   const uint64_t soff = s * W.slice;
   const uint64_t itoff = (uint64_t)P.it * mpi;
-  const RingOp o = ring_op(n, r, P.k);
+  const RingOp o = coll_op(W.coll, n, r, P.k);
   const uint64_t rseq = rx_base + itoff + (uint64_t)o.recv_msg, sseq = tx_base + itoff + (uint64_t)o.send_msg;
   if (o.recv_msg >= 0 && W.ready(r, prev, w) < rseq + 1) return false;
   if (o.send_msg >= 0 && sseq + 1 > (uint64_t)K && W.credit(r, next, w) < sseq + 1 - K) return false;
@@ -96,7 +102,7 @@ bool ring_step(World& W, Prog& P) {
   }
   if (o.send_msg >= 0) W.ready(next, r, w) = sseq + 1;
   if (o.recv_msg >= 0) W.credit(prev, r, w) = rseq + 1;
-  if (++P.k == ring_num_ops(n)) {
+  if (++P.k == coll_num_ops(W.coll, n)) {
     P.k = 0;
     if (++P.it == W.iters) P.done = true;
   }
@@ -131,8 +137,21 @@ bool read_step(World& W, Prog& P) {
     // every load of the slice came first (in place, recv chunk r of a peer is its send chunk r)
     if (len) {
       memcpy((char*)W.recv[r] + coff, res.data(), (size_t)len);
+      // (kernels.hip scatter_fold: the fold with no pushes -- W.recv[r] is recv - r * chunk_bytes)
+      if (W.coll == kCollReduceScatter) return;
       for (int k = 1; k < n; ++k) memcpy((char*)W.recv[direct_peer(n, r, k)] + coff, res.data(), (size_t)len);
     }
+  };
+  // kernels.hip gather_push: slice `it` of this rank's send (W.send[r] is send - r * chunk_bytes)
+  // into chunk r of its own recv (not in place) and of every peer's
+  auto push = [&](uint32_t it) {
+    const uint64_t s = (uint64_t)it * W.A + w;
+    const uint64_t len = slice_len(W.chunk_bytes, W.slice, s);
+    const uint64_t coff = (uint64_t)r * W.chunk_bytes + s * W.slice;
+    if (!len) return;
+    const char* src = (const char*)W.send[r] + coff;
+    if (W.own[(size_t)r]) memcpy((char*)W.recv[r] + coff, src, (size_t)len);
+    for (int k = 1; k < n; ++k) memcpy((char*)W.recv[direct_peer(n, r, (k - 1 + w) % (n - 1) + 1)] + coff, src, (size_t)len);
   };
   switch (P.j) {
     case 0:
@@ -168,7 +187,10 @@ bool read_step(World& W, Prog& P) {
       P.k = 0;
       return true;
     case 2:
-      if (P.it < W.iters) fold(P.it++);
+      if (P.it < W.iters) {
+        if (W.coll == kCollAllGather) push(P.it++);
+        else fold(P.it++);
+      }
       if (P.it >= W.iters) P.j = 3;
       return true;
     case 3:
@@ -236,6 +258,123 @@ bool oneshot_step(World& W, Prog& P) {
   return true;
 }
 
+// a fresh communicator state: scratch, mailboxes and the per-pair FIFO counters, all zero
+void init_world(World& W, int n, int channels, int slots, int op, uint64_t slice_bytes) {
+  W.n = n; W.C = channels; W.K = slots; W.op = op; W.algo = 0; W.slot_bytes = slice_bytes;
+  // n - 1 regions per rank, exactly as Comm allocates (schedule.h region_index)
+  W.scratch.assign((size_t)n, std::vector<char>((size_t)(n > 1 ? n - 1 : 1) * scratch_region_bytes(channels, slots, slice_bytes)));
+  W.mbox.assign((size_t)n, std::vector<uint64_t>((size_t)mbox_words(n, channels), 0));
+  W.tx_seq.assign((size_t)n, std::vector<uint64_t>((size_t)n * channels, 0));
+  W.rx_seq.assign((size_t)n, std::vector<uint64_t>((size_t)n * channels, 0));
+}
+
+// One call on the state W, as Comm::collective + Comm::launch run it: schedule `code` (0 ring,
+// 1 one-shot, 2 read (persistent kernel), 4 read's grid form), collective `coll` over `count`
+// elements (the all-reduce's; per rank for a half).  0, -1 on deadlock, -2 on bad arguments.
+int run_call(World& W, int code, int coll, uint64_t count, const float* const* send, float* const* recv,
+             uint64_t slice_bytes, uint64_t min_slice, uint64_t schedule_seed, uint64_t& rng, uint64_t& steps) {
+  const int n = W.n, channels = W.C;
+  const bool half = coll != kCollAllReduce;
+  if (code > 4 || code == 3 || (half && code != 0 && code != 2)) return -2;
+  const int a = code >= 2 ? 2 : code;  // 0 ring, 1 one-shot, 2 read
+  const uint64_t chunk = half ? count : count / (uint64_t)n;
+  W.coll = coll;
+  W.chunk_bytes = chunk * 4;
+  W.send.assign(send, send + n);
+  W.recv.assign(recv, recv + n);
+  W.own.assign((size_t)n, 1);
+  // as Comm::launch: adaptive payload (min_slice 0 = off; the read schedule's own rule), fixed
+  // slot stride, one pipeline per slice up to all of them
+  if (a == 1 && W.chunk_bytes) {
+    if (min_slice && !oneshot_fits(W.chunk_bytes, n, channels, slice_bytes, true)) return -2;
+    W.slice = min_slice ? oneshot_slice(W.chunk_bytes, n, channels, slice_bytes) : slice_bytes;
+    if ((W.chunk_bytes + W.slice - 1) / W.slice * (uint64_t)n > (uint64_t)channels) return -2;
+  } else if (!min_slice || a == 1) W.slice = slice_bytes;
+  else if (a == 2) W.slice = read_slice(W.chunk_bytes, channels, slice_bytes, min_slice, kReadDepth);
+  else W.slice = effective_slice(W.chunk_bytes, channels, slice_bytes, min_slice, 1);
+  if (code == 4 && W.chunk_bytes) W.slice = W.chunk_bytes;  // grid form: one "slice", pipeline 0's protocol
+  W.nslices = (W.chunk_bytes + W.slice - 1) / W.slice;
+  W.A = call_pipelines(a == 1 ? W.nslices * (uint64_t)n : W.nslices, channels, 1);  // one-shot: per chunk too
+  W.iters = (uint32_t)((W.nslices + (uint64_t)W.A - 1) / (uint64_t)W.A);
+  for (int r = 0; r < n; ++r) {
+    if (half) {
+      // Comm::collective: one device copy of the chunk with one rank; the ring's all-gather gets
+      // the own chunk by a copy before the launch when the call is not in place; then the
+      // one-chunk buffer's pointer shifted by r chunks (Comm::launch)
+      const char* s = (const char*)send[r];
+      char* d = (char*)recv[r];
+      if (n == 1) {
+        if (s != d) memcpy(d, s, (size_t)W.chunk_bytes);
+        continue;
+      }
+      if (coll == kCollAllGather) {
+        W.own[(size_t)r] = s != d + (uint64_t)r * W.chunk_bytes;
+        if (a == 0 && W.own[(size_t)r]) memcpy(d + (uint64_t)r * W.chunk_bytes, s, (size_t)W.chunk_bytes);
+        W.send[r] = (const float*)(s - (uint64_t)r * W.chunk_bytes);
+      } else {
+        W.recv[r] = (float*)(d - (uint64_t)r * W.chunk_bytes);
+      }
+      continue;
+    }
+    // send -> recv copy of the tail (Comm::collective)
+    if ((const void*)recv[r] == (const void*)send[r]) continue;  // in place
+    const uint64_t body = W.chunk_bytes * (uint64_t)n;
+    if (n == 1 || chunk == 0) memcpy(recv[r], send[r], count * 4);
+    else if (count * 4 > body) memcpy((char*)recv[r] + body, (const char*)send[r] + body, count * 4 - body);
+  }
+  if (n == 1 || chunk == 0) return 0;
+  std::vector<Prog> progs;
+  for (int r = 0; r < n; ++r)
+    for (int w = 0; w < channels; ++w) {
+      Prog p;
+      p.r = r; p.w = w;
+      p.done = W.iters == 0 || w >= W.A;  // pipelines past A sit the call out
+      progs.push_back(p);
+    }
+  for (;;) {
+    bool any = false, all_done = true;
+    const size_t np = progs.size();
+    const size_t start = schedule_seed ? (size_t)((rng >> 33) % np) : 0;
+    for (size_t j = 0; j < np; ++j) {
+      Prog& P = progs[(start + j) % np];
+      if (P.done) continue;
+      all_done = false;
+      // a random number of ops per turn for this program when seeded
+      int burst = 1;
+      if (schedule_seed) {
+        rng = rng * 6364136223846793005ull + 1442695040888963407ull;
+        burst = 1 + (int)((rng >> 40) % 4);
+      }
+      for (int b = 0; b < burst && !P.done; ++b) {
+        const bool ok = a == 2 ? read_step(W, P) : a == 1 ? oneshot_step(W, P) : ring_step(W, P);
+        if (!ok) break;
+        any = true;
+        ++steps;
+      }
+    }
+    if (schedule_seed) rng = rng * 6364136223846793005ull + 1442695040888963407ull;
+    if (all_done) break;
+    if (!any) return -1;  // deadlock
+  }
+  // the kernels' last action per pipeline that ran: advance the per-pair FIFO counters
+  for (int r = 0; r < n; ++r)
+    for (int w = 0; w < W.A; ++w) {
+      if (a == 2 || a == 1) {
+        const uint64_t m = a == 2 ? read_msgs_per_call(W.iters) : 1;  // one-shot: one message each way
+        for (int q = 0; q < n; ++q) {
+          if (q == r) continue;
+          W.tx_seq[r][(size_t)q * channels + w] += m;
+          W.rx_seq[r][(size_t)q * channels + w] += m;
+        }
+      } else {
+        const uint64_t m = (uint64_t)W.iters * coll_msgs_per_iter(coll, n);
+        W.tx_seq[r][(size_t)mod_n(r + 1, n) * channels + w] += m;
+        W.rx_seq[r][(size_t)mod_n(r - 1, n) * channels + w] += m;
+      }
+    }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -246,6 +385,15 @@ uint64_t mnccl_oneshot_slice(uint64_t chunk_bytes, int n, int channels, uint64_t
 }
 int mnccl_oneshot_fits(uint64_t chunk_bytes, int n, int channels, uint64_t slot_bytes, int forced) {
   return oneshot_fits(chunk_bytes, n, channels, slot_bytes, forced != 0) ? 1 : 0;
+}
+
+// csrc/schedule.h op tables of the ring and its halves (coll_op; ring_op for comparison), exported
+// for the host-logic tests: out = {kind, chunk, send_msg, recv_msg}
+int mnccl_coll_num_ops(int coll, int n) { return coll_num_ops(coll, n); }
+int mnccl_coll_msgs_per_iter(int coll, int n) { return coll_msgs_per_iter(coll, n); }
+void mnccl_coll_op(int coll, int n, int r, int k, int* out) {
+  const RingOp o = coll < 0 ? ring_op(n, r, k) : coll_op(coll, n, r, k);  // coll < 0: ring_op itself
+  out[0] = o.kind; out[1] = o.chunk; out[2] = o.send_msg; out[3] = o.recv_msg;
 }
 
 // csrc/schedule.h effective_slice, exported for the host-logic tests
@@ -293,91 +441,39 @@ int mnccl_sim_allreduce(uint64_t algo, const float* const* send, float* const* r
                         uint64_t schedule_seed, uint64_t* steps_out) {
   if (n < 1 || n > 16 || channels < 1 || slots < 1 || slice_bytes < 4 || slice_bytes % 4) return -2;
   World W;
-  W.n = n; W.C = channels; W.K = slots; W.op = op; W.algo = (int)algo; W.slot_bytes = slice_bytes;
-  const uint64_t chunk = count / (uint64_t)n;
-  W.chunk_bytes = chunk * 4;
-  W.send.assign(send, send + n);
-  W.recv.assign(recv, recv + n);
-  // n - 1 regions per rank, exactly as Comm allocates (schedule.h region_index)
-  W.scratch.assign((size_t)n, std::vector<char>((size_t)(n > 1 ? n - 1 : 1) * scratch_region_bytes(channels, slots, slice_bytes)));
-  W.mbox.assign((size_t)n, std::vector<uint64_t>((size_t)mbox_words(n, channels), 0));
-  W.tx_seq.assign((size_t)n, std::vector<uint64_t>((size_t)n * channels, 0));
-  W.rx_seq.assign((size_t)n, std::vector<uint64_t>((size_t)n * channels, 0));
+  init_world(W, n, channels, slots, op, slice_bytes);
+  W.algo = (int)algo;
   uint64_t steps = 0;
   uint64_t rng = schedule_seed * 6364136223846793005ull + 1442695040888963407ull;
   for (int call = 0; call < calls; ++call) {
-    const int code = (int)((algo >> (3 * call)) & 7);
-    if (code > 4 || code == 3) return -2;
-    const int a = code >= 2 ? 2 : code;  // 0 ring, 1 one-shot, 2 read
-    // as Comm::launch: adaptive payload (min_slice 0 = off; the read schedule's own rule), fixed
-    // slot stride, one pipeline per slice up to all of them
-    if (a == 1 && W.chunk_bytes) {
-      if (min_slice && !oneshot_fits(W.chunk_bytes, n, channels, slice_bytes, true)) return -2;
-      W.slice = min_slice ? oneshot_slice(W.chunk_bytes, n, channels, slice_bytes) : slice_bytes;
-      if ((W.chunk_bytes + W.slice - 1) / W.slice * (uint64_t)n > (uint64_t)channels) return -2;
-    } else if (!min_slice || a == 1) W.slice = slice_bytes;
-    else if (a == 2) W.slice = read_slice(W.chunk_bytes, channels, slice_bytes, min_slice, kReadDepth);
-    else W.slice = effective_slice(W.chunk_bytes, channels, slice_bytes, min_slice, 1);
-    if (code == 4 && W.chunk_bytes) W.slice = W.chunk_bytes;  // grid form: one "slice", pipeline 0's protocol
-    W.nslices = (W.chunk_bytes + W.slice - 1) / W.slice;
-    W.A = call_pipelines(a == 1 ? W.nslices * (uint64_t)n : W.nslices, channels, 1);  // one-shot: per chunk too
-    W.iters = (uint32_t)((W.nslices + (uint64_t)W.A - 1) / (uint64_t)W.A);
-    for (int r = 0; r < n; ++r) {  // send -> recv copy of the tail (Comm::allreduce)
-      if ((const void*)recv[r] == (const void*)send[r]) continue;  // in place
-      const uint64_t body = W.chunk_bytes * (uint64_t)n;
-      if (n == 1 || chunk == 0) memcpy(recv[r], send[r], count * 4);
-      else if (count * 4 > body) memcpy((char*)recv[r] + body, (const char*)send[r] + body, count * 4 - body);
-    }
-    if (n == 1 || chunk == 0) continue;
-    std::vector<Prog> progs;
-    for (int r = 0; r < n; ++r)
-      for (int w = 0; w < channels; ++w) {
-        Prog p;
-        p.r = r; p.w = w;
-        p.done = W.iters == 0 || w >= W.A;  // pipelines past A sit the call out
-        progs.push_back(p);
-      }
-    for (;;) {
-      bool any = false, all_done = true;
-      const size_t np = progs.size();
-      const size_t start = schedule_seed ? (size_t)((rng >> 33) % np) : 0;
-      for (size_t j = 0; j < np; ++j) {
-        Prog& P = progs[(start + j) % np];
-        if (P.done) continue;
-        all_done = false;
-        // a random number of ops per turn for this program when seeded
-        int burst = 1;
-        if (schedule_seed) {
-          rng = rng * 6364136223846793005ull + 1442695040888963407ull;
-          burst = 1 + (int)((rng >> 40) % 4);
-        }
-        for (int b = 0; b < burst && !P.done; ++b) {
-          const bool ok = a == 2 ? read_step(W, P) : a == 1 ? oneshot_step(W, P) : ring_step(W, P);
-          if (!ok) break;
-          any = true;
-          ++steps;
-        }
-      }
-      if (schedule_seed) rng = rng * 6364136223846793005ull + 1442695040888963407ull;
-      if (all_done) break;
-      if (!any) return -1;  // deadlock
-    }
-    // the kernels' last action per pipeline that ran: advance the per-pair FIFO counters
-    for (int r = 0; r < n; ++r)
-      for (int w = 0; w < W.A; ++w) {
-        if (a == 2 || a == 1) {
-          const uint64_t m = a == 2 ? read_msgs_per_call(W.iters) : 1;  // one-shot: one message each way
-          for (int q = 0; q < n; ++q) {
-            if (q == r) continue;
-            W.tx_seq[r][(size_t)q * channels + w] += m;
-            W.rx_seq[r][(size_t)q * channels + w] += m;
-          }
-        } else {
-          const uint64_t m = (uint64_t)W.iters * ring_msgs_per_iter(n);
-          W.tx_seq[r][(size_t)mod_n(r + 1, n) * channels + w] += m;
-          W.rx_seq[r][(size_t)mod_n(r - 1, n) * channels + w] += m;
-        }
-      }
+    const int rc = run_call(W, (int)((algo >> (3 * call)) & 7), kCollAllReduce, count, send, recv, slice_bytes, min_slice,
+                            schedule_seed, rng, steps);
+    if (rc != 0) return rc;
+  }
+  if (steps_out) *steps_out = steps;
+  return 0;
+}
+
+// A sequence of calls of any collective on one simulated communicator state, as one communicator
+// runs them: call i is collective coll[i] (schedule.h Coll: 0 all-reduce over counts[i] elements,
+// 1 reduce-scatter / 2 all-gather of counts[i] elements per rank) on schedule sched[i] (the codes
+// of mnccl_sim_allreduce; the halves have the ring and the persistent read form only), with rank
+// r's buffers send[i * n + r] / recv[i * n + r] (in place as NCCL defines it; the tests size them).
+// The other arguments and the return value as mnccl_sim_allreduce.
+int mnccl_sim_collective(int n, int calls, const int* coll, const int* sched, const uint64_t* counts,
+                         const float* const* send, float* const* recv, int op, uint64_t slice_bytes,
+                         uint64_t min_slice, int channels, int slots, uint64_t schedule_seed, uint64_t* steps_out) {
+  if (n < 1 || n > 16 || channels < 1 || slots < 1 || slice_bytes < 4 || slice_bytes % 4 || calls < 0) return -2;
+  World W;
+  init_world(W, n, channels, slots, op, slice_bytes);
+  uint64_t steps = 0;
+  uint64_t rng = schedule_seed * 6364136223846793005ull + 1442695040888963407ull;
+  for (int call = 0; call < calls; ++call) {
+    const int c = coll[call];
+    if (c < kCollAllReduce || c > kCollAllGather || (c != kCollAllReduce && sched[call] != 0 && sched[call] != 2)) return -2;
+    const int rc = run_call(W, sched[call], c, counts[call], send + (size_t)call * n, recv + (size_t)call * n, slice_bytes,
+                            min_slice, schedule_seed, rng, steps);
+    if (rc != 0) return rc;
   }
   if (steps_out) *steps_out = steps;
   return 0;

@@ -78,6 +78,8 @@ SIGNATURES = {
     "ncclCommUserRank": (_I, [_VP, ctypes.POINTER(_I)]),
     "ncclCommCount": (_I, [_VP, ctypes.POINTER(_I)]),
     "ncclAllReduce": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
+    "ncclReduceScatter": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
+    "ncclAllGather": (_I, [_VP, _VP, _SZ, _I, _VP, _VP]),
     "mncclLocalReduce": (_I, [_VP, _VP, _VP, _SZ, _I, _I, _VP]),
     "mncclCommGetAsyncError": (_I, [_VP, ctypes.POINTER(_I)]),
     "mncclCommGetInfo": (_I, [_VP, ctypes.POINTER(CommInfo)]),
@@ -136,6 +138,16 @@ class Comm:
     def all_reduce(self, send_ptr, recv_ptr, count, dtype=ncclFloat, op=ncclSum, stream=0):
         """Returns the ncclResult_t (does not raise) -- the reference's calling convention."""
         return load().ncclAllReduce(send_ptr, recv_ptr, count, dtype, op, self.handle, stream)
+
+    def reduce_scatter(self, send_ptr, recv_ptr, recvcount, dtype=ncclFloat, op=ncclSum, stream=0):
+        """ncclReduceScatter: send holds nranks * recvcount elements, recv gets chunk `rank` of
+        their all-reduce (the same bits).  Returns the ncclResult_t."""
+        return load().ncclReduceScatter(send_ptr, recv_ptr, recvcount, dtype, op, self.handle, stream)
+
+    def all_gather(self, send_ptr, recv_ptr, sendcount, dtype=ncclFloat, stream=0):
+        """ncclAllGather: recv holds nranks * sendcount elements, rank q's send at
+        [q * sendcount, (q + 1) * sendcount).  Returns the ncclResult_t."""
+        return load().ncclAllGather(send_ptr, recv_ptr, sendcount, dtype, self.handle, stream)
 
     def rank(self):
         r = ctypes.c_int()
