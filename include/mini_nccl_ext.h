@@ -24,6 +24,12 @@
  *   ncclReduceScatter    recv = chunk `rank` of what ncclAllReduce would produce over send's
  *                        nranks * recvcount elements, bit for bit.
  *   ncclAllGather        recv = every rank's send, rank q's at element q * sendcount.
+ *
+ * and NCCL's two rooted collectives:
+ *
+ *   ncclBroadcast        every rank's recv = the root's send.
+ *   ncclReduce           the root's recv = the reduction of every rank's send (ncclAllReduce's bits
+ *                        when count is a multiple of nranks); nobody else's recv is touched.
  */
 #ifndef MINI_NCCL_EXT_H_
 #define MINI_NCCL_EXT_H_
@@ -52,7 +58,8 @@ extern "C" {
    prefix: retired_bytes, retired_budget, budget_refusals, window_fast, run_pipelines), window calls carry the
    schedule choice in their signature and skip the host rendezvous only when no two ranks share a
    GPU (MINI_NCCL_WINDOW_RENDEZVOUS); still 600: ncclReduceScatter and ncclAllGather were added
-   without a change to anything above -- a caller detects them by symbol */
+   without a change to anything above -- a caller detects them by symbol; still 600: ncclBroadcast
+   and ncclReduce were added the same way */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -189,6 +196,45 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
                                ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);
 ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype,
                            ncclComm_t comm, hipStream_t stream);
+
+/* The two rooted collectives, NCCL's signatures.
+ * ncclBroadcast: every rank's recvbuff ends up holding the root's `count` elements of sendbuff.
+ * sendbuff is read on the root only; elsewhere it is ignored and may be NULL.  In place on the root:
+ * sendbuff == recvbuff.  Any datatype ncclAllGather takes (no arithmetic).
+ * ncclReduce: the root's recvbuff ends up holding the reduction of every rank's `count` elements of
+ * sendbuff.  recvbuff is written on the root only; elsewhere it is ignored, may be NULL and is never
+ * touched.  In place on the root: recvbuff == sendbuff.  Datatypes and ops as ncclAllReduce.
+ * Association: with q = ceil(count / nranks), chunk c is elements [c * q, min((c + 1) * q, count)) --
+ * trailing chunks may be short or empty, and there is NO unreduced tail (ncclAllReduce's count %
+ * nranks elements are the reference's quirk, not these calls') -- and every element of chunk c is
+ * folded in ncclAllReduce's order for chunk c: acc = x_c, then acc = op(x_q, acc) for q = c + 1, ...,
+ * c - 1 (mod nranks).  So when count % nranks == 0 the root's result is ncclAllReduce's, bit for bit,
+ * and ncclReduce followed by ncclBroadcast from the same root gives it on every rank.  ncclBroadcast
+ * moves its data by the same partition.
+ * Argument checks, in this order: NULL comm: ncclInvalidArgument; count == 0: ncclSuccess (before the
+ * datatype is looked at or the communicator read); an unsupported datatype / op: ncclInternalError;
+ * then, with the communicator: root outside [0, nranks): ncclInvalidArgument; a NULL buffer this
+ * rank's role needs (ncclBroadcast: recvbuff anywhere, sendbuff on the root; ncclReduce: sendbuff
+ * anywhere, recvbuff on the root): ncclInvalidArgument; on the root, sendbuff and recvbuff overlapping
+ * without being equal: ncclInvalidArgument.  In the last three nothing is launched or negotiated and
+ * the communicator stays usable.  Ranks that disagree on the root or on the collective get
+ * ncclInvalidUsage on every rank where the call is negotiated (the read schedule's rendezvous), the
+ * communicator staying usable; no exception crosses the boundary.
+ * Blocking mode, stream ordering, graph capture, sticky errors and the watchdog as ncclAllReduce;
+ * nranks == 1 is a copy when the pointers differ.  Pinned host buffers go through their device
+ * mapping, pageable ones through the stage (and cannot be captured).
+ * Schedules: the read schedule where an all-reduce's larger calls would run it -- every rank folds
+ * (ncclReduce), or copies out of the root's send (ncclBroadcast), chunk `rank` only and stores it
+ * into the root's / every rank's recv, so the root's busiest link carries about 2 * bytes / nranks
+ * where a root doing all the work would put all `bytes` on each of its links (a count derived from
+ * the schedule: no run with ranks on distinct GPUs exists) -- otherwise the ring: a chain from the
+ * root for ncclBroadcast, ncclAllReduce's ring with the other ranks' stores masked off for
+ * ncclReduce.  mncclCommInfo_t.last_algo reports mncclAlgoRead or mncclAlgoRing.  No one-shot, grid
+ * or registered-window form. */
+ncclResult_t ncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
+                           ncclComm_t comm, hipStream_t stream);
+ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclRedOp_t op,
+                        int root, ncclComm_t comm, hipStream_t stream);
 
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream);

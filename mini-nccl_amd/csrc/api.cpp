@@ -160,6 +160,47 @@ ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcoun
   }
 }
 
+// The two rooted collectives (mini_nccl_ext.h).  The buffer a rank's role does not use may be NULL,
+// so the buffers are checked where the communicator's rank and size are known (Comm::collective),
+// with the root: after count == 0 and the datatype, as the header states.
+ncclResult_t ncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
+                           ncclComm_t comm, hipStream_t stream) {
+  if (!comm) return ncclInvalidArgument;
+  if (count == 0) return ncclSuccess;
+  RoctxRange range("mini_ncclBroadcast");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] Broadcast Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->broadcast(sendbuff, recvbuff, count, (int)datatype, root, stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] Broadcast Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
+ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclRedOp_t op,
+                        int root, ncclComm_t comm, hipStream_t stream) {
+  if (!comm) return ncclInvalidArgument;
+  if (count == 0) return ncclSuccess;
+  RoctxRange range("mini_ncclReduce");
+  if (!dtype_ok(datatype) || !op_ok(op)) {
+    fprintf(stderr, "[Mini-NCCL] Reduce Internal Error: unsupported %s\n", dtype_ok(datatype) ? "RedOp" : "DataType");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->reduce(sendbuff, recvbuff, count, (int)datatype, (int)op, root, stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] Reduce Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream) {
   if (!out || !local || !incoming) return ncclInvalidArgument;

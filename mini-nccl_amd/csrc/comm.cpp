@@ -143,6 +143,9 @@ void Comm::setup_device_resources() {
   hip_check(hipHostGetDevicePointer((void**)&d_ctl_, h_ctl_, 0), "ctl device pointer");
   hip_check(hipEventCreateWithFlags(&order_ev_, hipEventDisableTiming), "event");
   if (nranks_ > 1) {
+    // the kernels' code object onto this GPU now, not inside the first collective call (whose host
+    // time a stream-ordered caller sees): best effort, the first launch loads it otherwise
+    if (preload_kernels() != hipSuccess) (void)hipGetLastError();
     // from the process's pool (ipcreg.h): a communicator created after another one re-uses its
     // blocks and the peers' imports of them instead of exporting a re-used address
     scratch_ = (char*)ipc::pool_acquire(scratch_bytes_, hipDeviceMallocUncached, &scratch_h_, &scratch_id_);
@@ -579,7 +582,7 @@ void Comm::wait_previous_call() {
 
 void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, int dtype, int op, hipStream_t stream,
                   uint32_t seq, bool vec, const char* const* psend, const char* const* precv,
-                  size_t tail_bytes, uint64_t sig, int coll) {
+                  size_t tail_bytes, uint64_t sig, int coll, int root, size_t total_bytes) {
   const int n = nranks_;
   CollParams p;
   memset(&p, 0, sizeof p);
@@ -589,6 +592,12 @@ void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, in
   // the one-chunk buffer of a half, shifted so that chunk `rank` of it is the buffer itself
   if (coll == kCollReduceScatter) p.recv -= (size_t)rank_ * chunk_bytes;
   if (coll == kCollAllGather) p.send -= (size_t)rank_ * chunk_bytes;
+  // the rooted collectives: root_fold stores into the ROOT's recv on every rank (this rank's
+  // mapping of it); the ring's broadcast moves the whole buffer as one chunk down the chain
+  p.root = root;
+  p.total_bytes = total_bytes;
+  if (coll == kCollReduce && algo == 2 && rank_ != root) p.recv = const_cast<char*>(precv[root]);
+  if (coll == kCollBroadcast && algo != 2) chunk_bytes = total_bytes;
   p.chunk_bytes = chunk_bytes;
   // C: the pipelines this call may launch (run_pipes_, <= the layout's wave_channels())
   const int C = run_pipes();
@@ -635,6 +644,8 @@ void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, in
   hipError_t e = grid        ? launch_read_grid(dtype, op, p, stream, cfg_.grid_vectors)
                  : algo == 2 && coll == kCollReduceScatter ? launch_scatter_fold(dtype, op, vec, wg, nt, p, stream)
                  : algo == 2 && coll == kCollAllGather     ? launch_gather_push(dtype, vec, wg, nt, p, stream)
+                 : algo == 2 && coll == kCollReduce        ? launch_root_fold(dtype, op, vec, wg, nt, p, stream)
+                 : algo == 2 && coll == kCollBroadcast     ? launch_root_relay(dtype, vec, wg, nt, p, stream)
                  : algo == 2 ? launch_read(dtype, op, vec, wg, nt, p, stream)
                  : algo == 3 ? launch_oneshot(dtype, op, vec, wg, nt, p, stream)
                              : launch_ring(dtype, op, vec, wg, nt, p, stream);
@@ -647,16 +658,49 @@ void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, in
 // (schedule.h Coll; `count` per rank): ncclReduceScatter's send and ncclAllGather's recv hold
 // n * count elements, the other buffer one chunk of `count`.
 ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
-                              hipStream_t stream) {
+                              hipStream_t stream, int root) {
   if (sticky_ != ncclSuccess) return sticky_;
   if (check_status() != ncclSuccess) return sticky_;
   const int esz = dtype_size(dtype);
-  const bool half = coll != kCollAllReduce;
+  // rooted: ncclBroadcast / ncclReduce (`count` elements in both buffers, like the all-reduce);
+  // half: one of the all-reduce's halves.  Neither has a one-shot, grid or registered-window form.
+  const bool rooted = coll == kCollBroadcast || coll == kCollReduce;
+  const bool half = coll == kCollReduceScatter || coll == kCollAllGather;
+  const bool is_root = rooted && rank_ == root;
   const char* const coll_name = coll == kCollReduceScatter ? "ncclReduceScatter"
                                 : coll == kCollAllGather   ? "ncclAllGather"
+                                : coll == kCollBroadcast   ? "ncclBroadcast"
+                                : coll == kCollReduce      ? "ncclReduce"
                                                            : "ncclAllReduce";
-  // bytes: the larger buffer's (the all-reduce's: both)
+  // bytes: the larger buffer's (the all-reduce's and the rooted collectives': both)
   const size_t bytes = count * (size_t)esz * (half ? (size_t)nranks_ : 1);
+  if (rooted) {
+    // the caller's errors, in this order: nothing launched, nothing negotiated
+    if (root < 0 || root >= nranks_) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: root %d is outside [0, %d)\n", rank_, coll_name, root, nranks_);
+      return ncclInvalidArgument;
+    }
+    // the buffers this rank's role needs: Broadcast reads send on the root only, Reduce writes recv
+    // on the root only
+    const bool need_send = coll == kCollReduce || is_root, need_recv = coll == kCollBroadcast || is_root;
+    if ((need_send && !send) || (need_recv && !recv)) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: %s is NULL\n", rank_, coll_name, need_send && !send ? "sendbuff" : "recvbuff");
+      return ncclInvalidArgument;
+    }
+    const uintptr_t s0 = (uintptr_t)send, r0 = (uintptr_t)recv;
+    if (is_root && s0 != r0 && s0 < r0 + bytes && r0 < s0 + bytes) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: send and recv overlap and the call is not in place\n", rank_,
+              coll_name);
+      return ncclInvalidArgument;
+    }
+    // the buffer this rank's role does not use is ignored: its other buffer stands in for it in
+    // the rendezvous (so NULL never reaches the export / import / liveness logic) and in the
+    // kernel's arguments -- a non-root's Broadcast send is never read, its Reduce recv never written
+    if (!is_root) {
+      if (coll == kCollBroadcast) send = recv;
+      else recv = const_cast<void*>(send);
+    }
+  }
   if (half) {
     // in place as NCCL defines it (the one-chunk buffer is chunk `rank` of the other); any other
     // overlap of the two byte ranges is the caller's error: nothing launched, nothing negotiated
@@ -696,7 +740,9 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
 
   const int n = nranks_;
   uint32_t seq = 0;  // this call's kernel (0: the call launches none)
-  const size_t chunk = half ? count : n > 0 ? count / (size_t)n : 0;  // mini_nccl.cu:69
+  // (rooted: ceil -- the trailing chunks are short or empty and there is no unreduced tail)
+  const size_t chunk = half ? count : rooted ? (count + (size_t)n - 1) / (size_t)n
+                       : n > 0 ? count / (size_t)n : 0;  // mini_nccl.cu:69
   const size_t chunk_bytes = chunk * (size_t)esz;
   if (n == 1 || chunk == 0) {
     // nRanks == 1 returns after the copy (mini_nccl.cu:66); chunk == 0 moves no slice
@@ -720,8 +766,8 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // function of the call's size and the rank-uniform config up to the read rendezvous, which
     // all ranks decide alike.
     // (the halves have no one-shot form: read where an all-reduce's larger calls would, else the ring)
-    const bool oneshot = !half && algo_ == 3 && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), true);
-    const bool small = !half && auto_ && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), false);
+    const bool oneshot = !half && !rooted && algo_ == 3 && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), true);
+    const bool small = !half && !rooted && auto_ && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), false);
     // (auto, and a forced one-shot's larger calls, only where the topology allows the read
     // schedule: classify_topology; MINI_NCCL_ALGO=read forces it anywhere)
     const bool read_sched = !oneshot &&
@@ -730,7 +776,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // registered windows: the read schedule with no host rendezvous (no record to wait for, no
     // pointer query) -- every rank promised the same windows and offsets, the kernel checks it
     // (all-reduce only: a half whose buffers lie in windows is negotiated like any other call)
-    const Window* win_s = !half && read_sched && window_fast_ && !windows_.empty() ? find_window(send, bytes) : nullptr;
+    const Window* win_s = !half && !rooted && read_sched && window_fast_ && !windows_.empty() ? find_window(send, bytes) : nullptr;
     const Window* win_r = win_s ? find_window(recv, bytes) : nullptr;
     if (win_s && win_r) {
       const uint64_t os = (uint64_t)((const char*)send - win_s->base), orv = (uint64_t)((char*)recv - win_r->base);
@@ -786,8 +832,10 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       // a half is staged in its in-place layout: the one-chunk buffer is chunk `rank` of the stage
       const size_t s_off = coll == kCollAllGather ? mine : 0, r_off = coll == kCollReduceScatter ? mine : 0;
       if (rs == Reach::kStaged) {
-        hip_check(hipMemcpyAsync(stage_ + s_off, send, coll == kCollAllGather ? chunk_bytes : bytes, hipMemcpyDefault,
-                                 stream), "stage in");
+        // (Broadcast: only the root's send holds anything -- the others' stands for their recv)
+        if (coll != kCollBroadcast || is_root)
+          hip_check(hipMemcpyAsync(stage_ + s_off, send, coll == kCollAllGather ? chunk_bytes : bytes, hipMemcpyDefault,
+                                   stream), "stage in");
         ksend = stage_ + s_off;
       }
       if (rr == Reach::kStaged) krecv = stage_ + r_off;  // also in place when send is staged too
@@ -800,7 +848,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // buffer and never touches the tail, api.cpp:173-175 + mini_nccl.cu:69); the kernels
     // write every other element of recv and copy the tail themselves (kernels.hip copy_tail)
     const size_t body = chunk_bytes * (size_t)n;
-    const size_t tail = !half && ksend != krecv && bytes > body ? bytes - body : 0;
+    const size_t tail = !half && !rooted && ksend != krecv && bytes > body ? bytes - body : 0;
     // 16-byte vector path whenever every message's local base is dword-aligned (vectors may
     // straddle 16-byte boundaries on the local side; each message's last len % 16 bytes go
     // element by element); element-wise path otherwise (2-byte types with odd chunks)
@@ -823,7 +871,10 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
         d = pbuf_.negotiate(send, recv, eligible, count, dtype, op, cfg_.timeout_ms / 1000.0 + 2.0,
                             [this] { wait_previous_call(); }, psend, precv, &vec_all,
                             // (with the collective: ranks that call different ones get kMismatch)
-                            half ? ((auto_ ? 0xff : algo_) | coll << 8) : auto_ ? -1 : algo_);
+                            // (and a rooted one's root: ranks that differ in it get kMismatch too)
+                            half || rooted ? ((auto_ ? 0xff : algo_) | coll << 8 | (rooted ? root << 16 : 0))
+                            : auto_        ? -1
+                                           : algo_);
       } catch (const PeerGaveUp& e) {
         return rendezvous_failed(e, true, cur_dev);
       } catch (const std::exception& e) {
@@ -840,7 +891,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       }
       if (d == PeerBuffers::kMismatch) {
         fprintf(stderr, "[Mini-NCCL] rank %d: ranks called %s with different count / datatype / op / schedule "
-                "(mncclCommSetAlgo), or different collectives\n", rank_, coll_name);
+                "(mncclCommSetAlgo), different collectives, or a different root\n", rank_, coll_name);
         if (cur_dev != device_) hipSetDevice(cur_dev);
         return ncclInvalidUsage;
       }
@@ -854,8 +905,15 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     if (seq == 0) seq = ++call_seq_;  // 0 = "no kernel" (wait_for)
     if (ag_own_copy && algo == 0)
       hip_check(hipMemcpyAsync((char*)krecv + mine, ksend, chunk_bytes, hipMemcpyDefault, stream), "own chunk");
-    launch(algo, ksend, krecv, chunk_bytes, dtype, op, stream, seq, vec, psend, precv, tail, 0, coll);
-    if (rr == Reach::kStaged)
+    // the ring's broadcast leaves the root's recv alone (the root only sends): out of place, it gets
+    // the root's send by a stream-ordered copy before the launch, as the ring's all-gather gets its
+    // own chunk (root_relay stores it itself)
+    if (coll == kCollBroadcast && is_root && algo == 0 && ksend != krecv)
+      hip_check(hipMemcpyAsync(krecv, ksend, bytes, hipMemcpyDefault, stream), "root's own copy");
+    launch(algo, ksend, krecv, chunk_bytes, dtype, op, stream, seq, vec, psend, precv, tail, 0, coll, root,
+           rooted ? bytes : 0);
+    // (Reduce: only the root's recv is written -- the others' stands for their send)
+    if (rr == Reach::kStaged && (coll != kCollReduce || is_root))
       hip_check(hipMemcpyAsync(recv, krecv, coll == kCollReduceScatter ? chunk_bytes : bytes, hipMemcpyDefault, stream),
                 "stage out");
   }

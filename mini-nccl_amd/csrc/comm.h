@@ -43,6 +43,20 @@ class Comm {
     return collective(kCollAllGather, send, recv, count, dtype, kSum, stream);
   }
 
+  // The rooted collectives (NCCL's ncclBroadcast / ncclReduce over `count` elements): every rank's
+  // recv gets the root's send; the root's recv gets the reduction of every rank's send, chunk c of
+  // ceil(count / n) elements folded in the all-reduce's order for chunk c (no unreduced tail).  The
+  // buffer a rank's role does not use (a non-root's send / recv) is ignored and may be NULL.  The
+  // schedule choice is the halves': the read schedule (kernels.hip root_relay / root_fold), else
+  // the ring (schedule.h coll_op).  root outside [0, n), a NULL buffer the role needs, or a partial
+  // overlap on the root: ncclInvalidArgument, nothing launched or negotiated.
+  ncclResult_t broadcast(const void* send, void* recv, size_t count, int dtype, int root, hipStream_t stream) {
+    return collective(kCollBroadcast, send, recv, count, dtype, kSum, stream, root);
+  }
+  ncclResult_t reduce(const void* send, void* recv, size_t count, int dtype, int op, int root, hipStream_t stream) {
+    return collective(kCollReduce, send, recv, count, dtype, op, stream, root);
+  }
+
   int rank() const { return rank_; }
   int nranks() const { return nranks_; }
   int device() const { return device_; }
@@ -105,10 +119,12 @@ class Comm {
   // kernels get them shifted by rank * chunk_bytes and keep the all-reduce's index math
   void launch(int algo, const void* send, void* recv, size_t chunk_bytes, int dtype, int op, hipStream_t stream,
               uint32_t seq, bool vec, const char* const* psend = nullptr, const char* const* precv = nullptr,
-              size_t tail_bytes = 0, uint64_t sig = 0, int coll = kCollAllReduce);
-  // the one call path of the three collectives; count: the all-reduce's, else per rank
+              size_t tail_bytes = 0, uint64_t sig = 0, int coll = kCollAllReduce, int root = 0,
+              size_t total_bytes = 0);
+  // the one call path of the five collectives; count: the all-reduce's and the rooted ones', per
+  // rank for the halves
   ncclResult_t collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
-                          hipStream_t stream);
+                          hipStream_t stream, int root = 0);
   // one rendezvous failure of the read schedule, reported like the kernel's (sticky, peers aborted)
   ncclResult_t rendezvous_failed(const std::exception& e, bool peer_gave_up, int cur_dev);
   struct Window {

@@ -29,7 +29,7 @@ struct CollParams {
   const uint32_t* host_abort;  // host-mapped abort request
   uint32_t* started;       // host-mapped start word: the kernel writes call_seq when it begins
   uint32_t call_seq;       // this launch's sequence number (Comm::wait_for's deadline starts here)
-  int32_t coll;            // schedule.h Coll: 0 all-reduce, 1 reduce-scatter (recv holds one chunk: the
+  int32_t coll;            // schedule.h Coll (3 / 4: below): 0 all-reduce, 1 reduce-scatter (recv holds one chunk: the
                            // host passes recv - rank * chunk_bytes), 2 all-gather (send holds one
                            // chunk: the host passes send - rank * chunk_bytes).  In what was padding:
                            // the struct's size and every other offset are the all-reduce's
@@ -48,6 +48,11 @@ struct CollParams {
   uint64_t sig;               // registered-window call (no host rendezvous): this call's signature,
                               // sent with START and compared with every peer's before any peer
                               // buffer is touched (0: a negotiated call, nothing to check)
+  // the rooted collectives (coll 3 broadcast / 4 reduce): chunk_bytes is ceil(count / n) elements,
+  // so the trailing chunks may be short or empty and every slice is clamped to the buffer's end
+  // (schedule.h rooted_len); unused (0) by the other collectives
+  uint64_t total_bytes;       // count * element size
+  int32_t root;
 };
 
 constexpr int kMaxRanks = 16;
@@ -71,6 +76,14 @@ hipError_t launch_scatter_fold(int dtype, int op, bool vec, int channels, int th
                                const CollParams& p, hipStream_t stream);
 hipError_t launch_gather_push(int dtype, bool vec, int channels, int threads,
                               const CollParams& p, hipStream_t stream);
+// the read schedule's rooted collectives (p.coll 4 / 3; the same persistent form and protocol):
+// root_fold folds chunk `rank` of every rank's send into the ROOT's recv at the same offset (p.recv
+// is that buffer: the host passes its mapping of the root's recv on the other ranks); root_relay
+// copies chunk `rank` of the root's send into every rank's recv (by element size: no arithmetic)
+hipError_t launch_root_fold(int dtype, int op, bool vec, int channels, int threads,
+                            const CollParams& p, hipStream_t stream);
+hipError_t launch_root_relay(int dtype, bool vec, int channels, int threads,
+                             const CollParams& p, hipStream_t stream);
 // the read schedule's push form for large calls as three launches (start, grid fold, done):
 // schedule.h read_grid_fits(p.chunk_bytes, p.n, kReadGridFloor) (2 <= n <= 8, whole 16-byte vectors), p.go set
 // vectors: 0 = schedule.h read_grid_vectors; 1 / 2 / 4 (MINI_NCCL_GRID_VECTORS) for fp32 Sum only
@@ -87,6 +100,12 @@ hipError_t launch_local_reduce(int dtype, int op, void* out, const void* local,
 enum : int { kProbeSys = 0, kProbeNt = 1, kProbePlain = 2 };
 hipError_t launch_link_probe(char* local, char* const* remote, int nremote, uint64_t bytes, int form, bool pull,
                              hipStream_t stream);
+
+// Loads the library's gfx950 code object onto the current device now (the runtime otherwise does it
+// inside the process's first kernel launch, i.e. inside its first collective call: milliseconds of
+// host time that grow with every kernel the library ships).  Best effort: an error is returned, not
+// thrown, and the first launch then loads it as before.
+hipError_t preload_kernels();
 
 bool dtype_supported(int dtype);
 int dtype_size(int dtype);

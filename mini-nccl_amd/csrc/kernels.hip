@@ -16,6 +16,9 @@
 //                 its pushes without a fold; the same protocol, so calls of any kind follow each
 //                 other on one communicator.  Their fallback is ring_kernel with the op table of
 //                 one half (schedule.h coll_op).
+//  root_fold / root_relay   the rooted collectives (ncclReduce / ncclBroadcast) on the same
+//                 protocol: every rank folds, or copies out of the root's send, chunk `rank` only,
+//                 so no link carries the whole buffer.  Their fallback is ring_kernel too.
 //  read_start / read_grid / read_done   the read schedule's push form as three launches (the
 //                 runtime form mncclAlgoReadGrid, for large calls): a grid of one-batch workgroups
 //                 between a one-wave START and a one-wave DONE.
@@ -361,6 +364,7 @@ template <> struct KindBits<kReduceSend> { static constexpr int v = kHasLocal | 
 template <> struct KindBits<kReduceCopySend> { static constexpr int v = kHasLocal | kHasIn | kSends | kReduces | kWritesRecv; };
 template <> struct KindBits<kCopySend> { static constexpr int v = kHasIn | kSends | kWritesRecv; };
 template <> struct KindBits<kCopy> { static constexpr int v = kHasIn | kWritesRecv; };
+template <> struct KindBits<kForward> { static constexpr int v = kHasIn | kSends; };  // (kDrop moves nothing)
 
 constexpr int kU = 8;  // 16-byte vectors per lane per batch: 8 KiB per wave in flight per stream
 
@@ -505,10 +509,12 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) ring_kernel(Col
   u64* tx_ctr = p.tx_seq + (u64)next * C + w;
   u64* rx_ctr = p.rx_seq + (u64)prev * C + w;
   const u64 tx_base = *tx_ctr, rx_base = *rx_ctr;
-  // the op table of the call's collective (schedule.h coll_op: the all-reduce's ring, or one of
-  // its halves for ncclReduceScatter / ncclAllGather)
-  const int coll = p.coll;
-  const int mpi = coll_msgs_per_iter(coll, n);
+  // the op table of the call's collective (schedule.h coll_op: the all-reduce's ring, one of its
+  // halves for ncclReduceScatter / ncclAllGather, the chain of ncclBroadcast or the masked ring of
+  // ncclReduce); each link's counters advance by what the link carried (Broadcast's root-1 -> root
+  // carries nothing: coll_tx_msgs / coll_rx_msgs, the same value everywhere else)
+  const int coll = p.coll, root = p.root;
+  const int mpi_tx = coll_tx_msgs(coll, n, r, root), mpi_rx = coll_rx_msgs(coll, n, r, root);
   const u64* my_ready = p.mbox + mbox_ready(C, prev, w);
   const u64* my_credit = p.mbox + mbox_credit(n, C, next, w);
   u64* out_ready = p.peer_mbox[next] + mbox_ready(C, r, w);
@@ -517,12 +523,16 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) ring_kernel(Col
 
   for (uint32_t it = 0; it < p.iters; ++it) {
     const u64 s = (u64)it * A + w;
-    const uint32_t len = (uint32_t)slice_len(p.chunk_bytes, p.slice_bytes, s);
+    const uint32_t len0 = (uint32_t)slice_len(p.chunk_bytes, p.slice_bytes, s);
     const u64 soff = s * p.slice_bytes;
-    const u64 itoff = (u64)it * mpi;
     for (int k = 0; k < nops; ++k) {
-      const RingOp o = coll_op(coll, n, r, k);
-      const u64 rseq = rx_base + itoff + (u64)o.recv_msg, sseq = tx_base + itoff + (u64)o.send_msg;
+      const RingOp o = coll_op(coll, n, r, k, root);
+      const u64 rseq = rx_base + (u64)it * mpi_rx + (u64)o.recv_msg, sseq = tx_base + (u64)it * mpi_tx + (u64)o.send_msg;
+      // ncclReduce: the trailing chunks may be short or empty (every rank clamps chunk o.chunk alike;
+      // an empty message still moves its flags)
+      const uint32_t len = coll == kCollReduce ? (uint32_t)rooted_len(p.total_bytes, (u64)o.chunk * p.chunk_bytes,
+                                                                      p.chunk_bytes, p.slice_bytes, s)
+                                               : len0;
       bool ok = true;
       if (o.recv_msg >= 0) ok = wave_wait_ge(my_ready, rseq + 1, ctl, lane);
       if (ok && o.send_msg >= 0 && sseq + 1 > (u64)K) ok = wave_wait_ge(my_credit, sseq + 1 - K, ctl, lane);
@@ -531,7 +541,7 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) ring_kernel(Col
         return;
       }
       if (o.recv_msg >= 0) acquire_sys(p.sys_fence);
-      if (len) {
+      if (len && o.kind != kDrop) {
         const u64 coff = (u64)o.chunk * p.chunk_bytes + soff;
         const rsrc_t in = make_rsrc(msg_slot(p, C, prev, r, w, rseq), len);
         const rsrc_t out = make_rsrc(msg_slot(p, C, r, next, w, sseq), len);
@@ -542,6 +552,7 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) ring_kernel(Col
           case kReduceSend: move<T, OPC, VEC, kReduceSend>(lsrc, ldst, in, out, len, lane); break;
           case kReduceCopySend: move<T, OPC, VEC, kReduceCopySend>(lsrc, ldst, in, out, len, lane); break;
           case kCopySend: move<T, OPC, VEC, kCopySend>(lsrc, ldst, in, out, len, lane); break;
+          case kForward: move<T, OPC, VEC, kForward>(lsrc, ldst, in, out, len, lane); break;
           default: move<T, OPC, VEC, kCopy>(lsrc, ldst, in, out, len, lane); break;
         }
       }
@@ -553,8 +564,8 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) ring_kernel(Col
     }
   }
   if (lane == 0) {
-    *tx_ctr = tx_base + (u64)p.iters * mpi;
-    *rx_ctr = rx_base + (u64)p.iters * mpi;
+    *tx_ctr = tx_base + (u64)p.iters * mpi_tx;
+    *rx_ctr = rx_base + (u64)p.iters * mpi_rx;
   }
 }
 
@@ -674,7 +685,9 @@ __device__ __forceinline__ void st_own16(rsrc_t r, uint32_t off, v4u v) {
 }
 
 // PUSH = false (scatter_fold, ncclReduceScatter): the same fold stored into this rank's recv only.
-template <typename T, int OPC, int G, int V, bool PUSH = true>
+// SYS (root_fold, ncclReduce: p.recv is the ROOT's recv, another agent's memory on every rank but
+// the root): the one store is a push and stays sc0 sc1 whatever MNCCL_OWN_NT says.
+template <typename T, int OPC, int G, int V, bool PUSH = true, bool SYS = false>
 __device__ __forceinline__ void read_fold_all(const CollParams& p, uint64_t coff, uint32_t nvec, int lane) {
   constexpr uint32_t step = 64 * V;
   const int n = p.n, r = p.rank, w = wave_id().w;
@@ -708,7 +721,10 @@ __device__ __forceinline__ void read_fold_all(const CollParams& p, uint64_t coff
         for (int u = 0; u < V; ++u) a[u] = reduce16<T, OPC>(x[g][u], a[u]);
       }
 #pragma unroll
-    for (int u = 0; u < V; ++u) st_own16(out, (b + (uint32_t)(u * 64 + lane)) * 16, a[u]);
+    for (int u = 0; u < V; ++u) {
+      if (SYS) st_slot16(out, (b + (uint32_t)(u * 64 + lane)) * 16, a[u]);
+      else st_own16(out, (b + (uint32_t)(u * 64 + lane)) * 16, a[u]);
+    }
 #pragma unroll
     for (int g = 0; g < (PUSH ? G : 0); ++g)
       if (g + 1 < n) {
@@ -736,7 +752,7 @@ __device__ __forceinline__ void read_fold_all(const CollParams& p, uint64_t coff
 
 // Returns the leading bytes of the slice whose result it also pushed to the peers (PUSH = false:
 // nothing is pushed and the value means nothing).
-template <typename T, int OPC, bool VEC, bool PUSH = true>
+template <typename T, int OPC, bool VEC, bool PUSH = true, bool SYS = false>
 __device__ __forceinline__ uint32_t read_fold(const CollParams& p, uint64_t coff, uint32_t nbytes, int lane) {
   if (!VEC) {
     read_fold_scalar<T, OPC>(p, coff, nbytes, lane, 0);
@@ -749,10 +765,10 @@ __device__ __forceinline__ uint32_t read_fold(const CollParams& p, uint64_t coff
     // variants within 256 registers without spilling)
     constexpr int h = sizeof(T) == 2 ? 1 : 0;
     if (!nvec) {
-    } else if (n == 2) read_fold_all<T, OPC, 1, 12 - 4 * h, PUSH>(p, coff, nvec, lane);
-    else if (n == 3) read_fold_all<T, OPC, 2, 8 - 2 * h, PUSH>(p, coff, nvec, lane);
-    else if (n <= 5) read_fold_all<T, OPC, 4, 4 - h, PUSH>(p, coff, nvec, lane);
-    else read_fold_all<T, OPC, 7, 3 - h, PUSH>(p, coff, nvec, lane);
+    } else if (n == 2) read_fold_all<T, OPC, 1, 12 - 4 * h, PUSH, SYS>(p, coff, nvec, lane);
+    else if (n == 3) read_fold_all<T, OPC, 2, 8 - 2 * h, PUSH, SYS>(p, coff, nvec, lane);
+    else if (n <= 5) read_fold_all<T, OPC, 4, 4 - h, PUSH, SYS>(p, coff, nvec, lane);
+    else read_fold_all<T, OPC, 7, 3 - h, PUSH, SYS>(p, coff, nvec, lane);
     if (nbytes & 15u) read_fold_scalar<T, OPC>(p, coff, nbytes, lane, nvec * 16);
     return nvec * 16;
   }
@@ -889,7 +905,9 @@ aborted:
 // calls only (no registered windows): no signature to compare.  read_kernel keeps its own copy of
 // the protocol: its fold sits at the 256-register bound and must compile to what it was.
 // body(coff, len, lane): the slice at byte coff = r * chunk_bytes + s * slice_bytes, len bytes long.
-template <typename Body>
+// ROOTED (root_fold / root_relay): the chunks are ceil(count / n) elements, so each slice's length
+// is additionally clamped to the buffer's end (schedule.h rooted_len).
+template <bool ROOTED = false, typename Body>
 __device__ __forceinline__ void read_half(const CollParams& p, u64 (*s_tx)[kMaxRanks], u64 (*s_rx)[kMaxRanks],
                                           const Body& body) {
   signal_start(p);
@@ -916,7 +934,8 @@ __device__ __forceinline__ void read_half(const CollParams& p, u64 (*s_tx)[kMaxR
   acquire_sys(p.sys_fence);
   for (uint32_t j = 0; j < iters; ++j) {
     const u64 s = (u64)j * A + w;
-    const uint32_t len = (uint32_t)slice_len(p.chunk_bytes, p.slice_bytes, s);
+    const uint32_t len = ROOTED ? (uint32_t)rooted_len(p.total_bytes, (u64)r * p.chunk_bytes, p.chunk_bytes, p.slice_bytes, s)
+                                : (uint32_t)slice_len(p.chunk_bytes, p.slice_bytes, s);
     const u64 coff = (u64)r * p.chunk_bytes + s * p.slice_bytes;
     if (len) body(coff, len, lane);
   }
@@ -1045,6 +1064,141 @@ template <int ESZ, bool VEC>
 __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) gather_push(CollParams p) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { gather_slice<ESZ, VEC>(p, coff, len, lane); });
+}
+
+// ---------------------------------------------------------------- the rooted collectives
+// ncclReduce (root_fold) and ncclBroadcast (root_relay) on device buffers every rank can share,
+// in read_half's protocol message for message.  Neither lets the root do the work: a root that
+// folded or pushed everything itself would move the whole buffer B over each of its links while
+// every other link idled.  Here every rank works on chunk `rank` (ceil(count / n) elements, the
+// trailing chunks short or empty), so each link into the root carries about 2B/n (derived from the
+// schedule, not measured: no run with ranks on distinct GPUs exists).
+//
+// Reduce: rank r folds its slices of chunk r from all n send buffers -- read_fold's fold, order,
+// batching and unconditional prefetch -- and stores the result at the same offset of the ROOT's
+// recv: p.recv is the root's recv on every rank (Comm::launch passes this rank's mapping of it), so
+// the fold helpers address it as scatter_fold's do.  On every rank but the root that store is a
+// push into another agent's memory and needs the all-reduce's push-visibility guarantee (file
+// header): sc0 sc1, whatever MNCCL_OWN_NT says (SYS).  A non-root rank writes nothing to a buffer
+// of its own.  In place on the root (recv == send): the reduce-scatter's argument -- only rank c
+// reads chunk c of anyone's send, and it stores a batch after that batch's loads.  Each GPU's HBM
+// serves n chunk reads, the root's also takes n chunk writes; a link into the root carries the
+// root's loads of chunk `root` and rank r's pushed chunk (derived).
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) root_fold(CollParams p) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half<true>(p, s_tx, s_rx,
+                  [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, OPC, VEC, false, true>(p, coff, len, lane); });
+}
+
+// Broadcast: rank r copies its slices of chunk r from the root's send -- sc0 sc1 loads over the
+// link, as the fold loads its peers; the root reads its own send non-temporal, as gather_push does
+// (ROOT) -- into its own recv and into the recv of every other rank: gather_slice's shape with
+// another source and destination set.  The root's recv is a destination like any other when the
+// root's call is out of place (so the root's own copy happens inside the kernel, chunk by chunk,
+// by the rank that loaded the chunk anyway) and is left out when it is in place: every rank sees
+// that from its mappings, peer_send[root] == peer_recv[root] (were the test ever wrong, the push
+// would store the bytes just loaded from that address: only rank c touches chunk c).  So a
+// non-root rank pushes into n - 2 peers (n - 1 with the root's recv), the root into n - 1; at
+// n = 2 there is no relay.  The root's links carry 2B/n each, the others B/n (derived).
+// Destination j of D, in ring order from r + 1 and skipping the root when it is left out:
+__device__ __forceinline__ int relay_peer(int n, int r, int j, int skip) {  // skip: ring distance to the root, 0 = none
+  const int k = 1 + j;
+  return direct_peer(n, r, skip && k >= skip ? k + 1 : k);
+}
+
+// 16-byte vectors of one slice: gather_push_vec's two batches in flight (the next batch's loads
+// leave unconditionally: past the slice they fall outside the buffer resource, return 0 and touch
+// nothing), the pushes starting at destination w mod D so a rank's pipelines spread over the
+// links; G descriptor slots up to 8 ranks, G = 0: the destinations in a loop.
+template <int G, int V, bool ROOT>
+__device__ __forceinline__ void relay_vec(const CollParams& p, const char* from, uint64_t coff, uint32_t nvec, int lane,
+                                          bool own, int D, int skip) {
+  constexpr uint32_t step = 64 * V;
+  constexpr int GS = G > 0 ? G : 1;
+  const int n = p.n, r = p.rank, w = wave_id().w;
+  const uint32_t vb = nvec * 16;
+  const rsrc_t src = make_rsrc(from + coff, vb), out = make_rsrc(p.recv + coff, own ? vb : 0u);
+  rsrc_t pout[GS];
+#pragma unroll
+  for (int g = 0; g < G; ++g) pout[g] = make_rsrc(p.peer_recv[relay_peer(n, r, g < D ? (g + w) % D : 0, skip)] + coff, g < D ? vb : 0u);
+  v4u xa[V], xb[V];
+  auto load = [&](v4u(&x)[V], uint32_t b) {
+#pragma unroll
+    for (int u = 0; u < V; ++u)
+      x[u] = ROOT ? ld_nt16(src, (b + (uint32_t)(u * 64 + lane)) * 16) : ld_slot16(src, (b + (uint32_t)(u * 64 + lane)) * 16);
+  };
+  auto store = [&](v4u(&x)[V], uint32_t b) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) st_own16(out, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+    if (G > 0) {
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+        if (g < D) {
+#pragma unroll
+          for (int u = 0; u < V; ++u) st_slot16(pout[g], (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+        }
+    } else {
+      for (int j = 0; j < D; ++j) {
+        const rsrc_t po = make_rsrc(p.peer_recv[relay_peer(n, r, (j + w) % D, skip)] + coff, vb);
+#pragma unroll
+        for (int u = 0; u < V; ++u) st_slot16(po, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+      }
+    }
+  };
+  uint32_t b = 0;
+  load(xa, b);
+  for (;;) {
+    load(xb, b + step);
+    store(xa, b);
+    if ((b += step) >= nvec) break;
+    load(xa, b + step);
+    store(xb, b);
+    if ((b += step) >= nvec) break;
+  }
+}
+
+// slice `nbytes` at byte `coff` of the root's send into the same offset of every recv; the last
+// nbytes % 16 bytes, and everything without VEC, element by element
+template <int ESZ, bool VEC, bool ROOT>
+__device__ __forceinline__ void relay_slice(const CollParams& p, uint64_t coff, uint32_t nbytes, int lane) {
+  const int n = p.n, r = p.rank, root = p.root;
+  const bool root_in_place = p.peer_send[root] == p.peer_recv[root];
+  const bool own = !(ROOT && root_in_place);  // the root in place: its chunk already is in its recv
+  const int skip = !ROOT && root_in_place ? mod_n(root - r, n) : 0;
+  const int D = n - 1 - (skip ? 1 : 0);
+  const char* from = ROOT ? p.send : p.peer_send[root];
+  uint32_t done = 0;
+  if (VEC) {
+    const uint32_t nvec = nbytes >> 4;
+    if (!nvec) {
+    } else if (n == 2) relay_vec<1, kGatherV, ROOT>(p, from, coff, nvec, lane, own, D, skip);
+    else if (n == 3) relay_vec<2, kGatherV, ROOT>(p, from, coff, nvec, lane, own, D, skip);
+    else if (n <= 5) relay_vec<4, kGatherV, ROOT>(p, from, coff, nvec, lane, own, D, skip);
+    else if (n <= 8) relay_vec<7, kGatherV, ROOT>(p, from, coff, nvec, lane, own, D, skip);
+    else relay_vec<0, kGatherV, ROOT>(p, from, coff, nvec, lane, own, D, skip);
+    done = nvec * 16;
+  }
+  if (done == nbytes) return;
+  typedef Scal<ESZ> S;
+  const rsrc_t src = make_rsrc(from + coff, nbytes), out = make_rsrc(p.recv + coff, own ? nbytes : 0u);
+  const uint32_t ne = nbytes / ESZ;
+  for (uint32_t i = done / ESZ + (uint32_t)lane; i < ne; i += 64) {
+    const typename S::U v = S::ld(src, i * (uint32_t)ESZ);
+    S::st(out, i * (uint32_t)ESZ, v);
+    for (int j = 0; j < D; ++j) S::st(make_rsrc(p.peer_recv[relay_peer(n, r, j, skip)] + coff, nbytes), i * (uint32_t)ESZ, v);
+  }
+}
+
+// No arithmetic, so by element size only.  Only rank c ever writes chunk c of any recv, nobody
+// reads a recv inside the call, and the root's send is only read (in place: see above).
+template <int ESZ, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) root_relay(CollParams p) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  if (p.rank == p.root)
+    read_half<true>(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { relay_slice<ESZ, VEC, true>(p, coff, len, lane); });
+  else
+    read_half<true>(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { relay_slice<ESZ, VEC, false>(p, coff, len, lane); });
 }
 
 // ---------------------------------------------------------------- read schedule, grid form
@@ -1447,6 +1601,12 @@ static hipError_t local_for_t(int op, void* out, const void* a, const void* b, u
   return hipGetLastError();
 }
 
+hipError_t preload_kernels() {
+  // asking for any kernel's attributes makes the runtime load the whole code object for this device
+  hipFuncAttributes attr;
+  return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&read_start_kernel));
+}
+
 hipError_t launch_ring(int dtype, int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
 #define M(T) return ring_for_t<T>(op, vec, C, nt, p, st)
   MNCCL_DISPATCH_T(dtype, M)
@@ -1493,6 +1653,43 @@ hipError_t launch_gather_push(int dtype, bool vec, int C, int nt, const CollPara
     default: return hipErrorInvalidValue;
   }
 #undef GATHER_CASE
+  return hipGetLastError();
+}
+
+template <typename T>
+static hipError_t root_fold_for_t(int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
+#define ROOT_FOLD_CASE(OPC)                                                                     \
+  case OPC:                                                                                      \
+    if (vec) hipLaunchKernelGGL((root_fold<T, OPC, true>), dim3(C), dim3(nt), 0, st, p);        \
+    else hipLaunchKernelGGL((root_fold<T, OPC, false>), dim3(C), dim3(nt), 0, st, p);           \
+    break;
+  switch (op) {
+    ROOT_FOLD_CASE(kSum) ROOT_FOLD_CASE(kProd) ROOT_FOLD_CASE(kMax) ROOT_FOLD_CASE(kMin)
+    default: return hipErrorInvalidValue;
+  }
+#undef ROOT_FOLD_CASE
+  return hipGetLastError();
+}
+
+hipError_t launch_root_fold(int dtype, int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
+  if (p.coll != kCollReduce || p.root < 0 || p.root >= p.n) return hipErrorInvalidValue;
+#define M(T) return root_fold_for_t<T>(op, vec, C, nt, p, st)
+  MNCCL_DISPATCH_T(dtype, M)
+#undef M
+}
+
+hipError_t launch_root_relay(int dtype, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
+  if (p.coll != kCollBroadcast || p.root < 0 || p.root >= p.n) return hipErrorInvalidValue;
+#define RELAY_CASE(ESZ)                                                                          \
+  case ESZ:                                                                                      \
+    if (vec) hipLaunchKernelGGL((root_relay<ESZ, true>), dim3(C), dim3(nt), 0, st, p);          \
+    else hipLaunchKernelGGL((root_relay<ESZ, false>), dim3(C), dim3(nt), 0, st, p);             \
+    break;
+  switch (dtype_size(dtype)) {
+    RELAY_CASE(2) RELAY_CASE(4) RELAY_CASE(8)
+    default: return hipErrorInvalidValue;
+  }
+#undef RELAY_CASE
   return hipGetLastError();
 }
 

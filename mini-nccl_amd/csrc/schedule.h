@@ -44,7 +44,11 @@ enum RingKind : int {
   kReduceSend = 1,      // out <- op(local, in)
   kReduceCopySend = 2,  // v = op(local, in); recv <- v; out <- v
   kCopySend = 3,        // recv <- in; out <- in
-  kCopy = 4             // recv <- in
+  kCopy = 4,            // recv <- in
+  // the rooted reduce's ring on the ranks that are not the root: the all-reduce's second phase
+  // with its stores into recv masked off (coll_op)
+  kForward = 5,         // out <- in
+  kDrop = 6             // the message is received and dropped
 };
 
 struct RingOp {
@@ -104,17 +108,56 @@ MNCCL_HD RingOp ring_op(int n, int r, int k) {
 //     op 0       : send chunk r
 //     op 1..n-2  : receive chunk (r-k) mod n, store, forward
 //     op n-1     : receive chunk (r+1) mod n, store
-enum Coll : int { kCollAllReduce = 0, kCollReduceScatter = 1, kCollAllGather = 2 };
+//
+// The two rooted collectives (ncclBroadcast / ncclReduce; `root` is rank-uniform).  Their chunks
+// are q = ceil(count / n) elements, the trailing ones short or empty (rooted_len): no tail.
+//   Broadcast (1 op, 1 message per iteration on every link but root-1 -> root, which carries
+//   nothing: each link's counters advance by what it carried, coll_tx_msgs / coll_rx_msgs, so
+//   sender and receiver of every link agree): the whole buffer is ONE chunk, slice-pipelined down
+//   the chain root -> root+1 -> ... -> root-1:
+//     root              : send
+//     the ranks between : receive, store, forward
+//     root-1            : receive, store
+//   Reduce (the all-reduce's 2n - 1 ops and 2(n-1) messages): the all-reduce's table, on every rank
+//   but the root with the stores into recv masked off -- kReduceCopySend becomes kReduceSend,
+//   kCopySend kForward, kCopy kDrop -- so the root's recv has the all-reduce's association by
+//   construction and nobody else's recv is touched.
+enum Coll : int { kCollAllReduce = 0, kCollReduceScatter = 1, kCollAllGather = 2, kCollBroadcast = 3, kCollReduce = 4 };
 
 MNCCL_HD int coll_num_ops(int coll, int n) {
-  return coll == kCollReduceScatter ? n + 1 : coll == kCollAllGather ? n : ring_num_ops(n);
+  return coll == kCollReduceScatter ? n + 1 : coll == kCollAllGather ? n : coll == kCollBroadcast ? 1 : ring_num_ops(n);
 }
+// messages per iteration on a link that carries the collective (Broadcast: all but root-1 -> root)
 MNCCL_HD int coll_msgs_per_iter(int coll, int n) {
-  return coll == kCollReduceScatter ? n : coll == kCollAllGather ? n - 1 : ring_msgs_per_iter(n);
+  return coll == kCollReduceScatter ? n
+         : coll == kCollAllGather   ? n - 1
+         : coll == kCollBroadcast   ? 1
+                                    : ring_msgs_per_iter(n);
 }
-MNCCL_HD RingOp coll_op(int coll, int n, int r, int k) {
-  if (coll != kCollReduceScatter && coll != kCollAllGather) return ring_op(n, r, k);
+// messages per iteration rank r sends to r+1 / receives from r-1: what its counters advance by
+MNCCL_HD int coll_tx_msgs(int coll, int n, int r, int root) {
+  return coll == kCollBroadcast && mod_n(r - root, n) == n - 1 ? 0 : coll_msgs_per_iter(coll, n);
+}
+MNCCL_HD int coll_rx_msgs(int coll, int n, int r, int root) {
+  return coll == kCollBroadcast && r == root ? 0 : coll_msgs_per_iter(coll, n);
+}
+MNCCL_HD RingOp coll_op(int coll, int n, int r, int k, int root = 0) {
   RingOp o;
+  if (coll == kCollBroadcast) {
+    const int pos = mod_n(r - root, n);  // place in the chain
+    o.kind = pos == 0 ? kSend : pos < n - 1 ? kCopySend : kCopy;
+    o.chunk = 0;
+    o.send_msg = pos < n - 1 ? 0 : -1;
+    o.recv_msg = pos > 0 ? 0 : -1;
+    return o;
+  }
+  if (coll == kCollReduce) {
+    o = ring_op(n, r, k);
+    if (r != root)
+      o.kind = o.kind == kReduceCopySend ? kReduceSend : o.kind == kCopySend ? kForward : o.kind == kCopy ? kDrop : o.kind;
+    return o;
+  }
+  if (coll != kCollReduceScatter && coll != kCollAllGather) return ring_op(n, r, k);
   const int last = coll_num_ops(coll, n) - 1;
   if (k == 0) {
     o.kind = kSend; o.chunk = r; o.send_msg = 0; o.recv_msg = -1;
@@ -160,6 +203,17 @@ MNCCL_HD uint64_t slice_len(uint64_t chunk_bytes, uint64_t slice_bytes, uint64_t
   if (off >= chunk_bytes) return 0;
   const uint64_t rest = chunk_bytes - off;
   return rest < slice_bytes ? rest : slice_bytes;
+}
+
+// The rooted collectives' slices (ncclBroadcast / ncclReduce): the buffer's `total_bytes` are cut
+// into n chunks of chunk_bytes = ceil(count / n) elements, so the trailing chunks may be short or
+// empty -- slice s of the chunk at byte `chunk_off` is additionally clamped to the buffer's end,
+// and a slice at or past the end has length 0 and touches nothing.
+MNCCL_HD uint64_t rooted_len(uint64_t total_bytes, uint64_t chunk_off, uint64_t chunk_bytes, uint64_t slice_bytes,
+                             uint64_t s) {
+  const uint64_t len = slice_len(chunk_bytes, slice_bytes, s), off = chunk_off + s * slice_bytes;
+  if (off >= total_bytes) return 0;
+  return len < total_bytes - off ? len : total_bytes - off;
 }
 
 // Payload bytes per message for one call: the configured slice for large chunks; for chunks

@@ -7,7 +7,8 @@
 //   * that the per-channel sequence bases carried across calls keep flags consistent.
 // mnccl_sim_collective runs sequences of all-reduce / reduce-scatter / all-gather calls on one
 // such state (the halves: schedule.h coll_op on the ring, kernels.hip scatter_fold / gather_push on
-// the read schedule).
+// the read schedule).  mnccl_sim_rooted adds ncclBroadcast / ncclReduce with a root per call (the
+// ring's chain and masked ring, kernels.hip root_relay / root_fold), interleaved with the others.
 // fp32 only (the schedule does not depend on the element type); ops as reference
 // mini_nccl.cu:38-41 with a = local, b = incoming.
 #include <stdint.h>
@@ -35,6 +36,8 @@ struct World {
   int coll = kCollAllReduce;  // the current call's collective (schedule.h Coll); for a half, the
                               // one-chunk buffer's pointer is shifted as Comm::launch shifts it
   std::vector<char> own;      // all-gather: per rank, whether the read kernel stores the own chunk
+  int root = 0;               // the rooted collectives: the call's root and the buffer's bytes (their
+  uint64_t total_bytes = 0;   // chunks are ceil(count / n) elements: schedule.h rooted_len)
   int A = 0;  // pipelines the current call runs (schedule.h call_pipelines)
   uint64_t slice, slot_bytes, chunk_bytes, nslices;  // payload per message, slot stride
   uint32_t iters;
@@ -65,6 +68,7 @@ void do_move(int kind, int op, const float* local, const float* in, float* recv,
       case kReduceCopySend: v = apply(op, local[i], in[i]); break;
       default: v = in[i]; break;
     }
+    if (kind == kDrop) continue;
     if (kind == kReduceCopySend || kind == kCopySend || kind == kCopy) recv[i] = v;
     if (kind != kCopy) out[i] = v;
   }
@@ -83,13 +87,17 @@ bool ring_step(World& W, Prog& P) {
   const int n = W.n, r = P.r, w = P.w, K = W.K;
   const int prev = mod_n(r - 1, n), next = mod_n(r + 1, n);
   const uint64_t tx_base = W.tx_seq[r][(size_t)next * W.C + w], rx_base = W.rx_seq[r][(size_t)prev * W.C + w];
-  const int mpi = coll_msgs_per_iter(W.coll, n);
+  // each link's counters advance by what it carried (Broadcast's root-1 -> root: nothing)
+  const int mpi_tx = coll_tx_msgs(W.coll, n, r, W.root), mpi_rx = coll_rx_msgs(W.coll, n, r, W.root);
   const uint64_t s = (uint64_t)P.it * W.A + w;  // slice s on pipeline s mod A (kernels.hip ring_kernel)
-  const uint64_t len = slice_len(W.chunk_bytes, W.slice, s);
   const uint64_t soff = s * W.slice;
-  const uint64_t itoff = (uint64_t)P.it * mpi;
-  const RingOp o = coll_op(W.coll, n, r, P.k);
-  const uint64_t rseq = rx_base + itoff + (uint64_t)o.recv_msg, sseq = tx_base + itoff + (uint64_t)o.send_msg;
+  const RingOp o = coll_op(W.coll, n, r, P.k, W.root);
+  // ncclReduce: the message's length is clamped to the buffer's end for its chunk
+  const uint64_t len = W.coll == kCollReduce
+                           ? rooted_len(W.total_bytes, (uint64_t)o.chunk * W.chunk_bytes, W.chunk_bytes, W.slice, s)
+                           : slice_len(W.chunk_bytes, W.slice, s);
+  const uint64_t rseq = rx_base + (uint64_t)P.it * mpi_rx + (uint64_t)o.recv_msg,
+                 sseq = tx_base + (uint64_t)P.it * mpi_tx + (uint64_t)o.send_msg;
   if (o.recv_msg >= 0 && W.ready(r, prev, w) < rseq + 1) return false;
   if (o.send_msg >= 0 && sseq + 1 > (uint64_t)K && W.credit(r, next, w) < sseq + 1 - K) return false;
   if (len) {
@@ -120,9 +128,14 @@ bool read_step(World& W, Prog& P) {
   auto tx = [&](int d) { return W.tx_seq[r][(size_t)d * W.C + w]; };
   auto rx = [&](int q) { return W.rx_seq[r][(size_t)q * W.C + w]; };
   const uint64_t mpc = read_msgs_per_call(W.iters);
+  const bool rooted = W.coll == kCollBroadcast || W.coll == kCollReduce;
+  auto slice_bytes_of = [&](uint64_t s) {  // kernels.hip read_half<ROOTED>
+    return rooted ? rooted_len(W.total_bytes, (uint64_t)r * W.chunk_bytes, W.chunk_bytes, W.slice, s)
+                  : slice_len(W.chunk_bytes, W.slice, s);
+  };
   auto fold = [&](uint32_t it) {  // slice `it` of chunk r, stored and pushed
     const uint64_t s = (uint64_t)it * W.A + w;
-    const uint64_t len = slice_len(W.chunk_bytes, W.slice, s);
+    const uint64_t len = slice_bytes_of(s);
     const uint64_t coff = (uint64_t)r * W.chunk_bytes + s * W.slice;
     const float* local = (const float*)((const char*)W.send[r] + coff);
     std::vector<float> res((size_t)(len / 4));
@@ -136,6 +149,11 @@ bool read_step(World& W, Prog& P) {
     }
     // every load of the slice came first (in place, recv chunk r of a peer is its send chunk r)
     if (len) {
+      // (kernels.hip root_fold: the one store goes into the ROOT's recv, nothing into this rank's)
+      if (W.coll == kCollReduce) {
+        memcpy((char*)W.recv[W.root] + coff, res.data(), (size_t)len);
+        return;
+      }
       memcpy((char*)W.recv[r] + coff, res.data(), (size_t)len);
       // (kernels.hip scatter_fold: the fold with no pushes -- W.recv[r] is recv - r * chunk_bytes)
       if (W.coll == kCollReduceScatter) return;
@@ -152,6 +170,18 @@ bool read_step(World& W, Prog& P) {
     const char* src = (const char*)W.send[r] + coff;
     if (W.own[(size_t)r]) memcpy((char*)W.recv[r] + coff, src, (size_t)len);
     for (int k = 1; k < n; ++k) memcpy((char*)W.recv[direct_peer(n, r, (k - 1 + w) % (n - 1) + 1)] + coff, src, (size_t)len);
+  };
+  // kernels.hip root_relay: slice `it` of chunk r of the ROOT's send into every rank's recv -- the
+  // root's own only when its call is out of place (seen from the buffers, as the kernel does)
+  auto relay = [&](uint32_t it) {
+    const uint64_t s = (uint64_t)it * W.A + w;
+    const uint64_t len = slice_bytes_of(s);
+    const uint64_t coff = (uint64_t)r * W.chunk_bytes + s * W.slice;
+    if (!len) return;
+    const bool root_in_place = (const void*)W.send[W.root] == (const void*)W.recv[W.root];
+    std::vector<char> v((const char*)W.send[W.root] + coff, (const char*)W.send[W.root] + coff + len);
+    for (int q = 0; q < n; ++q)
+      if (q != W.root || !root_in_place) memcpy((char*)W.recv[q] + coff, v.data(), (size_t)len);
   };
   switch (P.j) {
     case 0:
@@ -189,6 +219,7 @@ bool read_step(World& W, Prog& P) {
     case 2:
       if (P.it < W.iters) {
         if (W.coll == kCollAllGather) push(P.it++);
+        else if (W.coll == kCollBroadcast) relay(P.it++);
         else fold(P.it++);
       }
       if (P.it >= W.iters) P.j = 3;
@@ -272,17 +303,40 @@ void init_world(World& W, int n, int channels, int slots, int op, uint64_t slice
 // 1 one-shot, 2 read (persistent kernel), 4 read's grid form), collective `coll` over `count`
 // elements (the all-reduce's; per rank for a half).  0, -1 on deadlock, -2 on bad arguments.
 int run_call(World& W, int code, int coll, uint64_t count, const float* const* send, float* const* recv,
-             uint64_t slice_bytes, uint64_t min_slice, uint64_t schedule_seed, uint64_t& rng, uint64_t& steps) {
+             uint64_t slice_bytes, uint64_t min_slice, uint64_t schedule_seed, uint64_t& rng, uint64_t& steps,
+             int root = 0) {
   const int n = W.n, channels = W.C;
-  const bool half = coll != kCollAllReduce;
+  const bool rooted = coll == kCollBroadcast || coll == kCollReduce;
+  const bool half = coll != kCollAllReduce;  // (the rooted ones too: ring and persistent read only)
   if (code > 4 || code == 3 || (half && code != 0 && code != 2)) return -2;
+  if (rooted && (root < 0 || root >= n)) return -2;
   const int a = code >= 2 ? 2 : code;  // 0 ring, 1 one-shot, 2 read
-  const uint64_t chunk = half ? count : count / (uint64_t)n;
+  const uint64_t chunk = rooted ? (count + (uint64_t)n - 1) / (uint64_t)n : half ? count : count / (uint64_t)n;
   W.coll = coll;
+  W.root = root;
+  W.total_bytes = rooted ? count * 4 : 0;
   W.chunk_bytes = chunk * 4;
   W.send.assign(send, send + n);
   W.recv.assign(recv, recv + n);
   W.own.assign((size_t)n, 1);
+  if (rooted) {
+    // Comm::collective: the buffer a rank's role does not use (it may be NULL) is stood in for by
+    // its other buffer; one rank: a copy; the ring's broadcast moves the whole buffer as one chunk
+    // and the root's recv, out of place, gets its send by a copy before the launch
+    for (int r = 0; r < n; ++r) {
+      if (r == root) continue;
+      if (coll == kCollBroadcast) W.send[r] = W.recv[r];
+      else W.recv[r] = const_cast<float*>(W.send[r]);
+    }
+    if (n == 1) {
+      if ((const void*)send[0] != (const void*)recv[0]) memcpy(recv[0], send[0], count * 4);
+      return 0;
+    }
+    if (coll == kCollBroadcast && a == 0) {
+      W.chunk_bytes = W.total_bytes;
+      if ((const void*)send[root] != (const void*)recv[root]) memcpy(recv[root], send[root], count * 4);
+    }
+  }
   // as Comm::launch: adaptive payload (min_slice 0 = off; the read schedule's own rule), fixed
   // slot stride, one pipeline per slice up to all of them
   if (a == 1 && W.chunk_bytes) {
@@ -296,7 +350,7 @@ int run_call(World& W, int code, int coll, uint64_t count, const float* const* s
   W.nslices = (W.chunk_bytes + W.slice - 1) / W.slice;
   W.A = call_pipelines(a == 1 ? W.nslices * (uint64_t)n : W.nslices, channels, 1);  // one-shot: per chunk too
   W.iters = (uint32_t)((W.nslices + (uint64_t)W.A - 1) / (uint64_t)W.A);
-  for (int r = 0; r < n; ++r) {
+  for (int r = 0; r < n && !rooted; ++r) {
     if (half) {
       // Comm::collective: one device copy of the chunk with one rank; the ring's all-gather gets
       // the own chunk by a copy before the launch when the call is not in place; then the
@@ -367,9 +421,8 @@ int run_call(World& W, int code, int coll, uint64_t count, const float* const* s
           W.rx_seq[r][(size_t)q * channels + w] += m;
         }
       } else {
-        const uint64_t m = (uint64_t)W.iters * coll_msgs_per_iter(coll, n);
-        W.tx_seq[r][(size_t)mod_n(r + 1, n) * channels + w] += m;
-        W.rx_seq[r][(size_t)mod_n(r - 1, n) * channels + w] += m;
+        W.tx_seq[r][(size_t)mod_n(r + 1, n) * channels + w] += (uint64_t)W.iters * coll_tx_msgs(coll, n, r, root);
+        W.rx_seq[r][(size_t)mod_n(r - 1, n) * channels + w] += (uint64_t)W.iters * coll_rx_msgs(coll, n, r, root);
       }
     }
   return 0;
@@ -391,6 +444,16 @@ int mnccl_oneshot_fits(uint64_t chunk_bytes, int n, int channels, uint64_t slot_
 // for the host-logic tests: out = {kind, chunk, send_msg, recv_msg}
 int mnccl_coll_num_ops(int coll, int n) { return coll_num_ops(coll, n); }
 int mnccl_coll_msgs_per_iter(int coll, int n) { return coll_msgs_per_iter(coll, n); }
+// the same with a root (the rooted collectives' tables) and what each rank's counters advance by
+void mnccl_coll_op_rooted(int coll, int n, int r, int k, int root, int* out) {
+  const RingOp o = coll_op(coll, n, r, k, root);
+  out[0] = o.kind; out[1] = o.chunk; out[2] = o.send_msg; out[3] = o.recv_msg;
+}
+int mnccl_coll_tx_msgs(int coll, int n, int r, int root) { return coll_tx_msgs(coll, n, r, root); }
+int mnccl_coll_rx_msgs(int coll, int n, int r, int root) { return coll_rx_msgs(coll, n, r, root); }
+uint64_t mnccl_rooted_len(uint64_t total_bytes, uint64_t chunk_off, uint64_t chunk_bytes, uint64_t slice_bytes, uint64_t s) {
+  return rooted_len(total_bytes, chunk_off, chunk_bytes, slice_bytes, s);
+}
 void mnccl_coll_op(int coll, int n, int r, int k, int* out) {
   const RingOp o = coll < 0 ? ring_op(n, r, k) : coll_op(coll, n, r, k);  // coll < 0: ring_op itself
   out[0] = o.kind; out[1] = o.chunk; out[2] = o.send_msg; out[3] = o.recv_msg;
@@ -473,6 +536,30 @@ int mnccl_sim_collective(int n, int calls, const int* coll, const int* sched, co
     if (c < kCollAllReduce || c > kCollAllGather || (c != kCollAllReduce && sched[call] != 0 && sched[call] != 2)) return -2;
     const int rc = run_call(W, sched[call], c, counts[call], send + (size_t)call * n, recv + (size_t)call * n, slice_bytes,
                             min_slice, schedule_seed, rng, steps);
+    if (rc != 0) return rc;
+  }
+  if (steps_out) *steps_out = steps;
+  return 0;
+}
+
+// mnccl_sim_collective with the two rooted collectives (schedule.h Coll 3 broadcast / 4 reduce over
+// counts[i] elements) and a root per call, roots[i] (ignored by the other collectives): any of the
+// five may follow any other, on either schedule, on the one communicator state.  A rank's unused
+// buffer (a non-root's send / recv) may be NULL.
+int mnccl_sim_rooted(int n, int calls, const int* coll, const int* sched, const uint64_t* counts, const int* roots,
+                     const float* const* send, float* const* recv, int op, uint64_t slice_bytes, uint64_t min_slice,
+                     int channels, int slots, uint64_t schedule_seed, uint64_t* steps_out) {
+  if (n < 1 || n > 16 || channels < 1 || slots < 1 || slice_bytes < 4 || slice_bytes % 4 || calls < 0) return -2;
+  World W;
+  init_world(W, n, channels, slots, op, slice_bytes);
+  uint64_t steps = 0;
+  uint64_t rng = schedule_seed * 6364136223846793005ull + 1442695040888963407ull;
+  for (int call = 0; call < calls; ++call) {
+    const int c = coll[call];
+    if (c < kCollAllReduce || c > kCollReduce || (c != kCollAllReduce && sched[call] != 0 && sched[call] != 2)) return -2;
+    if (counts[call] == 0) return -2;
+    const int rc = run_call(W, sched[call], c, counts[call], send + (size_t)call * n, recv + (size_t)call * n, slice_bytes,
+                            min_slice, schedule_seed, rng, steps, roots[call]);
     if (rc != 0) return rc;
   }
   if (steps_out) *steps_out = steps;

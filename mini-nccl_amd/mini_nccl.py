@@ -80,6 +80,8 @@ SIGNATURES = {
     "ncclAllReduce": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclReduceScatter": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclAllGather": (_I, [_VP, _VP, _SZ, _I, _VP, _VP]),
+    "ncclBroadcast": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
+    "ncclReduce": (_I, [_VP, _VP, _SZ, _I, _I, _I, _VP, _VP]),
     "mncclLocalReduce": (_I, [_VP, _VP, _VP, _SZ, _I, _I, _VP]),
     "mncclCommGetAsyncError": (_I, [_VP, ctypes.POINTER(_I)]),
     "mncclCommGetInfo": (_I, [_VP, ctypes.POINTER(CommInfo)]),
@@ -148,6 +150,16 @@ class Comm:
         """ncclAllGather: recv holds nranks * sendcount elements, rank q's send at
         [q * sendcount, (q + 1) * sendcount).  Returns the ncclResult_t."""
         return load().ncclAllGather(send_ptr, recv_ptr, sendcount, dtype, self.handle, stream)
+
+    def broadcast(self, send_ptr, recv_ptr, count, dtype=ncclFloat, root=0, stream=0):
+        """ncclBroadcast: every rank's recv gets the root's `count` elements of send (send is read on
+        the root only: elsewhere it may be 0 / None)."""
+        return load().ncclBroadcast(send_ptr, recv_ptr, count, dtype, root, self.handle, stream)
+
+    def reduce(self, send_ptr, recv_ptr, count, dtype=ncclFloat, op=ncclSum, root=0, stream=0):
+        """ncclReduce: the root's recv gets the reduction of every rank's `count` elements of send
+        (recv is written on the root only: elsewhere it may be 0 / None and is never touched)."""
+        return load().ncclReduce(send_ptr, recv_ptr, count, dtype, op, root, self.handle, stream)
 
     def rank(self):
         r = ctypes.c_int()
