@@ -30,6 +30,10 @@
  *   ncclBroadcast        every rank's recv = the root's send.
  *   ncclReduce           the root's recv = the reduction of every rank's send (ncclAllReduce's bits
  *                        when count is a multiple of nranks); nobody else's recv is touched.
+ *
+ * and RCCL's dense exchange:
+ *
+ *   ncclAllToAll         block q of rank r's send becomes block r of rank q's recv, byte for byte.
  */
 #ifndef MINI_NCCL_EXT_H_
 #define MINI_NCCL_EXT_H_
@@ -59,7 +63,7 @@ extern "C" {
    schedule choice in their signature and skip the host rendezvous only when no two ranks share a
    GPU (MINI_NCCL_WINDOW_RENDEZVOUS); still 600: ncclReduceScatter and ncclAllGather were added
    without a change to anything above -- a caller detects them by symbol; still 600: ncclBroadcast
-   and ncclReduce were added the same way */
+   and ncclReduce were added the same way; still 600: ncclAllToAll was added the same way */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -235,6 +239,27 @@ ncclResult_t ncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, n
                            ncclComm_t comm, hipStream_t stream);
 ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclRedOp_t op,
                         int root, ncclComm_t comm, hipStream_t stream);
+
+/* The all-to-all, RCCL's name and signature.  sendbuff and recvbuff each hold nranks * count
+ * elements: block q of rank r's send, elements [q * count, (q + 1) * count), ends up as block r of
+ * rank q's recv, byte for byte (no arithmetic: any datatype ncclAllGather takes; NaN payloads and
+ * every other bit pattern survive); block `rank` of a rank's own send goes to block `rank` of its own
+ * recv.  Checks, in this order: a NULL comm, sendbuff or recvbuff is ncclInvalidArgument; count == 0
+ * is ncclSuccess; an unsupported datatype is ncclInternalError; any overlap of the two byte ranges
+ * [buff, buff + nranks * count * size) -- sendbuff == recvbuff included: there is no in-place form,
+ * as in RCCL, at any rank count -- is ncclInvalidArgument, with nothing launched or negotiated and
+ * the communicator still usable.  Ranks that disagree on the collective, count or datatype get
+ * ncclInvalidUsage wherever the call is negotiated, and the communicator stays usable.  Blocking
+ * mode, stream ordering, graph capture, sticky errors, the watchdog and host buffers as for
+ * ncclAllGather (two pageable buffers are staged side by side); nranks == 1 is one device copy.
+ * Schedules: the read schedule where an all-reduce's larger calls would run it -- every rank pushes
+ * block q of its send straight into rank q's recv, so every off-diagonal block crosses one link once
+ * and all nranks - 1 links of a rank are busy for the whole call -- otherwise the ring, where the
+ * block for the rank d places on travels d hops (nranks * (nranks - 1) / 2 messages per link and
+ * iteration).  mncclCommInfo_t.last_algo reports mncclAlgoRead or mncclAlgoRing.  No one-shot, grid
+ * or registered-window form. */
+ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclComm_t comm,
+                          hipStream_t stream);
 
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream);

@@ -201,6 +201,27 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
   }
 }
 
+// The all-to-all (mini_nccl_ext.h): the halves' checks in their order; the overlap of the two
+// buffers is checked where the communicator's size is known (Comm::collective), after the datatype.
+ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclComm_t comm,
+                          hipStream_t stream) {
+  if (!comm || !sendbuff || !recvbuff) return ncclInvalidArgument;
+  if (count == 0) return ncclSuccess;
+  RoctxRange range("mini_ncclAllToAll");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] AllToAll Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->all_to_all(sendbuff, recvbuff, count, (int)datatype, stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] AllToAll Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream) {
   if (!out || !local || !incoming) return ncclInvalidArgument;

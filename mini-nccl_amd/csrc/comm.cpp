@@ -646,6 +646,7 @@ void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, in
                  : algo == 2 && coll == kCollAllGather     ? launch_gather_push(dtype, vec, wg, nt, p, stream)
                  : algo == 2 && coll == kCollReduce        ? launch_root_fold(dtype, op, vec, wg, nt, p, stream)
                  : algo == 2 && coll == kCollBroadcast     ? launch_root_relay(dtype, vec, wg, nt, p, stream)
+                 : algo == 2 && coll == kCollAllToAll      ? launch_exchange_push(dtype, vec, wg, nt, p, stream)
                  : algo == 2 ? launch_read(dtype, op, vec, wg, nt, p, stream)
                  : algo == 3 ? launch_oneshot(dtype, op, vec, wg, nt, p, stream)
                              : launch_ring(dtype, op, vec, wg, nt, p, stream);
@@ -656,7 +657,8 @@ void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, in
 
 // The call path of ncclAllReduce (coll 0: `count` elements in send and in recv) and of its halves
 // (schedule.h Coll; `count` per rank): ncclReduceScatter's send and ncclAllGather's recv hold
-// n * count elements, the other buffer one chunk of `count`.
+// n * count elements, the other buffer one chunk of `count`.  ncclAllToAll (coll 5): both buffers
+// hold n blocks of `count` elements, and a chunk is one block.
 ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
                               hipStream_t stream, int root) {
   if (sticky_ != ncclSuccess) return sticky_;
@@ -666,14 +668,17 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
   // half: one of the all-reduce's halves.  Neither has a one-shot, grid or registered-window form.
   const bool rooted = coll == kCollBroadcast || coll == kCollReduce;
   const bool half = coll == kCollReduceScatter || coll == kCollAllGather;
+  // a2a: ncclAllToAll (`count` elements per block, n blocks in both buffers); the same schedules
+  const bool a2a = coll == kCollAllToAll;
   const bool is_root = rooted && rank_ == root;
   const char* const coll_name = coll == kCollReduceScatter ? "ncclReduceScatter"
                                 : coll == kCollAllGather   ? "ncclAllGather"
                                 : coll == kCollBroadcast   ? "ncclBroadcast"
                                 : coll == kCollReduce      ? "ncclReduce"
+                                : coll == kCollAllToAll    ? "ncclAllToAll"
                                                            : "ncclAllReduce";
   // bytes: the larger buffer's (the all-reduce's and the rooted collectives': both)
-  const size_t bytes = count * (size_t)esz * (half ? (size_t)nranks_ : 1);
+  const size_t bytes = count * (size_t)esz * (half || a2a ? (size_t)nranks_ : 1);
   if (rooted) {
     // the caller's errors, in this order: nothing launched, nothing negotiated
     if (root < 0 || root >= nranks_) {
@@ -714,6 +719,15 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       return ncclInvalidArgument;
     }
   }
+  if (a2a) {
+    // no in-place form (as in RCCL): any overlap of the two byte ranges, send == recv included and
+    // at every rank count, is the caller's error -- nothing launched, nothing negotiated
+    const uintptr_t s0 = (uintptr_t)send, r0 = (uintptr_t)recv;
+    if (s0 < r0 + bytes && r0 < s0 + bytes) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: send and recv overlap (there is no in-place form)\n", rank_, coll_name);
+      return ncclInvalidArgument;
+    }
+  }
   int cur_dev = -1;
   hip_check(hipGetDevice(&cur_dev), "hipGetDevice");
   if (cur_dev != device_) hip_check(hipSetDevice(device_), "hipSetDevice");
@@ -741,7 +755,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
   const int n = nranks_;
   uint32_t seq = 0;  // this call's kernel (0: the call launches none)
   // (rooted: ceil -- the trailing chunks are short or empty and there is no unreduced tail)
-  const size_t chunk = half ? count : rooted ? (count + (size_t)n - 1) / (size_t)n
+  const size_t chunk = half || a2a ? count : rooted ? (count + (size_t)n - 1) / (size_t)n
                        : n > 0 ? count / (size_t)n : 0;  // mini_nccl.cu:69
   const size_t chunk_bytes = chunk * (size_t)esz;
   if (n == 1 || chunk == 0) {
@@ -766,8 +780,8 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // function of the call's size and the rank-uniform config up to the read rendezvous, which
     // all ranks decide alike.
     // (the halves have no one-shot form: read where an all-reduce's larger calls would, else the ring)
-    const bool oneshot = !half && !rooted && algo_ == 3 && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), true);
-    const bool small = !half && !rooted && auto_ && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), false);
+    const bool oneshot = !half && !rooted && !a2a && algo_ == 3 && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), true);
+    const bool small = !half && !rooted && !a2a && auto_ && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), false);
     // (auto, and a forced one-shot's larger calls, only where the topology allows the read
     // schedule: classify_topology; MINI_NCCL_ALGO=read forces it anywhere)
     const bool read_sched = !oneshot &&
@@ -776,7 +790,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // registered windows: the read schedule with no host rendezvous (no record to wait for, no
     // pointer query) -- every rank promised the same windows and offsets, the kernel checks it
     // (all-reduce only: a half whose buffers lie in windows is negotiated like any other call)
-    const Window* win_s = !half && !rooted && read_sched && window_fast_ && !windows_.empty() ? find_window(send, bytes) : nullptr;
+    const Window* win_s = !half && !rooted && !a2a && read_sched && window_fast_ && !windows_.empty() ? find_window(send, bytes) : nullptr;
     const Window* win_r = win_s ? find_window(recv, bytes) : nullptr;
     if (win_s && win_r) {
       const uint64_t os = (uint64_t)((const char*)send - win_s->base), orv = (uint64_t)((char*)recv - win_r->base);
@@ -828,9 +842,12 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
         if (cur_dev != device_) hipSetDevice(cur_dev);
         return ncclInvalidUsage;
       }
-      ensure_stage(bytes, stream);
+      // (the all-to-all has no in-place form: with both buffers pageable the stage holds both, send
+      // staged in whole, recv staged out whole, in regions that do not overlap)
+      const size_t a2a_recv = a2a && rs == Reach::kStaged && rr == Reach::kStaged ? (bytes + 255) & ~(size_t)255 : 0;
+      ensure_stage(a2a_recv + bytes, stream);
       // a half is staged in its in-place layout: the one-chunk buffer is chunk `rank` of the stage
-      const size_t s_off = coll == kCollAllGather ? mine : 0, r_off = coll == kCollReduceScatter ? mine : 0;
+      const size_t s_off = coll == kCollAllGather ? mine : 0, r_off = coll == kCollReduceScatter ? mine : a2a_recv;
       if (rs == Reach::kStaged) {
         // (Broadcast: only the root's send holds anything -- the others' stands for their recv)
         if (coll != kCollBroadcast || is_root)
@@ -848,7 +865,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // buffer and never touches the tail, api.cpp:173-175 + mini_nccl.cu:69); the kernels
     // write every other element of recv and copy the tail themselves (kernels.hip copy_tail)
     const size_t body = chunk_bytes * (size_t)n;
-    const size_t tail = !half && !rooted && ksend != krecv && bytes > body ? bytes - body : 0;
+    const size_t tail = !half && !rooted && !a2a && ksend != krecv && bytes > body ? bytes - body : 0;
     // 16-byte vector path whenever every message's local base is dword-aligned (vectors may
     // straddle 16-byte boundaries on the local side; each message's last len % 16 bytes go
     // element by element); element-wise path otherwise (2-byte types with odd chunks)
@@ -872,7 +889,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
                             [this] { wait_previous_call(); }, psend, precv, &vec_all,
                             // (with the collective: ranks that call different ones get kMismatch)
                             // (and a rooted one's root: ranks that differ in it get kMismatch too)
-                            half || rooted ? ((auto_ ? 0xff : algo_) | coll << 8 | (rooted ? root << 16 : 0))
+                            half || rooted || a2a ? ((auto_ ? 0xff : algo_) | coll << 8 | (rooted ? root << 16 : 0))
                             : auto_        ? -1
                                            : algo_);
       } catch (const PeerGaveUp& e) {
@@ -910,6 +927,11 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // own chunk (root_relay stores it itself)
     if (coll == kCollBroadcast && is_root && algo == 0 && ksend != krecv)
       hip_check(hipMemcpyAsync(krecv, ksend, bytes, hipMemcpyDefault, stream), "root's own copy");
+    // the ring's all-to-all moves the blocks between ranks only: the own block reaches the own recv
+    // the same way (exchange_push stores it itself)
+    if (a2a && algo == 0)
+      hip_check(hipMemcpyAsync((char*)krecv + mine, (const char*)ksend + mine, chunk_bytes, hipMemcpyDefault, stream),
+                "own block");
     launch(algo, ksend, krecv, chunk_bytes, dtype, op, stream, seq, vec, psend, precv, tail, 0, coll, root,
            rooted ? bytes : 0);
     // (Reduce: only the root's recv is written -- the others' stands for their send)

@@ -57,6 +57,15 @@ class Comm {
     return collective(kCollReduce, send, recv, count, dtype, op, stream, root);
   }
 
+  // The all-to-all (RCCL's ncclAllToAll; `count` elements per block, n blocks in both buffers):
+  // block q of this rank's send becomes block `rank` of rank q's recv, byte for byte.  The schedule
+  // choice is the halves': the read schedule (kernels.hip exchange_push), else the ring (schedule.h
+  // coll_op).  No in-place form: any overlap of the two buffers is ncclInvalidArgument, nothing
+  // launched or negotiated.
+  ncclResult_t all_to_all(const void* send, void* recv, size_t count, int dtype, hipStream_t stream) {
+    return collective(kCollAllToAll, send, recv, count, dtype, kSum, stream);
+  }
+
   int rank() const { return rank_; }
   int nranks() const { return nranks_; }
   int device() const { return device_; }
@@ -121,8 +130,8 @@ class Comm {
               uint32_t seq, bool vec, const char* const* psend = nullptr, const char* const* precv = nullptr,
               size_t tail_bytes = 0, uint64_t sig = 0, int coll = kCollAllReduce, int root = 0,
               size_t total_bytes = 0);
-  // the one call path of the five collectives; count: the all-reduce's and the rooted ones', per
-  // rank for the halves
+  // the one call path of the six collectives; count: the all-reduce's and the rooted ones', per
+  // rank for the halves, per block for the all-to-all
   ncclResult_t collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
                           hipStream_t stream, int root = 0);
   // one rendezvous failure of the read schedule, reported like the kernel's (sticky, peers aborted)

@@ -31,7 +31,8 @@ struct CollParams {
   uint32_t call_seq;       // this launch's sequence number (Comm::wait_for's deadline starts here)
   int32_t coll;            // schedule.h Coll (3 / 4: below): 0 all-reduce, 1 reduce-scatter (recv holds one chunk: the
                            // host passes recv - rank * chunk_bytes), 2 all-gather (send holds one
-                           // chunk: the host passes send - rank * chunk_bytes).  In what was padding:
+                           // chunk: the host passes send - rank * chunk_bytes), 5 all-to-all (a chunk is
+                           // one block of the n in send and in recv).  In what was padding:
                            // the struct's size and every other offset are the all-reduce's
   uint64_t timeout_ticks;  // s_memrealtime ticks (100 MHz)
   int32_t sys_fence;       // system-scope release fence before each ready flag
@@ -84,6 +85,11 @@ hipError_t launch_root_fold(int dtype, int op, bool vec, int channels, int threa
                             const CollParams& p, hipStream_t stream);
 hipError_t launch_root_relay(int dtype, bool vec, int channels, int threads,
                              const CollParams& p, hipStream_t stream);
+// the read schedule's all-to-all (p.coll 5; the same persistent form and protocol; a chunk is one
+// block of the n in send and in recv): exchange_push stores block q of send into block `rank` of
+// rank q's recv, for every q (by element size: no arithmetic)
+hipError_t launch_exchange_push(int dtype, bool vec, int channels, int threads,
+                                const CollParams& p, hipStream_t stream);
 // the read schedule's push form for large calls as three launches (start, grid fold, done):
 // schedule.h read_grid_fits(p.chunk_bytes, p.n, kReadGridFloor) (2 <= n <= 8, whole 16-byte vectors), p.go set
 // vectors: 0 = schedule.h read_grid_vectors; 1 / 2 / 4 (MINI_NCCL_GRID_VECTORS) for fp32 Sum only

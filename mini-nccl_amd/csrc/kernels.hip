@@ -19,6 +19,9 @@
 //  root_fold / root_relay   the rooted collectives (ncclReduce / ncclBroadcast) on the same
 //                 protocol: every rank folds, or copies out of the root's send, chunk `rank` only,
 //                 so no link carries the whole buffer.  Their fallback is ring_kernel too.
+//  exchange_push  the all-to-all (ncclAllToAll) on the same protocol: every rank pushes block q of
+//                 its own send into rank q's recv, so every block crosses one link once.  Its
+//                 fallback is ring_kernel with a table of hops (schedule.h coll_op).
 //  read_start / read_grid / read_done   the read schedule's push form as three launches (the
 //                 runtime form mncclAlgoReadGrid, for large calls): a grid of one-batch workgroups
 //                 between a one-wave START and a one-wave DONE.
@@ -1201,6 +1204,112 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) root_relay(Coll
     read_half<true>(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { relay_slice<ESZ, VEC, false>(p, coff, len, lane); });
 }
 
+// ---------------------------------------------------------------- the all-to-all
+// ncclAllToAll (exchange_push) on device buffers every rank can share, in read_half's protocol
+// message for message: block q of rank r's send becomes block r of rank q's recv; a chunk is one
+// block, and both buffers hold n of them.  For slice s of the call, pipeline w of rank r loads the
+// slice of EVERY block q from its own send, non-temporal as gather_push reads its send, and pushes
+// it into rank q's recv at block r -- its own block into its own recv.  Every off-diagonal block
+// crosses exactly one link exactly once, and all n - 1 links of a rank are busy for the whole call.
+//
+// It pushes rather than pulls: the all-gather and the all-reduce already rest on pushed sc0 sc1
+// stores being visible to the owner's later kernels (file header).  A pull form -- rank q loading
+// block q of every peer's send -- would rest on a second cross-device property, a peer's earlier
+// plain stores into its send being visible to loads over the link, that nobody has observed for
+// this pattern.  Only rank r ever writes block r of any recv, nobody reads a recv inside the call,
+// and the buffers of a call never overlap (Comm::collective refuses it): there is no in-place form.
+// Each GPU's HBM moves 2n blocks per call (n read, n landing); each link carries one block each way.
+//
+// 16-byte vectors of one slice, V per lane per batch.  The (destination, batch) pairs of the slice
+// form one sequence -- destination by destination, the peers in direct_peer order starting at peer
+// w mod n-1 so a rank's pipelines spread over all links, this rank itself last -- and two of its
+// batches are in flight per wave: the next batch's loads leave before this one is stored, across
+// destinations too, unconditionally (the vmcnt reason read_fold_all explains).  Past the slice the
+// loads fall outside the buffer resource, return 0 and touch nothing; past the last destination the
+// resource is empty.  The descriptors are rebuilt from the kernel's arguments when the destination
+// changes (wave-uniform: they stay in SGPRs), so one form serves every rank count.
+constexpr int kExchangeV = 8;
+
+template <int V>
+__device__ __forceinline__ void exchange_push_vec(const CollParams& p, uint64_t soff, uint32_t nvec, int lane) {
+  constexpr uint32_t step = 64 * V;
+  const int n = p.n, r = p.rank, first = wave_id().w % (n - 1);
+  const uint32_t vb = nvec * 16;
+  const u64 cb = p.chunk_bytes, mine = (u64)r * cb + soff;
+  // destination k of n (k == n: past the end, nothing is loaded)
+  auto dest = [&](int k) { return k < n - 1 ? direct_peer(n, r, 1 + (first + k) % (n - 1)) : r; };
+  auto src_of = [&](int k) { return make_rsrc(p.send + (u64)dest(k) * cb + soff, k < n ? vb : 0u); };
+  auto dst_of = [&](int k) { return make_rsrc((k < n - 1 ? const_cast<char*>(p.peer_recv[dest(k)]) : p.recv) + mine, vb); };
+  auto load = [&](v4u(&x)[V], rsrc_t s, uint32_t b) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) x[u] = ld_nt16(s, (b + (uint32_t)(u * 64 + lane)) * 16);
+  };
+  auto store = [&](v4u(&x)[V], rsrc_t d, bool own, uint32_t b) {
+    if (own) {
+#pragma unroll
+      for (int u = 0; u < V; ++u) st_own16(d, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+    } else {
+#pragma unroll
+      for (int u = 0; u < V; ++u) st_slot16(d, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+    }
+  };
+  int k = 0;       // the batch about to be stored: destination k, vectors from b
+  uint32_t b = 0;
+  rsrc_t src = src_of(0), dst = dst_of(0);
+  v4u xa[V], xb[V];
+  // loads the batch after (k, b) into nxt, stores cur, moves on; false after the last batch
+  auto turn = [&](v4u(&cur)[V], v4u(&nxt)[V]) {
+    int k2 = k;
+    uint32_t b2 = b + step;
+    if (b2 >= nvec) {
+      b2 = 0;
+      src = src_of(++k2);
+    }
+    load(nxt, src, b2);
+    store(cur, dst, k == n - 1, b);
+    if (k2 != k) dst = dst_of(k2);
+    k = k2;
+    b = b2;
+    return k < n;
+  };
+  load(xa, src, 0);
+  while (turn(xa, xb) && turn(xb, xa)) {
+  }
+}
+
+// slice `nbytes` at byte `soff` of every block; the last nbytes % 16 bytes, and everything without
+// VEC, element by element
+template <int ESZ, bool VEC>
+__device__ __forceinline__ void exchange_slice(const CollParams& p, uint64_t soff, uint32_t nbytes, int lane) {
+  const int n = p.n, r = p.rank;
+  uint32_t done = 0;
+  if (VEC) {
+    const uint32_t nvec = nbytes >> 4;
+    if (nvec) exchange_push_vec<kExchangeV>(p, soff, nvec, lane);
+    done = nvec * 16;
+  }
+  if (done == nbytes) return;
+  typedef Scal<ESZ> S;
+  const uint32_t ne = nbytes / ESZ;
+  const u64 cb = p.chunk_bytes, mine = (u64)r * cb + soff;
+  for (int k = 1; k <= n; ++k) {
+    const int q = direct_peer(n, r, k);  // k == n: this rank itself
+    const rsrc_t src = make_rsrc(p.send + (u64)q * cb + soff, nbytes);
+    const rsrc_t dst = make_rsrc((q == r ? p.recv : const_cast<char*>(p.peer_recv[q])) + mine, nbytes);
+    for (uint32_t i = done / ESZ + (uint32_t)lane; i < ne; i += 64) S::st(dst, i * (uint32_t)ESZ, S::ld(src, i * (uint32_t)ESZ));
+  }
+}
+
+// No arithmetic, so by element size only.  read_half hands the slice's offset in chunk `rank`; the
+// slice's offset within a block is what every block shares.
+template <int ESZ, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) exchange_push(CollParams p) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) {
+    exchange_slice<ESZ, VEC>(p, coff - (u64)p.rank * p.chunk_bytes, len, lane);
+  });
+}
+
 // ---------------------------------------------------------------- read schedule, grid form
 // mncclAlgoReadGrid / MINI_NCCL_ALGO=read_grid, and auto's large read calls since 5.1
 // (schedule.h read_grid_form): the push form of a large call (read_grid_fits) as three launches on
@@ -1690,6 +1799,21 @@ hipError_t launch_root_relay(int dtype, bool vec, int C, int nt, const CollParam
     default: return hipErrorInvalidValue;
   }
 #undef RELAY_CASE
+  return hipGetLastError();
+}
+
+hipError_t launch_exchange_push(int dtype, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
+  if (p.coll != kCollAllToAll || p.n < 2) return hipErrorInvalidValue;
+#define EXCHANGE_CASE(ESZ)                                                                       \
+  case ESZ:                                                                                      \
+    if (vec) hipLaunchKernelGGL((exchange_push<ESZ, true>), dim3(C), dim3(nt), 0, st, p);       \
+    else hipLaunchKernelGGL((exchange_push<ESZ, false>), dim3(C), dim3(nt), 0, st, p);          \
+    break;
+  switch (dtype_size(dtype)) {
+    EXCHANGE_CASE(2) EXCHANGE_CASE(4) EXCHANGE_CASE(8)
+    default: return hipErrorInvalidValue;
+  }
+#undef EXCHANGE_CASE
   return hipGetLastError();
 }
 

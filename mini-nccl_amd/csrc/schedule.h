@@ -122,16 +122,35 @@ MNCCL_HD RingOp ring_op(int n, int r, int k) {
 //   but the root with the stores into recv masked off -- kReduceCopySend becomes kReduceSend,
 //   kCopySend kForward, kCopy kDrop -- so the root's recv has the all-reduce's association by
 //   construction and nobody else's recv is touched.
-enum Coll : int { kCollAllReduce = 0, kCollReduceScatter = 1, kCollAllGather = 2, kCollBroadcast = 3, kCollReduce = 4 };
+//
+// The all-to-all (ncclAllToAll: block q of rank r's send becomes block r of rank q's recv; a chunk
+// is one block of `count` elements and both buffers hold n of them).  On the ring the block from
+// rank s to rank s + d travels d hops, so per iteration, for d = 1 .. n-1 in this order, with
+// m_d = d(d-1)/2 the group's first message:
+//     kSend     of send block (r+d) mod n, send_msg m_d
+//     kForward  j = 1 .. d-1: recv_msg m_d + j - 1, send_msg m_d + j
+//     kCopy     into recv block (r-d) mod n, recv_msg m_d + d - 1
+// (n-1)(n+2)/2 ops and n(n-1)/2 messages per iteration on every link; every message is received by
+// the op right after the one that sent it on the rank before, as in the tables above.  Each op
+// touches only one of send and recv, so one `chunk` per op is enough.  The own block reaches the
+// own recv by a device copy before the launch, as the ring's all-gather gets its own chunk.
+enum Coll : int {
+  kCollAllReduce = 0, kCollReduceScatter = 1, kCollAllGather = 2, kCollBroadcast = 3, kCollReduce = 4, kCollAllToAll = 5
+};
 
 MNCCL_HD int coll_num_ops(int coll, int n) {
-  return coll == kCollReduceScatter ? n + 1 : coll == kCollAllGather ? n : coll == kCollBroadcast ? 1 : ring_num_ops(n);
+  return coll == kCollReduceScatter ? n + 1
+         : coll == kCollAllGather   ? n
+         : coll == kCollBroadcast   ? 1
+         : coll == kCollAllToAll    ? (n - 1) * (n + 2) / 2
+                                    : ring_num_ops(n);
 }
 // messages per iteration on a link that carries the collective (Broadcast: all but root-1 -> root)
 MNCCL_HD int coll_msgs_per_iter(int coll, int n) {
   return coll == kCollReduceScatter ? n
          : coll == kCollAllGather   ? n - 1
          : coll == kCollBroadcast   ? 1
+         : coll == kCollAllToAll    ? n * (n - 1) / 2
                                     : ring_msgs_per_iter(n);
 }
 // messages per iteration rank r sends to r+1 / receives from r-1: what its counters advance by
@@ -155,6 +174,17 @@ MNCCL_HD RingOp coll_op(int coll, int n, int r, int k, int root = 0) {
     o = ring_op(n, r, k);
     if (r != root)
       o.kind = o.kind == kReduceCopySend ? kReduceSend : o.kind == kCopySend ? kForward : o.kind == kCopy ? kDrop : o.kind;
+    return o;
+  }
+  if (coll == kCollAllToAll) {
+    // group d holds d + 1 ops and starts at op (d-1)(d+2)/2; j: the op's place in its group
+    int d = 1, j = k;
+    while (j > d) j -= d + 1, ++d;
+    const int m = d * (d - 1) / 2;
+    o.kind = j == 0 ? kSend : j < d ? kForward : kCopy;
+    o.chunk = j == 0 ? mod_n(r + d, n) : j < d ? 0 : mod_n(r - d, n);
+    o.send_msg = j < d ? m + j : -1;
+    o.recv_msg = j > 0 ? m + j - 1 : -1;
     return o;
   }
   if (coll != kCollReduceScatter && coll != kCollAllGather) return ring_op(n, r, k);

@@ -9,6 +9,7 @@
 // such state (the halves: schedule.h coll_op on the ring, kernels.hip scatter_fold / gather_push on
 // the read schedule).  mnccl_sim_rooted adds ncclBroadcast / ncclReduce with a root per call (the
 // ring's chain and masked ring, kernels.hip root_relay / root_fold), interleaved with the others.
+// mnccl_sim_mixed adds ncclAllToAll (the ring's hop table, kernels.hip exchange_push) to those five.
 // fp32 only (the schedule does not depend on the element type); ops as reference
 // mini_nccl.cu:38-41 with a = local, b = incoming.
 #include <stdint.h>
@@ -183,6 +184,18 @@ bool read_step(World& W, Prog& P) {
     for (int q = 0; q < n; ++q)
       if (q != W.root || !root_in_place) memcpy((char*)W.recv[q] + coff, v.data(), (size_t)len);
   };
+  // kernels.hip exchange_push: slice `it` of EVERY block q of this rank's send into block r of rank
+  // q's recv, the peers in direct_peer order from peer w mod n-1, this rank's own block last
+  auto exchange = [&](uint32_t it) {
+    const uint64_t s = (uint64_t)it * W.A + w;
+    const uint64_t len = slice_len(W.chunk_bytes, W.slice, s);
+    const uint64_t soff = s * W.slice, mine = (uint64_t)r * W.chunk_bytes + soff;
+    if (!len) return;
+    for (int k = 0; k < n; ++k) {
+      const int q = k < n - 1 ? direct_peer(n, r, 1 + (w % (n - 1) + k) % (n - 1)) : r;
+      memcpy((char*)W.recv[q] + mine, (const char*)W.send[r] + (uint64_t)q * W.chunk_bytes + soff, (size_t)len);
+    }
+  };
   switch (P.j) {
     case 0:
       // START (kernels.hip read_kernel).  A registered-window call's signature is stored with it but
@@ -220,6 +233,7 @@ bool read_step(World& W, Prog& P) {
       if (P.it < W.iters) {
         if (W.coll == kCollAllGather) push(P.it++);
         else if (W.coll == kCollBroadcast) relay(P.it++);
+        else if (W.coll == kCollAllToAll) exchange(P.it++);
         else fold(P.it++);
       }
       if (P.it >= W.iters) P.j = 3;
@@ -361,7 +375,11 @@ int run_call(World& W, int code, int coll, uint64_t count, const float* const* s
         if (s != d) memcpy(d, s, (size_t)W.chunk_bytes);
         continue;
       }
-      if (coll == kCollAllGather) {
+      if (coll == kCollAllToAll) {
+        // no pointer shift and no in-place form; the ring moves the blocks between ranks only, the
+        // own block reaches the own recv by a copy before the launch (Comm::collective)
+        if (a == 0) memcpy(d + (uint64_t)r * W.chunk_bytes, s + (uint64_t)r * W.chunk_bytes, (size_t)W.chunk_bytes);
+      } else if (coll == kCollAllGather) {
         W.own[(size_t)r] = s != d + (uint64_t)r * W.chunk_bytes;
         if (a == 0 && W.own[(size_t)r]) memcpy(d + (uint64_t)r * W.chunk_bytes, s, (size_t)W.chunk_bytes);
         W.send[r] = (const float*)(s - (uint64_t)r * W.chunk_bytes);
@@ -557,6 +575,29 @@ int mnccl_sim_rooted(int n, int calls, const int* coll, const int* sched, const 
   for (int call = 0; call < calls; ++call) {
     const int c = coll[call];
     if (c < kCollAllReduce || c > kCollReduce || (c != kCollAllReduce && sched[call] != 0 && sched[call] != 2)) return -2;
+    if (counts[call] == 0) return -2;
+    const int rc = run_call(W, sched[call], c, counts[call], send + (size_t)call * n, recv + (size_t)call * n, slice_bytes,
+                            min_slice, schedule_seed, rng, steps, roots[call]);
+    if (rc != 0) return rc;
+  }
+  if (steps_out) *steps_out = steps;
+  return 0;
+}
+
+// mnccl_sim_rooted with the all-to-all (schedule.h Coll 5: counts[i] elements per block, n blocks in
+// both of a rank's buffers, which must not overlap): any of the six collectives may follow any
+// other, on either schedule, on the one communicator state.
+int mnccl_sim_mixed(int n, int calls, const int* coll, const int* sched, const uint64_t* counts, const int* roots,
+                    const float* const* send, float* const* recv, int op, uint64_t slice_bytes, uint64_t min_slice,
+                    int channels, int slots, uint64_t schedule_seed, uint64_t* steps_out) {
+  if (n < 1 || n > 16 || channels < 1 || slots < 1 || slice_bytes < 4 || slice_bytes % 4 || calls < 0) return -2;
+  World W;
+  init_world(W, n, channels, slots, op, slice_bytes);
+  uint64_t steps = 0;
+  uint64_t rng = schedule_seed * 6364136223846793005ull + 1442695040888963407ull;
+  for (int call = 0; call < calls; ++call) {
+    const int c = coll[call];
+    if (c < kCollAllReduce || c > kCollAllToAll || (c != kCollAllReduce && sched[call] != 0 && sched[call] != 2)) return -2;
     if (counts[call] == 0) return -2;
     const int rc = run_call(W, sched[call], c, counts[call], send + (size_t)call * n, recv + (size_t)call * n, slice_bytes,
                             min_slice, schedule_seed, rng, steps, roots[call]);

@@ -82,6 +82,7 @@ SIGNATURES = {
     "ncclAllGather": (_I, [_VP, _VP, _SZ, _I, _VP, _VP]),
     "ncclBroadcast": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclReduce": (_I, [_VP, _VP, _SZ, _I, _I, _I, _VP, _VP]),
+    "ncclAllToAll": (_I, [_VP, _VP, _SZ, _I, _VP, _VP]),
     "mncclLocalReduce": (_I, [_VP, _VP, _VP, _SZ, _I, _I, _VP]),
     "mncclCommGetAsyncError": (_I, [_VP, ctypes.POINTER(_I)]),
     "mncclCommGetInfo": (_I, [_VP, ctypes.POINTER(CommInfo)]),
@@ -160,6 +161,11 @@ class Comm:
         """ncclReduce: the root's recv gets the reduction of every rank's `count` elements of send
         (recv is written on the root only: elsewhere it may be 0 / None and is never touched)."""
         return load().ncclReduce(send_ptr, recv_ptr, count, dtype, op, root, self.handle, stream)
+
+    def all_to_all(self, send_ptr, recv_ptr, count, dtype=ncclFloat, stream=0):
+        """ncclAllToAll: send and recv each hold nranks * count elements; block q of this rank's send
+        becomes block `rank` of rank q's recv (no in-place form).  Returns the ncclResult_t."""
+        return load().ncclAllToAll(send_ptr, recv_ptr, count, dtype, self.handle, stream)
 
     def rank(self):
         r = ctypes.c_int()

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""Times ncclReduceScatter, ncclAllGather, ncclBroadcast and ncclReduce beside ncclAllReduce on one
-communicator.
+"""Times ncclReduceScatter, ncclAllGather, ncclBroadcast, ncclReduce and ncclAllToAll beside
+ncclAllReduce on one communicator.
 
     python tools/coll_bench.py --gpus 4 [--same-device] [--bytes N] [--rounds R] [--calls K] [--warmup W]
                                [--kinds all_reduce,reduce_scatter,...]
 
 Starts one process per rank (rank r on GPU r % visible GPUs; every rank on GPU 0 with --same-device
 or when only one GPU is visible -- the tests' placement rule, tests/gpu_workers.rank_device) and times
-five calls over the same `bytes` per rank (n chunks of bytes / n), all on the read schedule's
+six calls over the same `bytes` per rank (n chunks of bytes / n), all on the read schedule's
 persistent form (mncclAlgoRead), fp32 Sum, stream-ordered (MINI_NCCL_BLOCKING=0):
 
     all_reduce      n chunks -> n chunks     2n chunks through each GPU's HBM
@@ -15,11 +15,15 @@ persistent form (mncclAlgoRead), fp32 Sum, stream-ordered (MINI_NCCL_BLOCKING=0)
     all_gather      1 chunk  -> n chunks     n + 1
     broadcast       root 0's n chunks -> n chunks on every rank (out of place)    n + 1
     reduce          n chunks -> root 0's n chunks                                 n + 1 on average
+    all_to_all      n chunks -> n chunks (chunk q to rank q)                      2n
 
 (broadcast: every rank loads one chunk of the root's send and stores it into all n recvs; reduce:
 every rank loads its chunk from all n sends and stores it into the root's recv -- on the one-GPU
 proxy the all-gather's and the reduce-scatter's bytes, the yardsticks of the two ratios
-broadcast_over_all_gather and reduce_over_reduce_scatter.)
+broadcast_over_all_gather and reduce_over_reduce_scatter.  all_to_all: every rank loads its n chunks
+and stores one into each recv -- no arithmetic, like the all-gather, but 2n chunks through each
+GPU's HBM against n + 1: all_to_all_over_all_gather beside the byte ratio 2n / (n + 1), with the
+spread of the all-gather's own rounds as the yardstick.)
 
 Each round times K calls of one kind between two device events, after W warm-up calls of each kind
 once at the start; the kinds alternate round by round in one process run, so drift hits all
@@ -42,7 +46,7 @@ for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "mini-nccl_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-KINDS = ("all_reduce", "reduce_scatter", "all_gather", "broadcast", "reduce")
+KINDS = ("all_reduce", "reduce_scatter", "all_gather", "broadcast", "reduce", "all_to_all")
 
 
 def rank_main(a):
@@ -68,6 +72,7 @@ def rank_main(a):
         "all_gather": lambda: comm.all_gather(small.ptr, big_b.ptr, chunk, M.ncclFloat, st.handle),
         "broadcast": lambda: comm.broadcast(big_a.ptr, big_b.ptr, n * chunk, M.ncclFloat, 0, st.handle),
         "reduce": lambda: comm.reduce(big_a.ptr, big_b.ptr, n * chunk, M.ncclFloat, M.ncclSum, 0, st.handle),
+        "all_to_all": lambda: comm.all_to_all(big_a.ptr, big_b.ptr, chunk, M.ncclFloat, st.handle),
     }
     kinds = tuple(a.kinds.split(","))
     e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
@@ -162,13 +167,17 @@ def main():
         "calls_per_round": a.calls, "warmup": a.warmup, "rounds": a.rounds,
         "ms": {k: round(v, 4) for k, v in med.items()},
         "rounds_ms": {k: [round(x, 4) for x in v] for k, v in rounds.items()},
-        "hbm_bytes": {k: (2 * n if k == "all_reduce" else n + 1) * chunk_bytes for k in kinds},
+        "hbm_bytes": {k: (2 * n if k in ("all_reduce", "all_to_all") else n + 1) * chunk_bytes for k in kinds},
         "ratio": dict([(f"{k}_over_all_reduce", round(med[k] / med["all_reduce"], 4)) for k in kinds if k != "all_reduce"] +
                       [(f"{k}_over_{y}", round(med[k] / med[y], 4))
-                       for k, y in (("reduce", "reduce_scatter"), ("broadcast", "all_gather")) if k in med and y in med] +
-                      [("hbm_bytes", round((n + 1) / (2 * n), 4))]),
+                       for k, y in (("reduce", "reduce_scatter"), ("broadcast", "all_gather"), ("all_to_all", "all_gather"))
+                       if k in med and y in med] +
+                      [("hbm_bytes", round((n + 1) / (2 * n), 4))] +
+                      ([("all_to_all_hbm_bytes_over_all_gather", round(2 * n / (n + 1), 4))] if "all_to_all" in med else [])),
         "all_reduce_spread": round((max(rounds["all_reduce"]) - min(rounds["all_reduce"])) / med["all_reduce"], 4),
     }
+    if "all_gather" in rounds:
+        res["all_gather_spread"] = round((max(rounds["all_gather"]) - min(rounds["all_gather"])) / med["all_gather"], 4)
     print(json.dumps(res))
     return 0 if res["ok"] else 1
 
