@@ -15,7 +15,7 @@ import traceback
 import numpy as np
 
 import rooted_workers as RW
-from coll_workers import GUARD, _info_fields
+from coll_workers import GUARD, _info_fields, offsets
 from gpu_workers import testkern, use_rank_device
 
 FILL = 0xAB
@@ -41,18 +41,18 @@ def _differ(got, exp):
 
 def _a2a_case(comm, case, rank, n, stream, barrier, rng):
     """One all-to-all case: dtype, count (elements per block), algo, seed, calls (new bytes every
-    call), offset (bytes: a misaligned base), mem / recv_mem (device / pinned / pageable, or a
-    per-rank list), skew_ms."""
+    call), offset / recv_offset (bytes: a misaligned base, or a per-rank list of them; recv_offset
+    defaults to offset), mem / recv_mem (device / pinned / pageable, or a per-rank list), skew_ms."""
     import hip_rt
     import oracle_api as O
-    dtype, c, seed, off = case["dtype"], case["count"], case.get("seed", 1), case.get("offset", 0)
+    dtype, c, seed, (off, roff) = case["dtype"], case["count"], case.get("seed", 1), offsets(case, rank)
     code, npd = O.DTYPES[dtype]
     bb = c * np.dtype(npd).itemsize
     nb = n * bb
     mem_s = RW._placement(case, "mem", "device", rank)
     mem_r = RW._placement(case, "recv_mem", mem_s, rank)
-    sbuf, rbuf = hip_rt.buffer(mem_s, nb + off), hip_rt.buffer(mem_r, nb + off + GUARD)
-    send, recv, guard = hip_rt.View(sbuf, off, nb), hip_rt.View(rbuf, off, nb), hip_rt.View(rbuf, off + nb, GUARD)
+    sbuf, rbuf = hip_rt.buffer(mem_s, nb + off), hip_rt.buffer(mem_r, nb + roff + GUARD)
+    send, recv, guard = hip_rt.View(sbuf, off, nb), hip_rt.View(rbuf, roff, nb), hip_rt.View(rbuf, roff + nb, GUARD)
     bad, first, detail, rc, algos = 0, -1, "", 0, []
     t0 = time.time()
     for k in range(case.get("calls", 1)):

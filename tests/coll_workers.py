@@ -35,6 +35,18 @@ def _info_fields(comm):
             "read_map_failures": ci["read_map_failures"], "async": comm.async_error()}
 
 
+def per_rank(v, rank):
+    """A case's value for this rank: the value itself, or entry rank of a per-rank list."""
+    return v[rank % len(v)] if isinstance(v, (list, tuple)) else v
+
+
+def offsets(case, rank):
+    """(offset, recv_offset) of this rank in bytes: each a value or a per-rank list; recv_offset
+    defaults to offset (in place the one offset serves both buffers)."""
+    off = case.get("offset", 0)
+    return per_rank(off, rank), per_rank(case.get("recv_offset", off), rank)
+
+
 def call(comm, coll, send_ptr, recv_ptr, count, code, opc, stream):
     if coll == "rs":
         return comm.reduce_scatter(send_ptr, recv_ptr, count, code, opc, stream)
@@ -46,8 +58,9 @@ def call(comm, coll, send_ptr, recv_ptr, count, code, opc, stream):
 def coll_rank(rank, n, port, cases, env, out_q, barrier=None):
     """Run `cases` on one communicator, every call checked.  A case: coll ("rs" / "ag" / "ar"),
     dtype, op, count (elements per rank; an all-reduce runs over n * count), inplace, algo, seed and
-    optionally calls (new inputs every call), special (f32 / f64 special values), offset (bytes: a
-    misaligned base), mem / recv_mem (device / pinned / pageable, or a per-rank list), skew_ms."""
+    optionally calls (new inputs every call), special (f32 / f64 special values), offset / recv_offset
+    (bytes: a misaligned base, or a per-rank list of them; recv_offset defaults to offset), mem /
+    recv_mem (device / pinned / pageable, or a per-rank list), skew_ms."""
     try:
         os.environ.update(env)
         os.environ["MINI_NCCL_PORT"] = str(port)
@@ -60,7 +73,7 @@ def coll_rank(rank, n, port, cases, env, out_q, barrier=None):
         results = []
         for case in cases:
             coll, dtype, op, c = case["coll"], case["dtype"], case.get("op", "sum"), case["count"]
-            inplace, seed, off = case.get("inplace", False), case.get("seed", 1), case.get("offset", 0)
+            inplace, seed, (off, roff) = case.get("inplace", False), case.get("seed", 1), offsets(case, rank)
             comm.set_algo(case["algo"])
             code, npd = O.DTYPES[dtype]
             esz = np.dtype(npd).itemsize
@@ -80,9 +93,9 @@ def coll_rank(rank, n, port, cases, env, out_q, barrier=None):
                 guard = hip_rt.View(whole, off + big, GUARD)
             else:
                 sbuf = hip_rt.buffer(placement("mem", "device"), ns * esz + off)
-                rbuf = hip_rt.buffer(placement("recv_mem", placement("mem", "device")), nr * esz + off + GUARD)
-                send, recv = hip_rt.View(sbuf, off, ns * esz), hip_rt.View(rbuf, off, nr * esz)
-                guard = hip_rt.View(rbuf, off + nr * esz, GUARD)
+                rbuf = hip_rt.buffer(placement("recv_mem", placement("mem", "device")), nr * esz + roff + GUARD)
+                send, recv = hip_rt.View(sbuf, off, ns * esz), hip_rt.View(rbuf, roff, nr * esz)
+                guard = hip_rt.View(rbuf, roff + nr * esz, GUARD)
                 rbuf.fill_byte(0xAB)
             bad, first, detail, rc, algos = 0, -1, "", 0, []
             rng = np.random.default_rng(seed * 97 + rank)

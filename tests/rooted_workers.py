@@ -37,12 +37,13 @@ def _placement(case, key, dflt, rank):
 def _rooted_case(comm, case, rank, n, stream, barrier, rng):
     """One Broadcast ("bc") / Reduce ("rd") case: count elements, root, inplace (on the root),
     null (a non-root passes NULL for the buffer its role does not use; otherwise a FILL-filled
-    buffer, which must come back unchanged), offset, special, calls, mem / recv_mem, skew_ms."""
+    buffer, which must come back unchanged), offset / recv_offset (each a value or a per-rank list;
+    recv_offset defaults to offset), special, calls, mem / recv_mem, skew_ms."""
     import hip_rt
     import oracle_api as O
     import rooted_ref
     coll, dtype, op, c, root = case["coll"], case["dtype"], case.get("op", "sum"), case["count"], case["root"]
-    inplace, seed, off = case.get("inplace", False), case.get("seed", 1), case.get("offset", 0)
+    inplace, seed, (off, roff) = case.get("inplace", False), case.get("seed", 1), CW.offsets(case, rank)
     code, npd = O.DTYPES[dtype]
     nb = c * np.dtype(npd).itemsize
     is_root = rank == root
@@ -60,13 +61,13 @@ def _rooted_case(comm, case, rank, n, stream, barrier, rng):
     else:
         # the unused side: NULL, or a FILL-filled buffer (with its guard) that nobody may write
         sbuf = hip_rt.buffer(mem_s, nb + off + GUARD) if uses_send or not case.get("null") else None
-        rbuf = hip_rt.buffer(mem_r, nb + off + GUARD) if uses_recv or not case.get("null") else None
+        rbuf = hip_rt.buffer(mem_r, nb + roff + GUARD) if uses_recv or not case.get("null") else None
         bufs += [b for b in (sbuf, rbuf) if b is not None]
         for b in bufs:
             b.fill_byte(FILL)
         send = hip_rt.View(sbuf, off, nb) if sbuf is not None else None
-        recv = hip_rt.View(rbuf, off, nb) if rbuf is not None else None
-        guard = hip_rt.View(rbuf, off + nb, GUARD) if uses_recv else None
+        recv = hip_rt.View(rbuf, roff, nb) if rbuf is not None else None
+        guard = hip_rt.View(rbuf, roff + nb, GUARD) if uses_recv else None
         spare = None if (uses_send and uses_recv) else (rbuf if uses_send else sbuf)
     bad, first, detail, rc, algos = 0, -1, "", 0, []
     t0 = time.time()
@@ -105,7 +106,7 @@ def _rooted_case(comm, case, rank, n, stream, barrier, rng):
             # a Reduce never writes a send buffer
             b += compare(send.download(npd, c), xs[rank], dtype, False)[0]
         if spare is not None:  # the unused buffer, whole: unchanged
-            b += int((spare.download(np.uint8, nb + off + GUARD) != FILL).sum())
+            b += int((spare.download(np.uint8, spare.nbytes) != FILL).sum())
         bad += b
     res = {"case": case, "rc": rc, "bad": bad, "first": first, "detail": detail, "algos": algos, "secs": time.time() - t0}
     res.update(_info_fields(comm))
@@ -116,11 +117,12 @@ def _rooted_case(comm, case, rank, n, stream, barrier, rng):
 
 def _unrooted_case(comm, case, rank, n, stream, barrier, rng):
     """An all-reduce / reduce-scatter / all-gather between the rooted calls (device buffers, out of
-    place or in place as coll_workers.coll_rank lays them out), checked the same way."""
+    place or in place as coll_workers.coll_rank lays them out, offset / recv_offset included), checked
+    the same way."""
     import hip_rt
     import oracle_api as O
     coll, dtype, op, c = case["coll"], case["dtype"], case.get("op", "sum"), case["count"]
-    inplace, seed = case.get("inplace", False), case.get("seed", 1)
+    inplace, seed, (off, roff) = case.get("inplace", False), case.get("seed", 1), CW.offsets(case, rank)
     code, npd = O.DTYPES[dtype]
     esz = np.dtype(npd).itemsize
     ns = n * c if coll in ("rs", "ar") else c
@@ -128,16 +130,16 @@ def _unrooted_case(comm, case, rank, n, stream, barrier, rng):
     mine = rank * c * esz if coll != "ar" else 0
     big = max(ns, nr) * esz
     if inplace:
-        whole = hip_rt.DeviceBuffer(big + GUARD)
+        whole = hip_rt.DeviceBuffer(big + off + GUARD)
         bufs = [whole]
-        send = hip_rt.View(whole, mine if coll == "ag" else 0, ns * esz)
-        recv = hip_rt.View(whole, mine if coll == "rs" else 0, nr * esz)
-        guard = hip_rt.View(whole, big, GUARD)
+        send = hip_rt.View(whole, off + (mine if coll == "ag" else 0), ns * esz)
+        recv = hip_rt.View(whole, off + (mine if coll == "rs" else 0), nr * esz)
+        guard = hip_rt.View(whole, off + big, GUARD)
     else:
-        sbuf, rbuf = hip_rt.DeviceBuffer(ns * esz), hip_rt.DeviceBuffer(nr * esz + GUARD)
+        sbuf, rbuf = hip_rt.DeviceBuffer(ns * esz + off), hip_rt.DeviceBuffer(nr * esz + roff + GUARD)
         bufs = [sbuf, rbuf]
-        send, recv = hip_rt.View(sbuf, 0, ns * esz), hip_rt.View(rbuf, 0, nr * esz)
-        guard = hip_rt.View(rbuf, nr * esz, GUARD)
+        send, recv = hip_rt.View(sbuf, off, ns * esz), hip_rt.View(rbuf, roff, nr * esz)
+        guard = hip_rt.View(rbuf, roff + nr * esz, GUARD)
         rbuf.fill_byte(FILL)
     xs = make_inputs(n, ns, dtype, seed, False)
     exp = CW.expected(coll, xs, rank, dtype, op)
