@@ -506,6 +506,7 @@ int mnccl_topology_blocks_read(int n, const int* link, const int* hops) { return
 int mnccl_read_grid_form(int forced, int auto_mode, int vec, uint64_t chunk_bytes, int n, uint64_t min_bytes) {
   return read_grid_form(forced != 0, auto_mode != 0, vec != 0, chunk_bytes, n, min_bytes) ? 1 : 0;
 }
+int mnccl_read_grid_vectors(int n) { return read_grid_vectors(n); }
 
 // Runs `calls` consecutive all-reduces (send -> recv, fp32; send == recv for in place) on n
 // simulated ranks with the GPU kernels' protocol; call i uses schedule (algo >> 3i) & 7 (0 ring,

@@ -118,15 +118,18 @@ def _rooted_case(comm, case, rank, n, stream, barrier, rng):
 def _unrooted_case(comm, case, rank, n, stream, barrier, rng):
     """An all-reduce / reduce-scatter / all-gather between the rooted calls (device buffers, out of
     place or in place as coll_workers.coll_rank lays them out, offset / recv_offset included), checked
-    the same way."""
+    the same way.  An all-reduce's tail: elements past the n chunks (count = n * c + tail), which keep
+    this rank's input; special: f32 / f64 special values among the inputs.  Out of place the send must
+    come back unchanged; grid_calls: the calls this one added to the communicator's read_grid_calls."""
     import hip_rt
     import oracle_api as O
     coll, dtype, op, c = case["coll"], case["dtype"], case.get("op", "sum"), case["count"]
     inplace, seed, (off, roff) = case.get("inplace", False), case.get("seed", 1), CW.offsets(case, rank)
     code, npd = O.DTYPES[dtype]
     esz = np.dtype(npd).itemsize
-    ns = n * c if coll in ("rs", "ar") else c
-    nr = n * c if coll in ("ag", "ar") else c
+    tail = case.get("tail", 0) if coll == "ar" else 0
+    ns = n * c + tail if coll in ("rs", "ar") else c
+    nr = n * c + tail if coll in ("ag", "ar") else c
     mine = rank * c * esz if coll != "ar" else 0
     big = max(ns, nr) * esz
     if inplace:
@@ -141,7 +144,7 @@ def _unrooted_case(comm, case, rank, n, stream, barrier, rng):
         send, recv = hip_rt.View(sbuf, off, ns * esz), hip_rt.View(rbuf, roff, nr * esz)
         guard = hip_rt.View(rbuf, roff + nr * esz, GUARD)
         rbuf.fill_byte(FILL)
-    xs = make_inputs(n, ns, dtype, seed, False)
+    xs = make_inputs(n, ns, dtype, seed, case.get("special", False))
     exp = CW.expected(coll, xs, rank, dtype, op)
     send.upload(xs[rank])
     guard.upload(np.full(GUARD, FILL, np.uint8))
@@ -151,6 +154,7 @@ def _unrooted_case(comm, case, rank, n, stream, barrier, rng):
     if case.get("skew_ms"):
         time.sleep(float(rng.uniform(0, case["skew_ms"])) / 1000.0)
     t0 = time.time()
+    grid0 = comm.info()["read_grid_calls"]
     rc = CW.call(comm, coll, send.ptr, recv.ptr, c if coll != "ar" else ns, code, O.OPS[op], stream.handle)
     bad, first, detail, algos = -1, -1, "", []
     if rc == 0:
@@ -161,7 +165,10 @@ def _unrooted_case(comm, case, rank, n, stream, barrier, rng):
         if bad:
             detail = f"got {got[first]!r} expected {exp[first]!r}"
         bad += int((guard.download(np.uint8, GUARD) != FILL).sum())
-    res = {"case": case, "rc": rc, "bad": bad, "first": first, "detail": detail, "algos": algos, "secs": time.time() - t0}
+        if not inplace:  # the send is only read
+            bad += compare(send.download(npd, ns), xs[rank], dtype, False)[0]
+    res = {"case": case, "rc": rc, "bad": bad, "first": first, "detail": detail, "algos": algos, "secs": time.time() - t0,
+           "grid_calls": comm.info()["read_grid_calls"] - grid0}
     res.update(_info_fields(comm))
     for b in bufs:
         b.free()

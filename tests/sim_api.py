@@ -27,6 +27,7 @@ def load():
         L.mnccl_resident_pipes.argtypes = [i, i, i, i, i]
         L.mnccl_topology_blocks_read.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(i)]
         L.mnccl_read_grid_form.argtypes = [i, i, i, u64, i, u64]
+        L.mnccl_read_grid_vectors.argtypes = [i]
         L.mnccl_sim_signed_read.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), i, u64, i, u64,
                                             ctypes.POINTER(u64), u64, ctypes.POINTER(i)]
         L.mnccl_oneshot_slice.argtypes = [u64, i, i, u64]
@@ -157,3 +158,8 @@ def read_grid_form(forced, auto_mode, vec, chunk_bytes, n, min_bytes=4 << 20):
     at least min_bytes: MINI_NCCL_GRID_MIN, default kReadGridMin = 4 MiB)."""
     return bool(load().mnccl_read_grid_form(int(forced), int(auto_mode), int(vec), chunk_bytes, n,
                                             min_bytes))
+
+
+def read_grid_vectors(n):
+    """csrc/schedule.h read_grid_vectors: 16-byte vectors per lane of a grid workgroup at n ranks."""
+    return load().mnccl_read_grid_vectors(n)

@@ -10,6 +10,11 @@ S - 1, S, S + 1 with a sub-vector tail, 2S, 2S + 1 and 3S + 1 vectors for every 
 read_fold_all, gather_push_vec, relay_vec and exchange_push_vec, 1023 ... 1024 + 129 for the fold past
 8 ranks, 511 ... 1025 for the ring's move_vec.
 
+The all-reduce's grid form (read_start / read_grid / read_done) runs at MINI_NCCL_GRID_MIN=65536, so a
+chunk is 64 KiB and the last workgroup's bytes: 0 (a whole batch of B = 1024 * V), 16, B - 16 and one
+vector either side of every row boundary, at n = 2 ... 8, at every V the MINI_NCCL_GRID_VECTORS knob
+sets, the whole dtype x op matrix, and bases off 16 bytes; read_grid_calls is checked per call.
+
 Rank r runs on GPU r % ndev, or every rank on GPU 0 on a 1-GPU box (gpu_workers.rank_device): with
 the ranks sharing a GPU these tests check the loops' arithmetic and addressing, not cross-device
 visibility.
@@ -58,7 +63,10 @@ def _run_group(name, timeout=300):
             assert res["async"] == 0
             assert res["ipc_open_failures"] == 0 and res["read_map_failures"] == 0, (r, c, res)
             # device buffers: the read schedule where it is asked for (the element path too), else the ring
-            assert res["algos"] == [c["algo"]], f"rank {r} case {c}: ran schedules {res['algos']}"
+            # (expect_algo: what a forced grid or auto call reports -- the read schedule)
+            assert res["algos"] == [c.get("expect_algo", c["algo"])], f"rank {r} case {c}: ran schedules {res['algos']}"
+            if "expect_grid" in c:
+                assert res["grid_calls"] == (1 if c["expect_grid"] else 0), f"rank {r} case {c}: {res['grid_calls']} grid-form calls"
     return out
 
 
@@ -97,3 +105,28 @@ def test_base_per_rank_and_buffer(dev, n):
     vector path, every rank and buffer on another 16-byte phase), and rank 1 alone 2-byte-misaligned
     with bf16 (the element path on every rank of the read schedule): every collective, read and ring."""
     _run_group(f"align-n{n}")
+
+
+@pytest.mark.parametrize("n", B.GRID_NS)
+def test_grid_batch_boundaries(dev, n):
+    """The all-reduce's grid form at every rank count it has (G = 1, 2, 4, 4, 7, 7, 7 peer slots, the
+    last two masked at n = 6 and 7), chunks of 64 KiB and a last workgroup of every class of the
+    rule's V: f32 and bf16 sum out of place and in place with and without a tail, the 5 x 4 dtype x op
+    matrix one vector into the last row, and the calls either side of the threshold, forced and auto,
+    so that grid and persistent calls follow each other on one communicator."""
+    _run_group(f"grid-n{n}")
+
+
+@pytest.mark.parametrize("n,vectors", [(n, v) for n in B.GRID_NS for v in B.GRID_VS if v != B.grid_rule_v(n)])
+def test_grid_vectors_batch_boundaries(dev, n, vectors):
+    """MINI_NCCL_GRID_VECTORS off the rule: f32 sum at every class of the knob's V (the host's grid
+    and the kernel's template argument must agree on it), f32 prod and bf16 sum on the rule's."""
+    _run_group(f"grid-v-n{n}-v{vectors}")
+
+
+@pytest.mark.parametrize("n", B.GRID_ALIGN_NS)
+def test_grid_bases_off_16_bytes(dev, n):
+    """The grid form with rank r's send 4 * (r mod 4) and its recv 4 * ((r + 1) mod 4) bytes into
+    their allocations; rank 1 alone 2-byte-misaligned with bf16 runs the persistent kernel's element
+    path instead."""
+    _run_group(f"grid-align-n{n}")
