@@ -580,6 +580,20 @@ void Comm::wait_previous_call() {
   if (have_last_) hip_check(hipEventSynchronize(order_ev_), "wait for the previous call");
 }
 
+// The persistent kernel of a schedule (2 read, 3 one-shot, otherwise the ring) and collective
+static int persistent_kernel(int algo, int coll) {
+  if (algo == 3) return kKernelOneshot;
+  if (algo != 2) return kKernelRing;
+  switch (coll) {
+    case kCollReduceScatter: return kKernelScatterFold;
+    case kCollAllGather: return kKernelGatherPush;
+    case kCollReduce: return kKernelRootFold;
+    case kCollBroadcast: return kKernelRootRelay;
+    case kCollAllToAll: return kKernelExchangePush;
+    default: return kKernelRead;
+  }
+}
+
 void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, int dtype, int op, hipStream_t stream,
                   uint32_t seq, bool vec, const char* const* psend, const char* const* precv,
                   size_t tail_bytes, uint64_t sig, int coll, int root, size_t total_bytes) {
@@ -641,16 +655,9 @@ void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, in
   // (the all-reduce's alone: its halves have the persistent form only)
   const bool grid = algo == 2 && coll == kCollAllReduce && read_grid_form(algo_ == 4, auto_, vec, chunk_bytes, n,
                                                                           cfg_.grid_min);
-  hipError_t e = grid        ? launch_read_grid(dtype, op, p, stream, cfg_.grid_vectors)
-                 : algo == 2 && coll == kCollReduceScatter ? launch_scatter_fold(dtype, op, vec, wg, nt, p, stream)
-                 : algo == 2 && coll == kCollAllGather     ? launch_gather_push(dtype, vec, wg, nt, p, stream)
-                 : algo == 2 && coll == kCollReduce        ? launch_root_fold(dtype, op, vec, wg, nt, p, stream)
-                 : algo == 2 && coll == kCollBroadcast     ? launch_root_relay(dtype, vec, wg, nt, p, stream)
-                 : algo == 2 && coll == kCollAllToAll      ? launch_exchange_push(dtype, vec, wg, nt, p, stream)
-                 : algo == 2 ? launch_read(dtype, op, vec, wg, nt, p, stream)
-                 : algo == 3 ? launch_oneshot(dtype, op, vec, wg, nt, p, stream)
-                             : launch_ring(dtype, op, vec, wg, nt, p, stream);
-  hip_check(e, "kernel launch");
+  hip_check(grid ? launch_read_grid(dtype, op, p, stream, cfg_.grid_vectors)
+                 : launch_persistent(persistent_kernel(algo, coll), dtype, op, vec, wg, nt, p, stream),
+            "kernel launch");
   last_algo_ = algo;
   if (grid) ++read_grid_calls_;
 }

@@ -62,34 +62,34 @@ constexpr int kMaxRanks = 16;
 // waves resident at once, and every rank's pipeline w waits for its peers' pipeline w.
 constexpr int kMinWavesPerSimd = 2;
 
+// The persistent kernels: one launch per call, `channels` workgroups of `threads`.
+enum PersistentKernel : int {
+  kKernelRing,     // the ring schedule, every collective (p.coll picks the op table)
+  kKernelRead,     // the read schedule's all-reduce
+  kKernelOneshot,  // the one-shot all-reduce
+  // the read schedule's two halves as collectives of their own (p.coll 1 / 2, the persistent form
+  // and protocol of kKernelRead): scatter_fold folds chunk `rank` of every peer's send into recv;
+  // gather_push stores send into chunk `rank` of every rank's recv (by element size: no arithmetic)
+  kKernelScatterFold,
+  kKernelGatherPush,
+  // the read schedule's rooted collectives (p.coll 4 / 3; the same persistent form and protocol):
+  // root_fold folds chunk `rank` of every rank's send into the ROOT's recv at the same offset (p.recv
+  // is that buffer: the host passes its mapping of the root's recv on the other ranks); root_relay
+  // copies chunk `rank` of the root's send into every rank's recv (by element size: no arithmetic)
+  kKernelRootFold,
+  kKernelRootRelay,
+  // the read schedule's all-to-all (p.coll 5; the same persistent form and protocol; a chunk is one
+  // block of the n in send and in recv): exchange_push stores block q of send into block `rank` of
+  // rank q's recv, for every q (by element size: no arithmetic)
+  kKernelExchangePush,
+};
+
 // Launchers return hipSuccess or the launch error; dtype/op must be supported
 // (checked by the caller).  vec = 16-byte path (all offsets 16-byte aligned).
-hipError_t launch_ring(int dtype, int op, bool vec, int channels, int threads,
-                       const CollParams& p, hipStream_t stream);
-hipError_t launch_read(int dtype, int op, bool vec, int channels, int threads,
-                       const CollParams& p, hipStream_t stream);
-hipError_t launch_oneshot(int dtype, int op, bool vec, int channels, int threads,
-                          const CollParams& p, hipStream_t stream);
-// the read schedule's two halves as collectives of their own (p.coll 1 / 2, the persistent form
-// and protocol of launch_read): scatter_fold folds chunk `rank` of every peer's send into recv;
-// gather_push stores send into chunk `rank` of every rank's recv (by element size: no arithmetic)
-hipError_t launch_scatter_fold(int dtype, int op, bool vec, int channels, int threads,
-                               const CollParams& p, hipStream_t stream);
-hipError_t launch_gather_push(int dtype, bool vec, int channels, int threads,
-                              const CollParams& p, hipStream_t stream);
-// the read schedule's rooted collectives (p.coll 4 / 3; the same persistent form and protocol):
-// root_fold folds chunk `rank` of every rank's send into the ROOT's recv at the same offset (p.recv
-// is that buffer: the host passes its mapping of the root's recv on the other ranks); root_relay
-// copies chunk `rank` of the root's send into every rank's recv (by element size: no arithmetic)
-hipError_t launch_root_fold(int dtype, int op, bool vec, int channels, int threads,
-                            const CollParams& p, hipStream_t stream);
-hipError_t launch_root_relay(int dtype, bool vec, int channels, int threads,
+// launch_persistent refuses a p.coll that is not the kernel's, a root outside [0, n) for the
+// rooted kernels and n < 2 for the all-to-all; the kernels that only copy ignore op.
+hipError_t launch_persistent(int kernel, int dtype, int op, bool vec, int channels, int threads,
                              const CollParams& p, hipStream_t stream);
-// the read schedule's all-to-all (p.coll 5; the same persistent form and protocol; a chunk is one
-// block of the n in send and in recv): exchange_push stores block q of send into block `rank` of
-// rank q's recv, for every q (by element size: no arithmetic)
-hipError_t launch_exchange_push(int dtype, bool vec, int channels, int threads,
-                                const CollParams& p, hipStream_t stream);
 // the read schedule's push form for large calls as three launches (start, grid fold, done):
 // schedule.h read_grid_fits(p.chunk_bytes, p.n, kReadGridFloor) (2 <= n <= 8, whole 16-byte vectors), p.go set
 // vectors: 0 = schedule.h read_grid_vectors; 1 / 2 / 4 (MINI_NCCL_GRID_VECTORS) for fp32 Sum only

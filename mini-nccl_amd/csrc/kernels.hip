@@ -19,6 +19,8 @@
 //  root_fold / root_relay   the rooted collectives (ncclReduce / ncclBroadcast) on the same
 //                 protocol: every rank folds, or copies out of the root's send, chunk `rank` only,
 //                 so no link carries the whole buffer.  Their fallback is ring_kernel too.
+//                 root_relay and gather_push run one loop (copy_push_slice): load a slice once,
+//                 store it into this rank's recv and push it into the other ranks'.
 //  exchange_push  the all-to-all (ncclAllToAll) on the same protocol: every rank pushes block q of
 //                 its own send into rank q's recv, so every block crosses one link once.  Its
 //                 fallback is ring_kernel with a table of hops (schedule.h coll_op).
@@ -660,12 +662,7 @@ __device__ __forceinline__ void read_fold_wide(const CollParams& p, uint64_t cof
 // per peer, 4-5: 4 KiB, 6-8: 3 KiB; all within 256 registers without spilling).  Measured on
 // the one-GPU proxy against the one-peer-ahead batches below (used past 8 ranks): equal at 2
 // and 3 ranks (profiles/r2_read_fold_all_n23_ab.txt), 0.94-1.05x at 4 and 8.
-#ifndef MNCCL_READ_FOLD_ALL
-#define MNCCL_READ_FOLD_ALL 1
-#endif
-#ifndef MNCCL_FOLD_ALL_MIN_N
-#define MNCCL_FOLD_ALL_MIN_N 2
-#endif
+//
 // The read schedule's second half: each rank pushes its result slices into every peer's recv
 // (sc0 sc1 stores, straight from the fold's registers) -- no per-iteration READY, no copy phase,
 // and each GPU's HBM moves 2n chunks per call (a load form, every peer reading the result back
@@ -675,22 +672,14 @@ __device__ __forceinline__ void read_fold_wide(const CollParams& p, uint64_t cof
 // loads of that slice).  The pushes are sc0 sc1 stores: each is acknowledged once it reached the
 // owner's memory, which drops any copy of the line the owner's L2 kept (file header), and this
 // rank never reads the pushed ranges inside the call.
-
-// The fold's store into this rank's OWN recv: no peer reads it inside the call (the pushes are the
-// peers' copies), so it needs no system-scope write-through -- MNCCL_OWN_NT=1 stores it
-// non-temporal, as the local reduce does (an A/B knob; the pushes stay sc0 sc1).
-#ifndef MNCCL_OWN_NT
-#define MNCCL_OWN_NT 0
-#endif
-__device__ __forceinline__ void st_own16(rsrc_t r, uint32_t off, v4u v) {
-  if (MNCCL_OWN_NT) st_nt16(r, off, v);
-  else st_slot16(r, off, v);
-}
-
-// PUSH = false (scatter_fold, ncclReduceScatter): the same fold stored into this rank's recv only.
-// SYS (root_fold, ncclReduce: p.recv is the ROOT's recv, another agent's memory on every rank but
-// the root): the one store is a push and stays sc0 sc1 whatever MNCCL_OWN_NT says.
-template <typename T, int OPC, int G, int V, bool PUSH = true, bool SYS = false>
+//
+// The fold's store into p.recv is sc0 sc1 like the pushes.  No peer reads this rank's OWN recv
+// inside the call, so there it could be non-temporal, as the local reduce's is: measured equal
+// within the spread and not shipped (profiles/r6_own_nt_store_ab.txt).
+// PUSH = false (scatter_fold, ncclReduceScatter): the same fold stored into p.recv only.  For
+// root_fold (ncclReduce) p.recv is the ROOT's recv, another agent's memory on every rank but the
+// root: there the one store is a push and has to be sc0 sc1.
+template <typename T, int OPC, int G, int V, bool PUSH = true>
 __device__ __forceinline__ void read_fold_all(const CollParams& p, uint64_t coff, uint32_t nvec, int lane) {
   constexpr uint32_t step = 64 * V;
   const int n = p.n, r = p.rank, w = wave_id().w;
@@ -724,10 +713,7 @@ __device__ __forceinline__ void read_fold_all(const CollParams& p, uint64_t coff
         for (int u = 0; u < V; ++u) a[u] = reduce16<T, OPC>(x[g][u], a[u]);
       }
 #pragma unroll
-    for (int u = 0; u < V; ++u) {
-      if (SYS) st_slot16(out, (b + (uint32_t)(u * 64 + lane)) * 16, a[u]);
-      else st_own16(out, (b + (uint32_t)(u * 64 + lane)) * 16, a[u]);
-    }
+    for (int u = 0; u < V; ++u) st_slot16(out, (b + (uint32_t)(u * 64 + lane)) * 16, a[u]);
 #pragma unroll
     for (int g = 0; g < (PUSH ? G : 0); ++g)
       if (g + 1 < n) {
@@ -755,7 +741,7 @@ __device__ __forceinline__ void read_fold_all(const CollParams& p, uint64_t coff
 
 // Returns the leading bytes of the slice whose result it also pushed to the peers (PUSH = false:
 // nothing is pushed and the value means nothing).
-template <typename T, int OPC, bool VEC, bool PUSH = true, bool SYS = false>
+template <typename T, int OPC, bool VEC, bool PUSH = true>
 __device__ __forceinline__ uint32_t read_fold(const CollParams& p, uint64_t coff, uint32_t nbytes, int lane) {
   if (!VEC) {
     read_fold_scalar<T, OPC>(p, coff, nbytes, lane, 0);
@@ -763,15 +749,17 @@ __device__ __forceinline__ uint32_t read_fold(const CollParams& p, uint64_t coff
   }
   const int n = p.n, r = p.rank;
   const uint32_t nvec = nbytes >> 4;
-  if (MNCCL_READ_FOLD_ALL && n >= MNCCL_FOLD_ALL_MIN_N && n <= 8) {
+  // (n >= 2 holds for every launched call, Comm::collective; stated, it keeps a rank count the
+  // ladder below has no slot for out of it, and the compiler schedules the fold with that)
+  if (n >= 2 && n <= 8) {
     // (2-byte types widen to f32 in reduce16: fewer vectors per peer keep the bf16 / fp16
     // variants within 256 registers without spilling)
     constexpr int h = sizeof(T) == 2 ? 1 : 0;
     if (!nvec) {
-    } else if (n == 2) read_fold_all<T, OPC, 1, 12 - 4 * h, PUSH, SYS>(p, coff, nvec, lane);
-    else if (n == 3) read_fold_all<T, OPC, 2, 8 - 2 * h, PUSH, SYS>(p, coff, nvec, lane);
-    else if (n <= 5) read_fold_all<T, OPC, 4, 4 - h, PUSH, SYS>(p, coff, nvec, lane);
-    else read_fold_all<T, OPC, 7, 3 - h, PUSH, SYS>(p, coff, nvec, lane);
+    } else if (n == 2) read_fold_all<T, OPC, 1, 12 - 4 * h, PUSH>(p, coff, nvec, lane);
+    else if (n == 3) read_fold_all<T, OPC, 2, 8 - 2 * h, PUSH>(p, coff, nvec, lane);
+    else if (n <= 5) read_fold_all<T, OPC, 4, 4 - h, PUSH>(p, coff, nvec, lane);
+    else read_fold_all<T, OPC, 7, 3 - h, PUSH>(p, coff, nvec, lane);
     if (nbytes & 15u) read_fold_scalar<T, OPC>(p, coff, nbytes, lane, nvec * 16);
     return nvec * 16;
   }
@@ -974,46 +962,57 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scatter_fold(Co
   read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, OPC, VEC, false>(p, coff, len, lane); });
 }
 
-// All-gather, 16-byte vectors of one slice: V vectors per lane per batch, loaded non-temporal from
-// this rank's send, stored into its own recv and pushed into every peer's recv at chunk r with the
-// sc0 sc1 stores whose visibility to the owner's later kernels the all-reduce's pushes rely on
-// (file header).  Two batches in flight per wave: the next batch's loads leave before this one is
-// stored -- unconditionally, for the vmcnt reason read_fold_all explains; past the slice they fall
-// outside the buffer resource, return 0 and touch nothing.  Pipeline w starts its pushes at peer
-// w mod n-1, so a rank's pipelines spread over all links.  own = false (in place): the own store's
-// resource is empty and drops it.  G peer slots up to 8 ranks (their descriptors stay in SGPRs);
-// G = 0: any rank count, the peers in a loop.
+// ---------------------------------------------------------------- copy and push
+// The loop of the all-gather (gather_push) and of the broadcast (root_relay): a slice of chunk r is
+// loaded once from `from` and stored into this rank's recv and into the recv of D other ranks.
+// Destination j of D, in ring order from r + 1, one rank left out (the broadcast's root in place):
+__device__ __forceinline__ int push_peer(int n, int r, int j, int skip) {  // skip: ring distance to that rank, 0 = none
+  const int k = 1 + j;
+  return direct_peer(n, r, skip && k >= skip ? k + 1 : k);
+}
+
+// 16-byte vectors of one slice: V vectors per lane per batch, loaded non-temporal when `from` is
+// this rank's own memory (LOCAL) and sc0 sc1 over the link otherwise, as the fold loads its peers;
+// stored into this rank's recv and pushed into the D destinations' recv with the sc0 sc1 stores
+// whose visibility to the owner's later kernels the all-reduce's pushes rely on (file header).
+// Two batches in flight per wave: the next batch's loads leave before this one is stored --
+// unconditionally, for the vmcnt reason read_fold_all explains; past the slice they fall outside
+// the buffer resource, return 0 and touch nothing.  Pipeline w starts its pushes at destination
+// w mod D, so a rank's pipelines spread over all links.  own = false (the chunk already is in this
+// rank's recv): the own store's resource is empty and drops it.  G descriptor slots up to 8 ranks
+// (they stay in SGPRs; a slot past D is empty); G = 0: any rank count, the destinations in a loop.
 constexpr int kGatherV = 8;
 
-template <int G, int V>
-__device__ __forceinline__ void gather_push_vec(const CollParams& p, uint64_t coff, uint32_t nvec, int lane, bool own) {
+template <int G, int V, bool LOCAL>
+__device__ __forceinline__ void copy_push_vec(const CollParams& p, const char* from, uint64_t coff, uint32_t nvec, int lane,
+                                              bool own, int D, int skip) {
   constexpr uint32_t step = 64 * V;
   constexpr int GS = G > 0 ? G : 1;
   const int n = p.n, r = p.rank, w = wave_id().w;
   const uint32_t vb = nvec * 16;
-  const rsrc_t src = make_rsrc(p.send + coff, vb), out = make_rsrc(p.recv + coff, own ? vb : 0u);
+  const rsrc_t src = make_rsrc(from + coff, vb), out = make_rsrc(p.recv + coff, own ? vb : 0u);
   rsrc_t pout[GS];
 #pragma unroll
-  for (int g = 0; g < G; ++g)
-    pout[g] = make_rsrc(p.peer_recv[direct_peer(n, r, 1 + (g + 1 < n ? (g + w) % (n - 1) : 0))] + coff, vb);
+  for (int g = 0; g < G; ++g) pout[g] = make_rsrc(p.peer_recv[push_peer(n, r, g < D ? (g + w) % D : 0, skip)] + coff, g < D ? vb : 0u);
   v4u xa[V], xb[V];
   auto load = [&](v4u(&x)[V], uint32_t b) {
 #pragma unroll
-    for (int u = 0; u < V; ++u) x[u] = ld_nt16(src, (b + (uint32_t)(u * 64 + lane)) * 16);
+    for (int u = 0; u < V; ++u)
+      x[u] = LOCAL ? ld_nt16(src, (b + (uint32_t)(u * 64 + lane)) * 16) : ld_slot16(src, (b + (uint32_t)(u * 64 + lane)) * 16);
   };
   auto store = [&](v4u(&x)[V], uint32_t b) {
 #pragma unroll
-    for (int u = 0; u < V; ++u) st_own16(out, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+    for (int u = 0; u < V; ++u) st_slot16(out, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
     if (G > 0) {
 #pragma unroll
       for (int g = 0; g < G; ++g)
-        if (g + 1 < n) {
+        if (g < D) {
 #pragma unroll
           for (int u = 0; u < V; ++u) st_slot16(pout[g], (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
         }
     } else {
-      for (int k = 0; k + 1 < n; ++k) {
-        const rsrc_t po = make_rsrc(p.peer_recv[direct_peer(n, r, 1 + (k + w) % (n - 1))] + coff, vb);
+      for (int j = 0; j < D; ++j) {
+        const rsrc_t po = make_rsrc(p.peer_recv[push_peer(n, r, (j + w) % D, skip)] + coff, vb);
 #pragma unroll
         for (int u = 0; u < V; ++u) st_slot16(po, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
       }
@@ -1031,42 +1030,44 @@ __device__ __forceinline__ void gather_push_vec(const CollParams& p, uint64_t co
   }
 }
 
-// slice `nbytes` at byte `coff` of every recv (chunk r), from the same offset of p.send (send -
-// r * chunk_bytes, Comm::launch); the last nbytes % 16 bytes, and everything without VEC, element
-// by element
-template <int ESZ, bool VEC>
-__device__ __forceinline__ void gather_slice(const CollParams& p, uint64_t coff, uint32_t nbytes, int lane) {
+// slice `nbytes` at byte `coff` of `from` into the same offset of every recv; the last nbytes % 16
+// bytes, and everything without VEC, element by element
+template <int ESZ, bool VEC, bool LOCAL>
+__device__ __forceinline__ void copy_push_slice(const CollParams& p, const char* from, bool own, int D, int skip,
+                                                uint64_t coff, uint32_t nbytes, int lane) {
   const int n = p.n, r = p.rank;
-  const bool own = p.send != p.recv;  // in place: this rank's chunk already is in its recv
   uint32_t done = 0;
   if (VEC) {
     const uint32_t nvec = nbytes >> 4;
     if (!nvec) {
-    } else if (n == 2) gather_push_vec<1, kGatherV>(p, coff, nvec, lane, own);
-    else if (n == 3) gather_push_vec<2, kGatherV>(p, coff, nvec, lane, own);
-    else if (n <= 5) gather_push_vec<4, kGatherV>(p, coff, nvec, lane, own);
-    else if (n <= 8) gather_push_vec<7, kGatherV>(p, coff, nvec, lane, own);
-    else gather_push_vec<0, kGatherV>(p, coff, nvec, lane, own);
+    } else if (n == 2) copy_push_vec<1, kGatherV, LOCAL>(p, from, coff, nvec, lane, own, D, skip);
+    else if (n == 3) copy_push_vec<2, kGatherV, LOCAL>(p, from, coff, nvec, lane, own, D, skip);
+    else if (n <= 5) copy_push_vec<4, kGatherV, LOCAL>(p, from, coff, nvec, lane, own, D, skip);
+    else if (n <= 8) copy_push_vec<7, kGatherV, LOCAL>(p, from, coff, nvec, lane, own, D, skip);
+    else copy_push_vec<0, kGatherV, LOCAL>(p, from, coff, nvec, lane, own, D, skip);
     done = nvec * 16;
   }
   if (done == nbytes) return;
   typedef Scal<ESZ> S;
-  const rsrc_t src = make_rsrc(p.send + coff, nbytes), out = make_rsrc(p.recv + coff, own ? nbytes : 0u);
+  const rsrc_t src = make_rsrc(from + coff, nbytes), out = make_rsrc(p.recv + coff, own ? nbytes : 0u);
   const uint32_t ne = nbytes / ESZ;
   for (uint32_t i = done / ESZ + (uint32_t)lane; i < ne; i += 64) {
     const typename S::U v = S::ld(src, i * (uint32_t)ESZ);
     S::st(out, i * (uint32_t)ESZ, v);
-    for (int k = 1; k < n; ++k) S::st(make_rsrc(p.peer_recv[direct_peer(n, r, k)] + coff, nbytes), i * (uint32_t)ESZ, v);
+    for (int j = 0; j < D; ++j) S::st(make_rsrc(p.peer_recv[push_peer(n, r, j, skip)] + coff, nbytes), i * (uint32_t)ESZ, v);
   }
 }
 
-// All-gather: no arithmetic, so by element size only.  Only rank q ever writes chunk q of any recv,
-// and nobody reads a recv inside the call.  Each GPU's HBM moves n + 1 chunks per call (one read,
-// n writes landing in it).
+// All-gather: the slice comes from the same offset of p.send (send - r * chunk_bytes, Comm::launch)
+// and goes to all n - 1 peers; in place, this rank's chunk already is in its recv.  No arithmetic,
+// so by element size only.  Only rank q ever writes chunk q of any recv, and nobody reads a recv
+// inside the call.  Each GPU's HBM moves n + 1 chunks per call (one read, n writes landing in it).
 template <int ESZ, bool VEC>
 __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) gather_push(CollParams p) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
-  read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { gather_slice<ESZ, VEC>(p, coff, len, lane); });
+  read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) {
+    copy_push_slice<ESZ, VEC, true>(p, p.send, p.send != p.recv, p.n - 1, 0, coff, len, lane);
+  });
 }
 
 // ---------------------------------------------------------------- the rooted collectives
@@ -1082,7 +1083,7 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) gather_push(Col
 // recv: p.recv is the root's recv on every rank (Comm::launch passes this rank's mapping of it), so
 // the fold helpers address it as scatter_fold's do.  On every rank but the root that store is a
 // push into another agent's memory and needs the all-reduce's push-visibility guarantee (file
-// header): sc0 sc1, whatever MNCCL_OWN_NT says (SYS).  A non-root rank writes nothing to a buffer
+// header): sc0 sc1, as every store of the fold is.  A non-root rank writes nothing to a buffer
 // of its own.  In place on the root (recv == send): the reduce-scatter's argument -- only rank c
 // reads chunk c of anyone's send, and it stores a batch after that batch's loads.  Each GPU's HBM
 // serves n chunk reads, the root's also takes n chunk writes; a link into the root carries the
@@ -1091,117 +1092,39 @@ template <typename T, int OPC, bool VEC>
 __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) root_fold(CollParams p) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   read_half<true>(p, s_tx, s_rx,
-                  [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, OPC, VEC, false, true>(p, coff, len, lane); });
+                  [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, OPC, VEC, false>(p, coff, len, lane); });
 }
 
 // Broadcast: rank r copies its slices of chunk r from the root's send -- sc0 sc1 loads over the
 // link, as the fold loads its peers; the root reads its own send non-temporal, as gather_push does
-// (ROOT) -- into its own recv and into the recv of every other rank: gather_slice's shape with
-// another source and destination set.  The root's recv is a destination like any other when the
+// (ROOT) -- into its own recv and into the recv of every other rank: the all-gather's loop
+// (copy_push_slice) with another source and destination set.  The root's recv is a destination like any other when the
 // root's call is out of place (so the root's own copy happens inside the kernel, chunk by chunk,
 // by the rank that loaded the chunk anyway) and is left out when it is in place: every rank sees
 // that from its mappings, peer_send[root] == peer_recv[root] (were the test ever wrong, the push
 // would store the bytes just loaded from that address: only rank c touches chunk c).  So a
 // non-root rank pushes into n - 2 peers (n - 1 with the root's recv), the root into n - 1; at
 // n = 2 there is no relay.  The root's links carry 2B/n each, the others B/n (derived).
-// Destination j of D, in ring order from r + 1 and skipping the root when it is left out:
-__device__ __forceinline__ int relay_peer(int n, int r, int j, int skip) {  // skip: ring distance to the root, 0 = none
-  const int k = 1 + j;
-  return direct_peer(n, r, skip && k >= skip ? k + 1 : k);
-}
-
-// 16-byte vectors of one slice: gather_push_vec's two batches in flight (the next batch's loads
-// leave unconditionally: past the slice they fall outside the buffer resource, return 0 and touch
-// nothing), the pushes starting at destination w mod D so a rank's pipelines spread over the
-// links; G descriptor slots up to 8 ranks, G = 0: the destinations in a loop.
-template <int G, int V, bool ROOT>
-__device__ __forceinline__ void relay_vec(const CollParams& p, const char* from, uint64_t coff, uint32_t nvec, int lane,
-                                          bool own, int D, int skip) {
-  constexpr uint32_t step = 64 * V;
-  constexpr int GS = G > 0 ? G : 1;
-  const int n = p.n, r = p.rank, w = wave_id().w;
-  const uint32_t vb = nvec * 16;
-  const rsrc_t src = make_rsrc(from + coff, vb), out = make_rsrc(p.recv + coff, own ? vb : 0u);
-  rsrc_t pout[GS];
-#pragma unroll
-  for (int g = 0; g < G; ++g) pout[g] = make_rsrc(p.peer_recv[relay_peer(n, r, g < D ? (g + w) % D : 0, skip)] + coff, g < D ? vb : 0u);
-  v4u xa[V], xb[V];
-  auto load = [&](v4u(&x)[V], uint32_t b) {
-#pragma unroll
-    for (int u = 0; u < V; ++u)
-      x[u] = ROOT ? ld_nt16(src, (b + (uint32_t)(u * 64 + lane)) * 16) : ld_slot16(src, (b + (uint32_t)(u * 64 + lane)) * 16);
-  };
-  auto store = [&](v4u(&x)[V], uint32_t b) {
-#pragma unroll
-    for (int u = 0; u < V; ++u) st_own16(out, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
-    if (G > 0) {
-#pragma unroll
-      for (int g = 0; g < G; ++g)
-        if (g < D) {
-#pragma unroll
-          for (int u = 0; u < V; ++u) st_slot16(pout[g], (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
-        }
-    } else {
-      for (int j = 0; j < D; ++j) {
-        const rsrc_t po = make_rsrc(p.peer_recv[relay_peer(n, r, (j + w) % D, skip)] + coff, vb);
-#pragma unroll
-        for (int u = 0; u < V; ++u) st_slot16(po, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
-      }
-    }
-  };
-  uint32_t b = 0;
-  load(xa, b);
-  for (;;) {
-    load(xb, b + step);
-    store(xa, b);
-    if ((b += step) >= nvec) break;
-    load(xa, b + step);
-    store(xb, b);
-    if ((b += step) >= nvec) break;
-  }
-}
-
-// slice `nbytes` at byte `coff` of the root's send into the same offset of every recv; the last
-// nbytes % 16 bytes, and everything without VEC, element by element
-template <int ESZ, bool VEC, bool ROOT>
-__device__ __forceinline__ void relay_slice(const CollParams& p, uint64_t coff, uint32_t nbytes, int lane) {
-  const int n = p.n, r = p.rank, root = p.root;
-  const bool root_in_place = p.peer_send[root] == p.peer_recv[root];
-  const bool own = !(ROOT && root_in_place);  // the root in place: its chunk already is in its recv
-  const int skip = !ROOT && root_in_place ? mod_n(root - r, n) : 0;
-  const int D = n - 1 - (skip ? 1 : 0);
-  const char* from = ROOT ? p.send : p.peer_send[root];
-  uint32_t done = 0;
-  if (VEC) {
-    const uint32_t nvec = nbytes >> 4;
-    if (!nvec) {
-    } else if (n == 2) relay_vec<1, kGatherV, ROOT>(p, from, coff, nvec, lane, own, D, skip);
-    else if (n == 3) relay_vec<2, kGatherV, ROOT>(p, from, coff, nvec, lane, own, D, skip);
-    else if (n <= 5) relay_vec<4, kGatherV, ROOT>(p, from, coff, nvec, lane, own, D, skip);
-    else if (n <= 8) relay_vec<7, kGatherV, ROOT>(p, from, coff, nvec, lane, own, D, skip);
-    else relay_vec<0, kGatherV, ROOT>(p, from, coff, nvec, lane, own, D, skip);
-    done = nvec * 16;
-  }
-  if (done == nbytes) return;
-  typedef Scal<ESZ> S;
-  const rsrc_t src = make_rsrc(from + coff, nbytes), out = make_rsrc(p.recv + coff, own ? nbytes : 0u);
-  const uint32_t ne = nbytes / ESZ;
-  for (uint32_t i = done / ESZ + (uint32_t)lane; i < ne; i += 64) {
-    const typename S::U v = S::ld(src, i * (uint32_t)ESZ);
-    S::st(out, i * (uint32_t)ESZ, v);
-    for (int j = 0; j < D; ++j) S::st(make_rsrc(p.peer_recv[relay_peer(n, r, j, skip)] + coff, nbytes), i * (uint32_t)ESZ, v);
-  }
-}
-
+//
 // No arithmetic, so by element size only.  Only rank c ever writes chunk c of any recv, nobody
 // reads a recv inside the call, and the root's send is only read (in place: see above).
 template <int ESZ, bool VEC>
 __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) root_relay(CollParams p) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  // one slice, by role: its source, whether this rank's recv takes it, and the D destinations
+  auto slice = [&p](auto is_root, u64 coff, uint32_t len, int lane) {
+    constexpr bool ROOT = decltype(is_root)::value;
+    const int n = p.n, r = p.rank, root = p.root;
+    const bool root_in_place = p.peer_send[root] == p.peer_recv[root];
+    const bool own = !(ROOT && root_in_place);  // the root in place: its chunk already is in its recv
+    const int skip = !ROOT && root_in_place ? mod_n(root - r, n) : 0;
+    const int D = n - 1 - (skip ? 1 : 0);
+    copy_push_slice<ESZ, VEC, ROOT>(p, ROOT ? p.send : p.peer_send[root], own, D, skip, coff, len, lane);
+  };
   if (p.rank == p.root)
-    read_half<true>(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { relay_slice<ESZ, VEC, true>(p, coff, len, lane); });
+    read_half<true>(p, s_tx, s_rx, [&](u64 coff, uint32_t len, int lane) { slice(std::true_type{}, coff, len, lane); });
   else
-    read_half<true>(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { relay_slice<ESZ, VEC, false>(p, coff, len, lane); });
+    read_half<true>(p, s_tx, s_rx, [&](u64 coff, uint32_t len, int lane) { slice(std::false_type{}, coff, len, lane); });
 }
 
 // ---------------------------------------------------------------- the all-to-all
@@ -1244,14 +1167,9 @@ __device__ __forceinline__ void exchange_push_vec(const CollParams& p, uint64_t 
 #pragma unroll
     for (int u = 0; u < V; ++u) x[u] = ld_nt16(s, (b + (uint32_t)(u * 64 + lane)) * 16);
   };
-  auto store = [&](v4u(&x)[V], rsrc_t d, bool own, uint32_t b) {
-    if (own) {
+  auto store = [&](v4u(&x)[V], rsrc_t d, uint32_t b) {
 #pragma unroll
-      for (int u = 0; u < V; ++u) st_own16(d, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
-    } else {
-#pragma unroll
-      for (int u = 0; u < V; ++u) st_slot16(d, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
-    }
+    for (int u = 0; u < V; ++u) st_slot16(d, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
   };
   int k = 0;       // the batch about to be stored: destination k, vectors from b
   uint32_t b = 0;
@@ -1266,7 +1184,7 @@ __device__ __forceinline__ void exchange_push_vec(const CollParams& p, uint64_t 
       src = src_of(++k2);
     }
     load(nxt, src, b2);
-    store(cur, dst, k == n - 1, b);
+    store(cur, dst, b);
     if (k2 != k) dst = dst_of(k2);
     k = k2;
     b = b2;
@@ -1350,21 +1268,14 @@ __global__ void __launch_bounds__(64) read_start_kernel(CollParams p) {
 // one batch of V vectors per lane of my chunk: the peers' slices of it loaded together (G peer
 // slots, as read_fold_all), folded in ring order, stored into my recv and pushed into every
 // peer's recv (the push order rotated by workgroup so the workgroups' stores spread over the links)
-// MNCCL_GRID_WAVES: one-wave batches per workgroup (an A/B knob: fewer, larger workgroups for the
-// dispatcher; each wave still folds its own batch, wave w of workgroup b batch b * W + w)
-#ifndef MNCCL_GRID_WAVES
-#define MNCCL_GRID_WAVES 1
-#endif
-constexpr int kGridWaves = MNCCL_GRID_WAVES;
-
 template <typename T, int OPC, int G, int V>
-__global__ void __launch_bounds__(64 * kGridWaves) read_grid_kernel(CollParams p) {
+__global__ void __launch_bounds__(64) read_grid_kernel(CollParams p) {
   if (*p.go != p.call_seq) return;  // START failed: the peers' buffers are not ours to touch
   constexpr uint32_t B = 64u * 16u * V;
-  const uint32_t batch = blockIdx.x * (uint32_t)kGridWaves + (kGridWaves > 1 ? threadIdx.x / 64u : 0u);
+  const uint32_t batch = blockIdx.x;
   const uint64_t off = (uint64_t)batch * B;
   if (off >= p.chunk_bytes) return;
-  const int n = p.n, r = p.rank, lane = kGridWaves > 1 ? (int)(threadIdx.x % 64u) : (int)threadIdx.x;
+  const int n = p.n, r = p.rank, lane = (int)threadIdx.x;
   const uint32_t len = (uint32_t)(p.chunk_bytes - off < B ? p.chunk_bytes - off : B);
   const uint64_t coff = (uint64_t)r * p.chunk_bytes + off;
   const rsrc_t loc = make_rsrc(p.send + coff, len), out = make_rsrc(p.recv + coff, len);
@@ -1385,7 +1296,7 @@ __global__ void __launch_bounds__(64 * kGridWaves) read_grid_kernel(CollParams p
       for (int u = 0; u < V; ++u) a[u] = reduce16<T, OPC>(x[g][u], a[u]);
     }
 #pragma unroll
-  for (int u = 0; u < V; ++u) st_own16(out, (uint32_t)(u * 64 + lane) * 16, a[u]);
+  for (int u = 0; u < V; ++u) st_slot16(out, (uint32_t)(u * 64 + lane) * 16, a[u]);
 #pragma unroll
   for (int g = 0; g < G; ++g)
     if (g + 1 < n) {
@@ -1633,80 +1544,80 @@ hipError_t launch_link_probe(char* local, char* const* remote, int nremote, uint
 }
 
 // ---------------------------------------------------------------- dispatch
-template <template <typename, int, bool> class K>
-struct Unused {};
+// A runtime dtype / op / vec / element size becomes a tag whose type carries the constant; the
+// callee (a generic lambda) names the kernel template with it.  An unknown value is refused.
+template <typename T> struct TypeTag { using type = T; };
+template <int I> using IntTag = std::integral_constant<int, I>;
 
-#define MNCCL_DISPATCH_T(dtype, MACRO)      \
-  switch (dtype) {                          \
-    case kF32: MACRO(float); break;         \
-    case kF64: MACRO(double); break;        \
-    case kI32: MACRO(int32_t); break;       \
-    case kF16: MACRO(_Float16); break;      \
-    case kBF16: MACRO(bf16_t); break;       \
-    default: return hipErrorInvalidValue;   \
-  }
-
-template <typename T>
-static hipError_t ring_for_t(int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-#define RING_CASE(OPC)                                                                           \
-  case OPC:                                                                                      \
-    if (vec) hipLaunchKernelGGL((ring_kernel<T, OPC, true>), dim3(C), dim3(nt), 0, st, p);      \
-    else hipLaunchKernelGGL((ring_kernel<T, OPC, false>), dim3(C), dim3(nt), 0, st, p);         \
-    break;
-  switch (op) {
-    RING_CASE(kSum) RING_CASE(kProd) RING_CASE(kMax) RING_CASE(kMin)
+template <typename F>
+static hipError_t for_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case kF32: return f(TypeTag<float>{});
+    case kF64: return f(TypeTag<double>{});
+    case kI32: return f(TypeTag<int32_t>{});
+    case kF16: return f(TypeTag<_Float16>{});
+    case kBF16: return f(TypeTag<bf16_t>{});
     default: return hipErrorInvalidValue;
   }
-#undef RING_CASE
-  return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t read_for_t(int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-#define READ_LAUNCH(OPC, V) hipLaunchKernelGGL((read_kernel<T, OPC, V>), dim3(C), dim3(nt), 0, st, p);
-#define READ_CASE(OPC)           \
-  case OPC:                      \
-    if (vec) {                   \
-      READ_LAUNCH(OPC, true)     \
-    } else {                     \
-      READ_LAUNCH(OPC, false)    \
-    }                            \
-    break;
+template <typename F>
+static hipError_t for_op(int op, F&& f) {
   switch (op) {
-    READ_CASE(kSum) READ_CASE(kProd) READ_CASE(kMax) READ_CASE(kMin)
+    case kSum: return f(IntTag<kSum>{});
+    case kProd: return f(IntTag<kProd>{});
+    case kMax: return f(IntTag<kMax>{});
+    case kMin: return f(IntTag<kMin>{});
     default: return hipErrorInvalidValue;
   }
-#undef READ_CASE
-#undef READ_LAUNCH
-  return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t local_for_t(int op, void* out, const void* a, const void* b, u64 count, hipStream_t st) {
+template <typename F>
+static hipError_t for_elem_size(int dtype, F&& f) {
+  switch (dtype_size(dtype)) {
+    case 2: return f(IntTag<2>{});
+    case 4: return f(IntTag<4>{});
+    case 8: return f(IntTag<8>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
+template <typename F>
+static hipError_t for_vec(bool vec, F&& f) {
+  return vec ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// the kernels that fold: f(type, op, vec)
+template <typename F>
+static hipError_t for_type_op_vec(int dtype, int op, bool vec, F&& f) {
+  return for_dtype(dtype, [&](auto t) {
+    return for_op(op, [&](auto o) { return for_vec(vec, [&](auto v) { return f(t, o, v); }); });
+  });
+}
+
+// the kernels that only copy: f(element size, vec)
+template <typename F>
+static hipError_t for_size_vec(int dtype, bool vec, F&& f) {
+  return for_elem_size(dtype, [&](auto e) { return for_vec(vec, [&](auto v) { return f(e, v); }); });
+}
+
+template <typename T, int OPC>
+static hipError_t local_for(void* out, const void* a, const void* b, u64 count, hipStream_t st) {
   // 16-byte vectors over the body whenever the three buffers are dword-aligned (4-byte-aligned
   // dwordx4 accesses are valid on gfx950), then the last (bytes % 16) bytes element-wise
   const bool vec = ((uintptr_t)out | (uintptr_t)a | (uintptr_t)b) % 4 == 0;
   const u64 nvec = vec ? count * sizeof(T) / 16 : 0;
   const u64 done = nvec * 16 / sizeof(T);
   const u64 kMaxExactBlocks = (1ull << 31) / 64;  // keep the exact grid under 2^31 threads
-#define LOCAL_CASE(OPC)                                                                                         \
-  case OPC:                                                                                                     \
-    if (nvec && (nvec + 63) / 64 <= kMaxExactBlocks)                                                            \
-      hipLaunchKernelGGL((local_reduce_vec<T, OPC>), dim3((unsigned)((nvec + 63) / 64)), dim3(64), 0, st,      \
-                         (char*)out, (const char*)a, (const char*)b, nvec);                                     \
-    else if (nvec)                                                                                              \
-      hipLaunchKernelGGL((local_reduce_vec_gs<T, OPC>), dim3(16384), dim3(256), 0, st, (char*)out,             \
-                         (const char*)a, (const char*)b, nvec);                                                 \
-    if (count > done)                                                                                           \
-      hipLaunchKernelGGL((local_reduce_scalar<T, OPC>),                                                         \
-                         dim3((unsigned)std::min<u64>((count - done + 255) / 256, 16384)), dim3(256), 0, st,    \
-                         (T*)out + done, (const T*)a + done, (const T*)b + done, count - done);                 \
-    break;
-  switch (op) {
-    LOCAL_CASE(kSum) LOCAL_CASE(kProd) LOCAL_CASE(kMax) LOCAL_CASE(kMin)
-    default: return hipErrorInvalidValue;
-  }
-#undef LOCAL_CASE
+  if (nvec && (nvec + 63) / 64 <= kMaxExactBlocks)
+    hipLaunchKernelGGL((local_reduce_vec<T, OPC>), dim3((unsigned)((nvec + 63) / 64)), dim3(64), 0, st, (char*)out,
+                       (const char*)a, (const char*)b, nvec);
+  else if (nvec)
+    hipLaunchKernelGGL((local_reduce_vec_gs<T, OPC>), dim3(16384), dim3(256), 0, st, (char*)out, (const char*)a,
+                       (const char*)b, nvec);
+  if (count > done)
+    hipLaunchKernelGGL((local_reduce_scalar<T, OPC>), dim3((unsigned)std::min<u64>((count - done + 255) / 256, 16384)),
+                       dim3(256), 0, st, (T*)out + done, (const T*)a + done, (const T*)b + done, count - done);
   return hipGetLastError();
 }
 
@@ -1716,162 +1627,71 @@ hipError_t preload_kernels() {
   return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&read_start_kernel));
 }
 
-hipError_t launch_ring(int dtype, int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-#define M(T) return ring_for_t<T>(op, vec, C, nt, p, st)
-  MNCCL_DISPATCH_T(dtype, M)
-#undef M
-}
-
-hipError_t launch_read(int dtype, int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-#define M(T) return read_for_t<T>(op, vec, C, nt, p, st)
-  MNCCL_DISPATCH_T(dtype, M)
-#undef M
-}
-
-template <typename T>
-static hipError_t scatter_for_t(int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-#define SCATTER_CASE(OPC)                                                                        \
-  case OPC:                                                                                      \
-    if (vec) hipLaunchKernelGGL((scatter_fold<T, OPC, true>), dim3(C), dim3(nt), 0, st, p);     \
-    else hipLaunchKernelGGL((scatter_fold<T, OPC, false>), dim3(C), dim3(nt), 0, st, p);        \
-    break;
-  switch (op) {
-    SCATTER_CASE(kSum) SCATTER_CASE(kProd) SCATTER_CASE(kMax) SCATTER_CASE(kMin)
-    default: return hipErrorInvalidValue;
-  }
-#undef SCATTER_CASE
+template <typename K>
+static hipError_t launch_on(K kernel, int C, int nt, const CollParams& p, hipStream_t st) {
+  hipLaunchKernelGGL(kernel, dim3(C), dim3(nt), 0, st, p);
   return hipGetLastError();
 }
 
-hipError_t launch_scatter_fold(int dtype, int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-  if (p.coll != kCollReduceScatter) return hipErrorInvalidValue;
-#define M(T) return scatter_for_t<T>(op, vec, C, nt, p, st)
-  MNCCL_DISPATCH_T(dtype, M)
-#undef M
-}
-
-hipError_t launch_gather_push(int dtype, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-  if (p.coll != kCollAllGather) return hipErrorInvalidValue;
-#define GATHER_CASE(ESZ)                                                                         \
-  case ESZ:                                                                                      \
-    if (vec) hipLaunchKernelGGL((gather_push<ESZ, true>), dim3(C), dim3(nt), 0, st, p);         \
-    else hipLaunchKernelGGL((gather_push<ESZ, false>), dim3(C), dim3(nt), 0, st, p);            \
-    break;
-  switch (dtype_size(dtype)) {
-    GATHER_CASE(2) GATHER_CASE(4) GATHER_CASE(8)
+hipError_t launch_persistent(int kernel, int dtype, int op, bool vec, int C, int nt, const CollParams& p,
+                             hipStream_t st) {
+  const bool root_ok = p.root >= 0 && p.root < p.n;
+#define FOLDS(K)                                                                                              \
+  for_type_op_vec(dtype, op, vec, [&](auto t, auto o, auto v) {                                              \
+    return launch_on(K<typename decltype(t)::type, decltype(o)::value, decltype(v)::value>, C, nt, p, st);   \
+  })
+#define COPIES(K) \
+  for_size_vec(dtype, vec, [&](auto e, auto v) { return launch_on(K<decltype(e)::value, decltype(v)::value>, C, nt, p, st); })
+  switch (kernel) {
+    case kKernelRing: return FOLDS(ring_kernel);
+    case kKernelRead: return FOLDS(read_kernel);
+    case kKernelOneshot: return FOLDS(oneshot_kernel);
+    case kKernelScatterFold: return p.coll == kCollReduceScatter ? FOLDS(scatter_fold) : hipErrorInvalidValue;
+    case kKernelGatherPush: return p.coll == kCollAllGather ? COPIES(gather_push) : hipErrorInvalidValue;
+    case kKernelRootFold: return p.coll == kCollReduce && root_ok ? FOLDS(root_fold) : hipErrorInvalidValue;
+    case kKernelRootRelay: return p.coll == kCollBroadcast && root_ok ? COPIES(root_relay) : hipErrorInvalidValue;
+    case kKernelExchangePush: return p.coll == kCollAllToAll && p.n >= 2 ? COPIES(exchange_push) : hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
-#undef GATHER_CASE
-  return hipGetLastError();
+#undef COPIES
+#undef FOLDS
 }
 
-template <typename T>
-static hipError_t root_fold_for_t(int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-#define ROOT_FOLD_CASE(OPC)                                                                     \
-  case OPC:                                                                                      \
-    if (vec) hipLaunchKernelGGL((root_fold<T, OPC, true>), dim3(C), dim3(nt), 0, st, p);        \
-    else hipLaunchKernelGGL((root_fold<T, OPC, false>), dim3(C), dim3(nt), 0, st, p);           \
-    break;
-  switch (op) {
-    ROOT_FOLD_CASE(kSum) ROOT_FOLD_CASE(kProd) ROOT_FOLD_CASE(kMax) ROOT_FOLD_CASE(kMin)
-    default: return hipErrorInvalidValue;
+// One grid launch; which (G, V) exist: the rule's pairs (schedule.h read_grid_vectors: V = 1 up to
+// 4 ranks, 2 past them) for every type and op, every pair for fp32 Sum (MINI_NCCL_GRID_VECTORS)
+template <typename T, int OPC, int G, int V>
+static hipError_t read_grid_launch(const CollParams& p, hipStream_t st) {
+  constexpr bool tuned = std::is_same<T, float>::value && OPC == kSum;
+  if constexpr (tuned || (V == 1 && G <= 4) || (V == 2 && G >= 4)) {
+    // V 16-byte vectors per lane per workgroup: V KiB of the chunk each
+    const uint64_t per_block = 1024ull * (uint64_t)V;
+    const unsigned blocks = (unsigned)((p.chunk_bytes + per_block - 1) / per_block);
+    hipLaunchKernelGGL((read_grid_kernel<T, OPC, G, V>), dim3(blocks), dim3(64), 0, st, p);
+    return hipGetLastError();
+  } else {
+    return hipErrorInvalidValue;
   }
-#undef ROOT_FOLD_CASE
-  return hipGetLastError();
 }
 
-hipError_t launch_root_fold(int dtype, int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-  if (p.coll != kCollReduce || p.root < 0 || p.root >= p.n) return hipErrorInvalidValue;
-#define M(T) return root_fold_for_t<T>(op, vec, C, nt, p, st)
-  MNCCL_DISPATCH_T(dtype, M)
-#undef M
-}
-
-hipError_t launch_root_relay(int dtype, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-  if (p.coll != kCollBroadcast || p.root < 0 || p.root >= p.n) return hipErrorInvalidValue;
-#define RELAY_CASE(ESZ)                                                                          \
-  case ESZ:                                                                                      \
-    if (vec) hipLaunchKernelGGL((root_relay<ESZ, true>), dim3(C), dim3(nt), 0, st, p);          \
-    else hipLaunchKernelGGL((root_relay<ESZ, false>), dim3(C), dim3(nt), 0, st, p);             \
-    break;
-  switch (dtype_size(dtype)) {
-    RELAY_CASE(2) RELAY_CASE(4) RELAY_CASE(8)
-    default: return hipErrorInvalidValue;
-  }
-#undef RELAY_CASE
-  return hipGetLastError();
-}
-
-hipError_t launch_exchange_push(int dtype, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-  if (p.coll != kCollAllToAll || p.n < 2) return hipErrorInvalidValue;
-#define EXCHANGE_CASE(ESZ)                                                                       \
-  case ESZ:                                                                                      \
-    if (vec) hipLaunchKernelGGL((exchange_push<ESZ, true>), dim3(C), dim3(nt), 0, st, p);       \
-    else hipLaunchKernelGGL((exchange_push<ESZ, false>), dim3(C), dim3(nt), 0, st, p);          \
-    break;
-  switch (dtype_size(dtype)) {
-    EXCHANGE_CASE(2) EXCHANGE_CASE(4) EXCHANGE_CASE(8)
-    default: return hipErrorInvalidValue;
-  }
-#undef EXCHANGE_CASE
-  return hipGetLastError();
-}
-
-template <typename T>
-static hipError_t oneshot_for_t(int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-#define ONESHOT_CASE(OPC)                                                                           \
-  case OPC:                                                                                         \
-    if (vec) hipLaunchKernelGGL((oneshot_kernel<T, OPC, true>), dim3(C), dim3(nt), 0, st, p);      \
-    else hipLaunchKernelGGL((oneshot_kernel<T, OPC, false>), dim3(C), dim3(nt), 0, st, p);         \
-    break;
-  switch (op) {
-    ONESHOT_CASE(kSum) ONESHOT_CASE(kProd) ONESHOT_CASE(kMax) ONESHOT_CASE(kMin)
-    default: return hipErrorInvalidValue;
-  }
-#undef ONESHOT_CASE
-  return hipGetLastError();
-}
-
-template <typename T>
-static hipError_t read_grid_for_t(int op, const CollParams& p, hipStream_t st, int vectors) {
-  // V 16-byte vectors per lane per workgroup: V KiB of the chunk each (schedule.h read_grid_vectors)
+template <typename T, int OPC>
+static hipError_t read_grid_for(const CollParams& p, hipStream_t st, int vectors) {
   const int n = p.n;
   // MINI_NCCL_GRID_VECTORS: 1 / 2 / 4 vectors per lane for fp32 Sum (the bench's workload: the
   // node's sweep weighs them over xGMI); every other call follows the rule
-  const bool tuned = vectors != 0 && std::is_same<T, float>::value && op == kSum;
+  const bool tuned = vectors != 0 && std::is_same<T, float>::value && OPC == kSum;
   const int V = tuned ? vectors : read_grid_vectors(n);
-  // the rule's instantiations below hard-code V per rank count; a rule they do not match is
+  // the rule's instantiations hard-code V per rank count; a rule they do not match is
   // refused rather than launched with a grid sized for another V
   if (!tuned && V != (n <= 4 ? 1 : 2)) return hipErrorInvalidValue;
-  const uint64_t per_block = 1024ull * (uint64_t)V * kGridWaves;
-  const unsigned blocks = (unsigned)((p.chunk_bytes + per_block - 1) / per_block);
-#define GRID_G(OPC, G, VV) \
-  hipLaunchKernelGGL((read_grid_kernel<T, OPC, G, VV>), dim3(blocks), dim3(64 * kGridWaves), 0, st, p)
-  if constexpr (std::is_same<T, float>::value) {
-    if (tuned) {
-#define GRID_V(VV)                                    if (n == 2) GRID_G(kSum, 1, VV);                    else if (n == 3) GRID_G(kSum, 2, VV);               else if (n <= 5) GRID_G(kSum, 4, VV);               else GRID_G(kSum, 7, VV);
-      if (V == 1) { GRID_V(1) }
-      else if (V == 2) { GRID_V(2) }
-      else { GRID_V(4) }
-#undef GRID_V
-      return hipGetLastError();
-    }
-  }
-#define GRID_CASE(OPC)                    \
-  case OPC:                               \
-    if (n == 2) GRID_G(OPC, 1, 1);        \
-    else if (n == 3) GRID_G(OPC, 2, 1);   \
-    else if (n == 4) GRID_G(OPC, 4, 1);   \
-    else if (n == 5) GRID_G(OPC, 4, 2);   \
-    else GRID_G(OPC, 7, 2);               \
-    break;
-  switch (op) {
-    GRID_CASE(kSum) GRID_CASE(kProd) GRID_CASE(kMax) GRID_CASE(kMin)
-    default: return hipErrorInvalidValue;
-  }
-#undef GRID_CASE
-#undef GRID_G
-  return hipGetLastError();
+  // G peer slots by rank count, as read_fold_all's
+  auto with_v = [&](auto v) {
+    constexpr int VV = decltype(v)::value;
+    return n == 2   ? read_grid_launch<T, OPC, 1, VV>(p, st)
+           : n == 3 ? read_grid_launch<T, OPC, 2, VV>(p, st)
+           : n <= 5 ? read_grid_launch<T, OPC, 4, VV>(p, st)
+                    : read_grid_launch<T, OPC, 7, VV>(p, st);
+  };
+  return V == 1 ? with_v(IntTag<1>{}) : V == 2 ? with_v(IntTag<2>{}) : with_v(IntTag<4>{});
 }
 
 hipError_t launch_read_grid(int dtype, int op, const CollParams& p, hipStream_t st, int vectors) {
@@ -1883,26 +1703,22 @@ hipError_t launch_read_grid(int dtype, int op, const CollParams& p, hipStream_t 
   hipLaunchKernelGGL(read_start_kernel, dim3(1), dim3(64), 0, st, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-#define M(T) e = read_grid_for_t<T>(op, p, st, vectors)
-  MNCCL_DISPATCH_T(dtype, M)
-#undef M
+  e = for_dtype(dtype, [&](auto t) {
+    return for_op(op, [&](auto o) { return read_grid_for<typename decltype(t)::type, decltype(o)::value>(p, st, vectors); });
+  });
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(read_done_kernel, dim3(1), dim3(64), 0, st, p);
   return hipGetLastError();
 }
 
-hipError_t launch_oneshot(int dtype, int op, bool vec, int C, int nt, const CollParams& p, hipStream_t st) {
-#define M(T) return oneshot_for_t<T>(op, vec, C, nt, p, st)
-  MNCCL_DISPATCH_T(dtype, M)
-#undef M
-}
-
 hipError_t launch_local_reduce(int dtype, int op, void* out, const void* local, const void* incoming, uint64_t count,
                                hipStream_t st) {
   if (count == 0) return hipSuccess;
-#define M(T) return local_for_t<T>(op, out, local, incoming, count, st)
-  MNCCL_DISPATCH_T(dtype, M)
-#undef M
+  return for_dtype(dtype, [&](auto t) {
+    return for_op(op, [&](auto o) {
+      return local_for<typename decltype(t)::type, decltype(o)::value>(out, local, incoming, count, st);
+    });
+  });
 }
 
 bool dtype_supported(int dtype) { return dtype_size(dtype) != 0; }

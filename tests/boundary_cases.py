@@ -1,6 +1,6 @@
 """The batch-boundary cases of tests/test_boundaries_gpu.py, as plain data (no HIP, no library).
 
-The read schedule's double-buffered loops (kernels.hip read_fold_all, gather_push_vec, relay_vec,
+The read schedule's double-buffered loops (kernels.hip read_fold_all, copy_push_vec,
 exchange_push_vec) move a slice of nvec 16-byte vectors in batches of S = 64 * V vectors, load the
 next batch unconditionally and leave after either register set; read_fold past 8 ranks runs full
 batches of 1024 and then read_fold_wide in steps of 128; the ring's move_vec full batches of 512
@@ -48,7 +48,7 @@ ROT_SLICE = 8208
 # the suite's small geometry: 1 KiB slices, 4 pipelines (2 slots: the default)
 SMALL = {"MINI_NCCL_SLICE_SIZE": "1024", "MINI_NCCL_CHANNELS": "4"}
 
-PUSH_BATCH = 512  # gather_push_vec / relay_vec / exchange_push_vec: 64 lanes x 8 vectors
+PUSH_BATCH = 512  # copy_push_vec / exchange_push_vec: 64 lanes x 8 vectors
 
 
 def fold_batch(n, esz):

@@ -7,7 +7,7 @@ bytes past recv and last_algo checked per call.
 The cases are tests/boundary_cases.py's (one communicator per group, all of its cases on it);
 tests/test_boundary_cases.py proves on the CPU that they put the slices on the batch boundaries:
 S - 1, S, S + 1 with a sub-vector tail, 2S, 2S + 1 and 3S + 1 vectors for every S = 64 * V of
-read_fold_all, gather_push_vec, relay_vec and exchange_push_vec, 1023 ... 1024 + 129 for the fold past
+read_fold_all, copy_push_vec and exchange_push_vec, 1023 ... 1024 + 129 for the fold past
 8 ranks, 511 ... 1025 for the ring's move_vec.
 
 The all-reduce's grid form (read_start / read_grid / read_done) runs at MINI_NCCL_GRID_MIN=65536, so a

@@ -21,7 +21,7 @@ READ_DEPTH = 16            # schedule.h kReadDepth
 # 8 - 2h at 3, 4 - h up to 5, 3 - h up to 8, h = 1 for the 2-byte types); past 8 ranks full batches of
 # 64 * kReadFoldU = 1024, then read_fold_wide's steps of 64 * kWideV = 128.
 FOLD_S = {(2, 4): 768, (2, 2): 512, (3, 4): 512, (3, 2): 384, (5, 4): 256, (5, 2): 192, (8, 4): 192, (8, 2): 128}
-# gather_push_vec / relay_vec / exchange_push_vec: 64 * kGatherV = 64 * kExchangeV = 512
+# copy_push_vec (gather_push, root_relay) / exchange_push_vec: 64 * kGatherV = 64 * kExchangeV = 512
 PUSH_S = 512
 # move_vec: full batches of 64 * kU = 512, then single vectors
 MOVE_CLASSES = {511, 512, 513, 1024, 1025}
