@@ -34,6 +34,9 @@
  * and RCCL's dense exchange:
  *
  *   ncclAllToAll         block q of rank r's send becomes block r of rank q's recv, byte for byte.
+ *   ncclAllToAllv        the same exchange with a count and a displacement per peer on both sides
+ *                        (expert-parallel dispatch / combine: every rank sends every peer a different
+ *                        number of tokens, possibly none).
  */
 #ifndef MINI_NCCL_EXT_H_
 #define MINI_NCCL_EXT_H_
@@ -63,7 +66,8 @@ extern "C" {
    schedule choice in their signature and skip the host rendezvous only when no two ranks share a
    GPU (MINI_NCCL_WINDOW_RENDEZVOUS); still 600: ncclReduceScatter and ncclAllGather were added
    without a change to anything above -- a caller detects them by symbol; still 600: ncclBroadcast
-   and ncclReduce were added the same way; still 600: ncclAllToAll was added the same way */
+   and ncclReduce were added the same way; still 600: ncclAllToAll was added the same way; still 600:
+   ncclAllToAllv was added the same way (detected by symbol) */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -260,6 +264,48 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
  * or registered-window form. */
 ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclComm_t comm,
                           hipStream_t stream);
+
+/* The variable all-to-all, RCCL's name and signature.  Counts and displacements are in elements; the
+ * four arrays are host arrays of nranks entries, read before the call returns (a captured call bakes
+ * them into the graph).  Elements [sdispls[q], sdispls[q] + sendcounts[q]) of rank r's send become
+ * elements [rdispls[r], rdispls[r] + recvcounts[r]) of rank q's recv, byte for byte; a rank's own
+ * block goes from its send to its recv; bytes of recv outside every block are never written.
+ * Datatypes as ncclAllToAll (no arithmetic: by element size).
+ *
+ * Checks, in this order (no exception crosses the boundary):
+ *  1. a NULL comm or a NULL array: ncclInvalidArgument;
+ *  2. an unsupported datatype: ncclInternalError, before the communicator is read;
+ *  3. with the communicator, each ncclInvalidArgument with nothing launched or negotiated and the
+ *     communicator still usable: a NULL sendbuff unless every sendcount is 0, a NULL recvbuff unless
+ *     every recvcount is 0 (an idle rank may pass the NULL data pointer of an empty tensor for both);
+ *     a displ + count or a byte size that overflows size_t; two non-empty recv blocks that overlap;
+ *     a non-empty recv block that overlaps a non-empty send block (there is no in-place form).  Send
+ *     blocks may overlap each other: they are only read;
+ *  4. after the per-call rendezvous -- every rank sees every rank's counts -- sendcounts_r[q] !=
+ *     recvcounts_q[r] for any pair: ncclInvalidUsage on every rank alike, nothing launched, the
+ *     communicator still usable; the same when the ranks disagree on the collective or the datatype;
+ *  5. nranks == 1: one device copy of block 0 (a count mismatch is still ncclInvalidUsage);
+ *  6. every count on every rank 0: ncclSuccess, nothing launched.
+ * A rank takes part in the rendezvous and the protocol even when all its own counts are 0: its peers
+ * still exchange among themselves.  Blocking mode, stream ordering, sticky errors and the watchdog
+ * as ncclAllToAll.
+ *
+ * Schedules.  Where every rank's buffers are device memory the peers can map: the read schedule, a
+ * persistent kernel in ncclAllToAll's protocol whose geometry follows the LARGEST block of the whole
+ * matrix; every block crosses one link once and no padding moves; a destination whose addresses are
+ * dword-aligned on both sides goes in 16-byte vectors, any other element by element
+ * (mncclCommInfo_t.last_algo: mncclAlgoRead).  Otherwise -- a forced ring, a topology that refuses
+ * read, host buffers (pinned or pageable) -- the ring's ncclAllToAll on blocks PADDED to the largest
+ * one, M rounded up to 16 bytes: the blocks are packed into a device stage, exchanged and unpacked
+ * (last_algo: mncclAlgoRing).  That fallback costs 2 * nranks * Mpad bytes of device memory per
+ * communicator and sends the padding over the links: a skewed matrix pays for its largest block
+ * nranks - 1 times per rank.  The stage may have to be allocated, so a call captured into a HIP graph
+ * cannot take the fallback: if it would and any rank's stream is capturing, every rank returns
+ * ncclInvalidUsage with nothing launched.  A captured call on the read schedule replays correctly.
+ * No one-shot, grid or registered-window form. */
+ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                           const size_t recvcounts[], const size_t rdispls[], ncclDataType_t datatype, ncclComm_t comm,
+                           hipStream_t stream);
 
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream);

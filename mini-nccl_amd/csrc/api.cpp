@@ -222,6 +222,29 @@ ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, nc
   }
 }
 
+// The variable all-to-all (mini_nccl_ext.h): the communicator and the four arrays, then the
+// datatype; the buffers may be NULL on a rank whose counts are all zero, so they are checked with
+// the counts where the communicator's size is known (Comm::all_to_all_v, varblock.h).
+ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                           const size_t recvcounts[], const size_t rdispls[], ncclDataType_t datatype, ncclComm_t comm,
+                           hipStream_t stream) {
+  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
+  RoctxRange range("mini_ncclAllToAllv");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] AllToAllv Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->all_to_all_v(sendbuff, sendcounts, sdispls, recvbuff, recvcounts, rdispls,
+                                                       (int)datatype, stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] AllToAllv Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream) {
   if (!out || !local || !incoming) return ncclInvalidArgument;

@@ -438,6 +438,8 @@ void Comm::release() {
   if (stage_) hipFree(stage_);
   stage_ = nullptr;
   stage_bytes_ = 0;
+  if (var_stub_) hipFree(var_stub_);
+  var_stub_ = nullptr;
   if (order_ev_) hipEventDestroy(order_ev_);
   order_ev_ = nullptr;
   have_last_ = false;
@@ -597,6 +599,28 @@ static int persistent_kernel(int algo, int coll) {
 void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, int dtype, int op, hipStream_t stream,
                   uint32_t seq, bool vec, const char* const* psend, const char* const* precv,
                   size_t tail_bytes, uint64_t sig, int coll, int root, size_t total_bytes) {
+  int A = 0;
+  const CollParams p = make_params(algo, send, recv, chunk_bytes, seq, psend, precv, tail_bytes, sig, coll, root,
+                                   total_bytes, &A);
+  const int n = nranks_;
+  const int nt = cfg_.threads, wg = A / geo_.waves;
+  // mncclAlgoReadGrid: the push form's large calls as start / grid fold / done (the same on every
+  // rank: the schedule, the push form, vec and the size are rank-uniform)
+  // (and auto's: schedule.h read_grid_form)
+  // (the all-reduce's alone: its halves have the persistent form only)
+  const bool grid = algo == 2 && coll == kCollAllReduce && read_grid_form(algo_ == 4, auto_, vec, p.chunk_bytes, n,
+                                                                          cfg_.grid_min);
+  hip_check(grid ? launch_read_grid(dtype, op, p, stream, cfg_.grid_vectors)
+                 : launch_persistent(persistent_kernel(algo, coll), dtype, op, vec, wg, nt, p, stream),
+            "kernel launch");
+  last_algo_ = algo;
+  if (grid) ++read_grid_calls_;
+}
+
+// The kernel argument of one call and *pipes, the pipelines it launches (a multiple of geo_.waves)
+CollParams Comm::make_params(int algo, const void* send, void* recv, size_t chunk_bytes, uint32_t seq,
+                             const char* const* psend, const char* const* precv, size_t tail_bytes, uint64_t sig,
+                             int coll, int root, size_t total_bytes, int* pipes) {
   const int n = nranks_;
   CollParams p;
   memset(&p, 0, sizeof p);
@@ -648,18 +672,8 @@ void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, in
   p.claim = claim_;
   p.go = go_;
   p.sig = algo == 2 ? sig : 0;
-  const int nt = cfg_.threads, wg = A / geo_.waves;
-  // mncclAlgoReadGrid: the push form's large calls as start / grid fold / done (the same on every
-  // rank: the schedule, the push form, vec and the size are rank-uniform)
-  // (and auto's: schedule.h read_grid_form)
-  // (the all-reduce's alone: its halves have the persistent form only)
-  const bool grid = algo == 2 && coll == kCollAllReduce && read_grid_form(algo_ == 4, auto_, vec, chunk_bytes, n,
-                                                                          cfg_.grid_min);
-  hip_check(grid ? launch_read_grid(dtype, op, p, stream, cfg_.grid_vectors)
-                 : launch_persistent(persistent_kernel(algo, coll), dtype, op, vec, wg, nt, p, stream),
-            "kernel launch");
-  last_algo_ = algo;
-  if (grid) ++read_grid_calls_;
+  *pipes = A;
+  return p;
 }
 
 // The call path of ncclAllReduce (coll 0: `count` elements in send and in recv) and of its halves
@@ -735,29 +749,9 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       return ncclInvalidArgument;
     }
   }
-  int cur_dev = -1;
-  hip_check(hipGetDevice(&cur_dev), "hipGetDevice");
-  if (cur_dev != device_) hip_check(hipSetDevice(device_), "hipSetDevice");
-
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cap) != hipSuccess) {
-    (void)hipGetLastError();
-    cap = hipStreamCaptureStatusNone;
-  }
-  if (cap == hipStreamCaptureStatusActive && !warned_capture_) {
-    // the reference warns here too (api.cpp:153-166); this build needs no host polling,
-    // so a captured all-reduce replays correctly (sequence state lives on the device)
-    if (cfg_.debug) fprintf(stderr, "[Mini-NCCL] HIP graph capture detected: host-side wait skipped\n");
-    warned_capture_ = true;
-  }
-
-  // One communicator, one sequence of calls: the persistent kernels read and advance the
-  // per-pipeline FIFO counters, and the staging buffer is shared, so a call on another stream
-  // waits for the previous call (NCCL's rule: calls on a communicator are ordered).  Graph
-  // capture keeps its own order (the captured stream) and is left alone.
-  const bool capturing = cap != hipStreamCaptureStatusNone;
-  if (!capturing && have_last_ && stream != last_stream_)
-    hip_check(hipStreamWaitEvent(stream, order_ev_, 0), "order after previous call");
+  const CallScope scope = begin_call(stream);
+  const int cur_dev = scope.cur_dev;
+  const hipStreamCaptureStatus cap = scope.cap;
 
   const int n = nranks_;
   uint32_t seq = 0;  // this call's kernel (0: the call launches none)
@@ -830,14 +824,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       if (seq == 0) seq = ++call_seq_;
       launch(2, send, recv, chunk_bytes, dtype, op, stream, seq, vec_w, psend, precv, tail, sig);
       ++window_calls_;
-      if (!capturing) {
-        hip_check(hipEventRecord(order_ev_, stream), "order event");
-        last_stream_ = stream;
-        have_last_ = true;
-      }
-      if (cur_dev != device_) hipSetDevice(cur_dev);
-      if (cfg_.blocking && !capturing) return wait_for(stream, seq);
-      return ncclSuccess;
+      return end_call(scope, stream, seq);
     }
     if (read_sched) pbuf_.reap(send, recv);
     const Reach rs = read_sched && pbuf_.known(send) ? (local_s = true, Reach::kDevice) : reach(send, &ksend, &local_s);
@@ -946,13 +933,42 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       hip_check(hipMemcpyAsync(recv, krecv, coll == kCollReduceScatter ? chunk_bytes : bytes, hipMemcpyDefault, stream),
                 "stage out");
   }
-  if (!capturing) {
+  return end_call(scope, stream, seq);
+}
+
+Comm::CallScope Comm::begin_call(hipStream_t stream) {
+  CallScope sc;
+  hip_check(hipGetDevice(&sc.cur_dev), "hipGetDevice");
+  if (sc.cur_dev != device_) hip_check(hipSetDevice(device_), "hipSetDevice");
+
+  if (hipStreamIsCapturing(stream, &sc.cap) != hipSuccess) {
+    (void)hipGetLastError();
+    sc.cap = hipStreamCaptureStatusNone;
+  }
+  if (sc.cap == hipStreamCaptureStatusActive && !warned_capture_) {
+    // the reference warns here too (api.cpp:153-166); this build needs no host polling,
+    // so a captured all-reduce replays correctly (sequence state lives on the device)
+    if (cfg_.debug) fprintf(stderr, "[Mini-NCCL] HIP graph capture detected: host-side wait skipped\n");
+    warned_capture_ = true;
+  }
+
+  // One communicator, one sequence of calls: the persistent kernels read and advance the
+  // per-pipeline FIFO counters, and the staging buffer is shared, so a call on another stream
+  // waits for the previous call (NCCL's rule: calls on a communicator are ordered).  Graph
+  // capture keeps its own order (the captured stream) and is left alone.
+  if (!sc.capturing() && have_last_ && stream != last_stream_)
+    hip_check(hipStreamWaitEvent(stream, order_ev_, 0), "order after previous call");
+  return sc;
+}
+
+ncclResult_t Comm::end_call(const CallScope& sc, hipStream_t stream, uint32_t seq) {
+  if (!sc.capturing()) {
     hip_check(hipEventRecord(order_ev_, stream), "order event");
     last_stream_ = stream;
     have_last_ = true;
   }
-  if (cur_dev != device_) hipSetDevice(cur_dev);
-  if (cfg_.blocking && cap == hipStreamCaptureStatusNone) return wait_for(stream, seq);
+  if (sc.cur_dev != device_) hipSetDevice(sc.cur_dev);
+  if (cfg_.blocking && !sc.capturing()) return wait_for(stream, seq);
   return ncclSuccess;
 }
 
@@ -967,6 +983,177 @@ ncclResult_t Comm::rendezvous_failed(const std::exception& e, bool peer_gave_up,
   }
   if (cur_dev != device_) hipSetDevice(cur_dev);
   return sticky_;
+}
+
+bool Comm::gather_rows(const VarRow& mine, int dtype, VarRow* rows) {
+  struct Rec {
+    VarRow row;
+    int32_t dtype, coll;
+  } me;
+  memset(&me, 0, sizeof me);
+  me.row = mine;
+  me.dtype = dtype;
+  me.coll = kCollAllToAllV;
+  std::vector<Rec> all((size_t)nranks_);
+  boot_.allgather(&me, all.data(), sizeof me);
+  bool same = true;
+  for (int q = 0; q < nranks_; ++q) {
+    rows[q] = all[(size_t)q].row;
+    same = same && all[(size_t)q].dtype == dtype && all[(size_t)q].coll == kCollAllToAllV;
+  }
+  return same;
+}
+
+// ncclAllToAllv.  The caller's local errors first (varblock.h: nothing launched, nothing
+// negotiated); then every rank's counts reach every rank -- through the read schedule's rendezvous
+// wherever the board exists, whatever the schedule (a rank the read schedule is closed to takes part
+// as ineligible), else over the bootstrap -- so every rank checks the same matrix and derives the
+// same geometry from its largest block M.  On the read schedule: kernels.hip varblock_push.  Else
+// the ring's all-to-all on blocks padded to Mpad = M rounded up to 16: the non-empty off-diagonal
+// blocks are packed into the stage at q * Mpad by stream-ordered copies straight from the user's
+// send (device, pinned or pageable alike), exchanged into a second stage region, and unpacked
+// straight into the user's recv; 2 n Mpad bytes of stage, and the padding crosses the links.  The
+// stage may have to be allocated, which a graph capture cannot do: if the decision is the fallback
+// and ANY rank is capturing (its flag rides in its row), every rank returns ncclInvalidUsage.
+// A rank whose counts are all zero still takes part in the rendezvous and the protocol: its peers
+// exchange among themselves and every pair's counters advance alike.
+ncclResult_t Comm::all_to_all_v(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
+                                const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream) {
+  if (sticky_ != ncclSuccess) return sticky_;
+  if (check_status() != ncclSuccess) return sticky_;
+  const int n = nranks_, esz = dtype_size(dtype);
+  const int local = varblock_check_local(n, esz, send, sendcounts, sdispls, recv, recvcounts, rdispls);
+  if (local != kVarOk) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: ncclAllToAllv: %s\n", rank_,
+            local == kVarNullBuffer    ? "a NULL buffer with a non-zero count"
+            : local == kVarOverflow    ? "a displacement plus count, or a byte size, overflows size_t"
+            : local == kVarRecvOverlap ? "two recv blocks overlap"
+                                       : "a recv block overlaps a send block (there is no in-place form)");
+    return ncclInvalidArgument;
+  }
+  if (n == 1) {
+    if (sendcounts[0] != recvcounts[0]) {
+      fprintf(stderr, "[Mini-NCCL] rank 0: ncclAllToAllv: sendcounts[0] != recvcounts[0]\n");
+      return ncclInvalidUsage;
+    }
+    if (sendcounts[0] == 0) return ncclSuccess;
+    const CallScope scope = begin_call(stream);
+    hip_check(hipMemcpyAsync((char*)recv + rdispls[0] * (size_t)esz, (const char*)send + sdispls[0] * (size_t)esz,
+                             sendcounts[0] * (size_t)esz, hipMemcpyDefault, stream), "copy");
+    return end_call(scope, stream, 0);
+  }
+  const CallScope scope = begin_call(stream);
+  auto leave = [&](ncclResult_t rc) {
+    if (scope.cur_dev != device_) hipSetDevice(scope.cur_dev);
+    return rc;
+  };
+  VarRow mine, rows[kMaxRanks];
+  memset(&mine, 0, sizeof mine);
+  for (int q = 0; q < n; ++q) {
+    mine.sendcounts[q] = sendcounts[q];
+    mine.recvcounts[q] = recvcounts[q];
+    mine.rdispls[q] = rdispls[q];
+  }
+  mine.flags = scope.capturing() ? (uint32_t)kVarCapturing : 0u;
+
+  PeerBuffers::Decision d = PeerBuffers::kFallback;
+  const char* psend[kMaxRanks] = {};
+  const char* precv[kMaxRanks] = {};
+  // a buffer this rank does not use (all its counts zero: it may be NULL) is stood in for by the
+  // other one, as the rooted collectives do; a rank with neither by the communicator's stub
+  const void* rsend = send ? send : recv;
+  void* rrecv = recv ? recv : const_cast<void*>(send);
+  if (pbuf_.available()) {
+    const bool read_ok = ((algo_ == 2 || algo_ == 4) && (!auto_ || topo_read_)) || (algo_ == 3 && topo_read_);
+    if (!rsend && read_ok) {
+      if (!var_stub_ && hipMalloc((void**)&var_stub_, 256) != hipSuccess) {
+        (void)hipGetLastError();
+        var_stub_ = nullptr;
+      }
+      rsend = rrecv = var_stub_;
+    }
+    bool eligible = false;
+    if (read_ok && rsend) {
+      pbuf_.reap(rsend, rrecv);
+      bool local_s = false, local_r = false;
+      const void* ks = rsend;
+      const void* kr = rrecv;
+      const bool dev_s = pbuf_.known(rsend) ? (local_s = true) : reach(rsend, &ks, &local_s) == Reach::kDevice;
+      const bool dev_r = pbuf_.known(rrecv) ? (local_r = true) : reach(rrecv, &kr, &local_r) == Reach::kDevice;
+      eligible = dev_s && dev_r && local_s && local_r;
+    }
+    bool vec_all = false;
+    try {
+      d = pbuf_.negotiate(rsend, rrecv, eligible, 0, dtype, 0, cfg_.timeout_ms / 1000.0 + 2.0,
+                          [this] { wait_previous_call(); }, psend, precv, &vec_all,
+                          (auto_ ? 0xff : algo_) | kCollAllToAllV << 8, &mine, rows);
+    } catch (const PeerGaveUp& e) {
+      return rendezvous_failed(e, true, scope.cur_dev);
+    } catch (const std::exception& e) {
+      return rendezvous_failed(e, false, scope.cur_dev);
+    }
+    if (d == PeerBuffers::kWindowPeer) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: a peer ran this call on registered windows where this rank called "
+              "ncclAllToAllv; communicator is no longer usable\n", rank_);
+      sticky_ = ncclInvalidUsage;
+      abort_peers();
+      return leave(sticky_);
+    }
+    if (d == PeerBuffers::kMismatch) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: ncclAllToAllv: some rank's sendcounts[q] differs from rank q's recvcounts "
+              "for it, or the ranks called different collectives / datatypes / schedules (mncclCommSetAlgo)\n", rank_);
+      return leave(ncclInvalidUsage);
+    }
+  } else if (!gather_rows(mine, dtype, rows) || varblock_matrix_mismatch(n, rows) != 0) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: ncclAllToAllv: some rank's sendcounts[q] differs from rank q's recvcounts "
+            "for it, or the ranks passed different datatypes\n", rank_);
+    return leave(ncclInvalidUsage);
+  }
+  const size_t M = (size_t)varblock_max_count(n, rows) * (size_t)esz;  // the largest block: the same everywhere
+  if (M == 0) return leave(ncclSuccess);  // nobody sends anything: nothing launched on any rank
+  if (d != PeerBuffers::kRead && varblock_any_capturing(n, rows)) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: ncclAllToAllv: this call runs the padded ring, whose stage cannot be "
+            "allocated inside a HIP graph capture (some rank's stream is capturing)\n", rank_);
+    return leave(ncclInvalidUsage);
+  }
+  uint32_t seq = ++call_seq_;
+  if (seq == 0) seq = ++call_seq_;
+  const char* s0 = static_cast<const char*>(send);
+  char* r0 = static_cast<char*>(recv);
+  if (d == PeerBuffers::kRead) {
+    VarBlockArgs v;
+    memset(&v, 0, sizeof v);
+    for (int q = 0; q < n; ++q) {
+      v.src_off[q] = (uint64_t)sdispls[q] * (uint64_t)esz;
+      v.dst_off[q] = rows[q].rdispls[rank_] * (uint64_t)esz;
+      v.bytes[q] = (uint64_t)sendcounts[q] * (uint64_t)esz;
+      const uint64_t dst = (uint64_t)(uintptr_t)(q == rank_ ? (const char*)rrecv : precv[q]) + v.dst_off[q];
+      const uint64_t src = (uint64_t)(uintptr_t)rsend + v.src_off[q];
+      if (v.bytes[q] && (src | dst) % 4 == 0) v.vec_mask |= 1u << q;
+    }
+    int A = 0;
+    const CollParams p = make_params(2, rsend, rrecv, M, seq, psend, precv, 0, 0, kCollAllToAllV, 0, 0, &A);
+    hip_check(launch_varblock(dtype, A / geo_.waves, cfg_.threads, p, v, stream), "kernel launch");
+    last_algo_ = 2;
+  } else {
+    const size_t Mpad = (M + 15) & ~(size_t)15;
+    ensure_stage(2 * (size_t)n * Mpad, stream);
+    char* in = stage_;
+    char* out = stage_ + (size_t)n * Mpad;
+    for (int q = 0; q < n; ++q)
+      if (q != rank_ && sendcounts[q])
+        hip_check(hipMemcpyAsync(in + (size_t)q * Mpad, s0 + sdispls[q] * (size_t)esz, sendcounts[q] * (size_t)esz,
+                                 hipMemcpyDefault, stream), "pack");
+    launch(0, in, out, Mpad, dtype, kSum, stream, seq, true, nullptr, nullptr, 0, 0, kCollAllToAll);
+    for (int q = 0; q < n; ++q)
+      if (q != rank_ && recvcounts[q])
+        hip_check(hipMemcpyAsync(r0 + rdispls[q] * (size_t)esz, out + (size_t)q * Mpad, recvcounts[q] * (size_t)esz,
+                                 hipMemcpyDefault, stream), "unpack");
+    if (sendcounts[rank_])
+      hip_check(hipMemcpyAsync(r0 + rdispls[rank_] * (size_t)esz, s0 + sdispls[rank_] * (size_t)esz,
+                               sendcounts[rank_] * (size_t)esz, hipMemcpyDefault, stream), "own block");
+  }
+  return end_call(scope, stream, seq);
 }
 
 const Comm::Window* Comm::find_window(const void* p, size_t bytes) const {

@@ -66,6 +66,15 @@ class Comm {
     return collective(kCollAllToAll, send, recv, count, dtype, kSum, stream);
   }
 
+  // The variable all-to-all (RCCL's ncclAllToAllv; counts and displacements in elements, host arrays
+  // of n entries read before the call returns): elements [sdispls[q], +sendcounts[q]) of this rank's
+  // send become elements [rdispls[r], +recvcounts[r]) of rank q's recv.  A call path of its own
+  // (comm.cpp): the local checks (varblock.h), a rendezvous that carries every rank's counts to every
+  // rank whatever the schedule, then the read schedule (kernels.hip varblock_push) or, where the
+  // rendezvous decides against it, the ring's all-to-all on blocks padded to the largest one.
+  ncclResult_t all_to_all_v(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
+                            const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream);
+
   int rank() const { return rank_; }
   int nranks() const { return nranks_; }
   int device() const { return device_; }
@@ -130,6 +139,22 @@ class Comm {
               uint32_t seq, bool vec, const char* const* psend = nullptr, const char* const* precv = nullptr,
               size_t tail_bytes = 0, uint64_t sig = 0, int coll = kCollAllReduce, int root = 0,
               size_t total_bytes = 0);
+  CollParams make_params(int algo, const void* send, void* recv, size_t chunk_bytes, uint32_t seq,
+                         const char* const* psend, const char* const* precv, size_t tail_bytes, uint64_t sig, int coll,
+                         int root, size_t total_bytes, int* pipes);
+  // what every call does around its work (collective() and all_to_all_v()): this rank's device made
+  // current, the stream's capture state, the order after the communicator's previous call; then the
+  // order event, the caller's device restored and the blocking mode's wait
+  struct CallScope {
+    int cur_dev = -1;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    bool capturing() const { return cap != hipStreamCaptureStatusNone; }
+  };
+  CallScope begin_call(hipStream_t stream);
+  ncclResult_t end_call(const CallScope& sc, hipStream_t stream, uint32_t seq);
+  // every rank's ncclAllToAllv row where the board is unavailable: over the bootstrap, like
+  // mncclCommLinkProbe's records.  False: the ranks disagree on the collective or the datatype
+  bool gather_rows(const VarRow& mine, int dtype, VarRow* rows);
   // the one call path of the six collectives; count: the all-reduce's and the rooted ones', per
   // rank for the halves, per block for the all-to-all
   ncclResult_t collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
@@ -191,6 +216,8 @@ class Comm {
 
   char* stage_ = nullptr;         // device staging copy for pageable host buffers (grown on demand)
   size_t stage_bytes_ = 0;
+  char* var_stub_ = nullptr;      // ncclAllToAllv: stands in for a rank's NULL buffers in the rendezvous
+                                  // (an idle rank passes none); allocated on first need
 
   hipEvent_t order_ev_ = nullptr;     // recorded after every call: cross-stream ordering, and the
                                       // blocking call's completion (wait_for)

@@ -90,6 +90,20 @@ enum PersistentKernel : int {
 // rooted kernels and n < 2 for the all-to-all; the kernels that only copy ignore op.
 hipError_t launch_persistent(int kernel, int dtype, int op, bool vec, int channels, int threads,
                              const CollParams& p, hipStream_t stream);
+// ncclAllToAllv on the read schedule (kernels.hip varblock_push): the per-destination blocks of this
+// rank, a second by-value kernel argument (CollParams stays byte for byte what it was).  Indexed by
+// destination rank q; this rank's own block at [rank].
+struct VarBlockArgs {
+  uint64_t src_off[16];  // byte offset of the block for q in this rank's send (sdispls[q] * element size)
+  uint64_t dst_off[16];  // byte offset of that block in rank q's recv (rank q's rdispls[rank] * element size)
+  uint64_t bytes[16];    // the block's length in bytes (0: nothing goes to q)
+  uint32_t vec_mask;     // bit q: source and destination address are both dword-aligned (16-byte path)
+  uint32_t pad;
+};
+// p: the all-to-all's geometry for chunk_bytes = the largest block of the whole matrix (the same on
+// every rank), p.peer_recv every rank's recv.  By element size (2 / 4 / 8 from dtype): no arithmetic.
+hipError_t launch_varblock(int dtype, int channels, int threads, const CollParams& p, const VarBlockArgs& v,
+                           hipStream_t stream);
 // the read schedule's push form for large calls as three launches (start, grid fold, done):
 // schedule.h read_grid_fits(p.chunk_bytes, p.n, kReadGridFloor) (2 <= n <= 8, whole 16-byte vectors), p.go set
 // vectors: 0 = schedule.h read_grid_vectors; 1 / 2 / 4 (MINI_NCCL_GRID_VECTORS) for fp32 Sum only

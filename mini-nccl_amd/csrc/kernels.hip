@@ -24,6 +24,9 @@
 //  exchange_push  the all-to-all (ncclAllToAll) on the same protocol: every rank pushes block q of
 //                 its own send into rank q's recv, so every block crosses one link once.  Its
 //                 fallback is ring_kernel with a table of hops (schedule.h coll_op).
+//  varblock_push  the variable all-to-all (ncclAllToAllv) on the same protocol: exchange_push with a
+//                 length and two offsets per destination, the slices cut for the largest block of
+//                 the whole matrix.  Its fallback is the ring's all-to-all on padded blocks.
 //  read_start / read_grid / read_done   the read schedule's push form as three launches (the
 //                 runtime form mncclAlgoReadGrid, for large calls): a grid of one-batch workgroups
 //                 between a one-wave START and a one-wave DONE.
@@ -1228,6 +1231,114 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) exchange_push(C
   });
 }
 
+// ---------------------------------------------------------------- the variable all-to-all
+// ncclAllToAllv (varblock_push) on device buffers every rank can share, in read_half's protocol
+// message for message: the block this rank sends to rank q has its own length, its own offset in
+// this rank's send and its own offset in rank q's recv (VarBlockArgs, the kernel's second argument:
+// the host has every rank's row from the rendezvous).  The call's geometry is the all-to-all's for
+// the LARGEST block of the whole matrix -- p.chunk_bytes, the same on every rank, so every pair's
+// counters advance alike -- and slice s covers bytes [s * slice, s * slice + varblock_len) of every
+// block: shorter blocks run out earlier, empty ones never start.  Pushes, not pulls, for
+// exchange_push's reason; only rank r writes the block from r of any recv, and the blocks of a call
+// overlap neither each other nor a send block (Comm::all_to_all_v refuses it).
+//
+// 16-byte vectors, exchange_push_vec's structure: the (destination, batch) pairs of the slice form
+// one sequence -- the peers in direct_peer order from peer w mod n-1, this rank itself last, a
+// destination with no vector in this slice skipped -- and the next batch's loads leave before this
+// batch is stored, across destinations too.  Each destination has its own vector count, and its
+// descriptors cover exactly its whole vectors: lanes past them read 0 and store nothing.  A
+// destination takes this path when its source and destination addresses are both dword-aligned
+// (v.vec_mask, wave-uniform); its last len % 16 bytes, and every other destination, go element by
+// element as exchange_slice's scalar path does -- one odd bf16 displacement costs one destination
+// the vectors, not the call.
+template <int V>
+__device__ __forceinline__ void varblock_push_vec(const CollParams& p, const VarBlockArgs& v, uint64_t soff, int lane) {
+  constexpr uint32_t step = 64 * V;
+  const int n = p.n, r = p.rank, first = wave_id().w % (n - 1);
+  auto dest = [&](int k) { return k < n - 1 ? direct_peer(n, r, 1 + (first + k) % (n - 1)) : r; };
+  // whole vectors of destination k in this slice (0: not a vector destination, exhausted, or k past the end)
+  auto nvec_of = [&](int k) -> uint32_t {
+    if (k >= n) return 0u;
+    const int q = dest(k);
+    return (v.vec_mask >> q) & 1u ? (uint32_t)(varblock_len_at(v.bytes[q], p.slice_bytes, soff) >> 4) : 0u;
+  };
+  auto next_from = [&](int k) {
+    while (k < n && nvec_of(k) == 0) ++k;
+    return k;
+  };
+  auto src_of = [&](int k, uint32_t nv) { return make_rsrc(p.send + (k < n ? v.src_off[dest(k)] : 0) + soff, nv * 16); };
+  auto dst_of = [&](int k, uint32_t nv) {
+    const int q = dest(k < n ? k : n - 1);
+    return make_rsrc((q == r ? p.recv : const_cast<char*>(p.peer_recv[q])) + v.dst_off[q] + soff, nv * 16);
+  };
+  auto load = [&](v4u(&x)[V], rsrc_t s, uint32_t b) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) x[u] = ld_nt16(s, (b + (uint32_t)(u * 64 + lane)) * 16);
+  };
+  auto store = [&](v4u(&x)[V], rsrc_t d, uint32_t b) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) st_slot16(d, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+  };
+  int k = next_from(0);  // the batch about to be stored: destination k, vectors from b of its nvec
+  if (k >= n) return;
+  uint32_t b = 0, nvec = nvec_of(k);
+  rsrc_t src = src_of(k, nvec), dst = dst_of(k, nvec);
+  v4u xa[V], xb[V];
+  // loads the batch after (k, b) into nxt, stores cur, moves on; false after the last batch
+  auto turn = [&](v4u(&cur)[V], v4u(&nxt)[V]) {
+    int k2 = k;
+    uint32_t b2 = b + step, nvec2 = nvec;
+    if (b2 >= nvec) {
+      b2 = 0;
+      k2 = next_from(k + 1);
+      nvec2 = nvec_of(k2);
+      src = src_of(k2, nvec2);  // past the last destination: empty, the loads return 0
+    }
+    load(nxt, src, b2);
+    store(cur, dst, b);
+    if (k2 != k) dst = dst_of(k2, nvec2);
+    k = k2;
+    b = b2;
+    nvec = nvec2;
+    return k < n;
+  };
+  load(xa, src, 0);
+  while (turn(xa, xb) && turn(xb, xa)) {
+  }
+}
+
+constexpr int kVarBlockV = 8;
+
+// slice at byte `soff` of every block: the vector destinations' whole vectors first, then element by
+// element each vector destination's last len % 16 bytes and every byte of the others
+template <int ESZ>
+__device__ __forceinline__ void varblock_slice(const CollParams& p, const VarBlockArgs& v, uint64_t soff, int lane) {
+  const int n = p.n, r = p.rank;
+  if (v.vec_mask) varblock_push_vec<kVarBlockV>(p, v, soff, lane);
+  typedef Scal<ESZ> S;
+  for (int k = 1; k <= n; ++k) {
+    const int q = direct_peer(n, r, k);  // k == n: this rank itself
+    const uint32_t len = (uint32_t)varblock_len_at(v.bytes[q], p.slice_bytes, soff);
+    const uint32_t done = (v.vec_mask >> q) & 1u ? len & ~15u : 0u;
+    if (done == len) continue;
+    const rsrc_t src = make_rsrc(p.send + v.src_off[q] + soff, len);
+    const rsrc_t dst = make_rsrc((q == r ? p.recv : const_cast<char*>(p.peer_recv[q])) + v.dst_off[q] + soff, len);
+    const uint32_t ne = len / ESZ;
+    for (uint32_t i = done / ESZ + (uint32_t)lane; i < ne; i += 64) S::st(dst, i * (uint32_t)ESZ, S::ld(src, i * (uint32_t)ESZ));
+  }
+}
+
+// No arithmetic, so by element size only; the path is chosen per destination at run time.
+// read_half hands the slice's offset in chunk `rank` of the largest-block geometry; the slice's
+// offset within a block is what every block shares.
+template <int ESZ>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) varblock_push(CollParams p, VarBlockArgs v) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half(p, s_tx, s_rx, [&p, &v](u64 coff, uint32_t, int lane) {
+    varblock_slice<ESZ>(p, v, coff - (u64)p.rank * p.chunk_bytes, lane);
+  });
+}
+
 // ---------------------------------------------------------------- read schedule, grid form
 // mncclAlgoReadGrid / MINI_NCCL_ALGO=read_grid, and auto's large read calls since 5.1
 // (schedule.h read_grid_form): the push form of a large call (read_grid_fits) as three launches on
@@ -1655,6 +1766,14 @@ hipError_t launch_persistent(int kernel, int dtype, int op, bool vec, int C, int
   }
 #undef COPIES
 #undef FOLDS
+}
+
+hipError_t launch_varblock(int dtype, int C, int nt, const CollParams& p, const VarBlockArgs& v, hipStream_t st) {
+  if (p.coll != kCollAllToAllV || p.n < 2) return hipErrorInvalidValue;
+  return for_elem_size(dtype, [&](auto e) {
+    hipLaunchKernelGGL(varblock_push<decltype(e)::value>, dim3(C), dim3(nt), 0, st, p, v);
+    return hipGetLastError();
+  });
 }
 
 // One grid launch; which (G, V) exist: the rule's pairs (schedule.h read_grid_vectors: V = 1 up to

@@ -23,7 +23,8 @@ namespace mnccl {
 
 namespace {
 
-constexpr uint32_t kBoardMagic = 0x4d4e4253u;  // 'MNBS'
+constexpr uint32_t kBoardMagic = 0x4d4e4254u;  // 'MNBT' (the record carries an ncclAllToAllv row: a rank
+                                               // built with the earlier record must not share a board)
 constexpr int kBoardDepth = 16;                // records per rank in flight (calls ahead of the slowest peer)
 constexpr int kMaxFreed = 8;                   // freed allocations one record reports (the rest: next calls)
 constexpr size_t kMaxKnown = 4096;
@@ -64,6 +65,9 @@ struct alignas(64) CallRec {
   // outcome map_ok reports, stored after it (release)
   alignas(64) std::atomic<uint64_t> mapped;
   int32_t map_ok;
+  // ncclAllToAllv: this rank's counts, recv displacements and flags (negotiate's `row`); written
+  // only by calls that pass one, read only by calls that do
+  VarRow var;
 };
 
 struct alignas(64) Counter {
@@ -378,7 +382,8 @@ void PeerBuffers::publish_fast(uint64_t count, int dtype, int op, uint64_t sig, 
 PeerBuffers::Decision PeerBuffers::negotiate(const void* send, const void* recv, bool eligible, uint64_t count,
                                              int dtype, int op, double timeout_s,
                                              const std::function<void()>& sync_previous, const char** psend,
-                                             const char** precv, bool* vec_all, int form) {
+                                             const char** precv, bool* vec_all, int form, const VarRow* row,
+                                             VarRow* rows_out) {
   const uint64_t k = ++seq_;
   const double t0 = now_s();
   // spins until ready() -- bounded by the peer q giving up and by the rendezvous limit
@@ -395,7 +400,7 @@ PeerBuffers::Decision PeerBuffers::negotiate(const void* send, const void* recv,
   };
   try {
     return negotiate_body(k, send, recv, eligible, count, dtype, op, form, sync_previous, psend, precv, vec_all,
-                          wait_for);
+                          wait_for, row, rows_out);
   } catch (...) {
     // this rank gives up (a peer that never came or gave up itself): say so on the board, so
     // every peer waiting in a rendezvous with it fails at once instead of at its own limit (the
@@ -524,7 +529,8 @@ template <typename WaitFor>
 PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, const void* recv, bool eligible,
                                                   uint64_t count, int dtype, int op, int form,
                                                   const std::function<void()>& sync_previous, const char** psend,
-                                                  const char** precv, bool* vec_all, const WaitFor& wait_for) {
+                                                  const char** precv, bool* vec_all, const WaitFor& wait_for,
+                                                  const VarRow* row, VarRow* rows_out) {
   auto wait = [&](const std::atomic<uint64_t>& v, uint64_t want, int q, const char* what) {
     wait_for([&] { return v.load(std::memory_order_acquire) >= want; }, q, what);
   };
@@ -560,6 +566,7 @@ PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, 
     ++me.nfreed;
     freed_.pop_front();
   }
+  if (row) me.var = *row;
   me.seq.store(k, std::memory_order_release);
 
   struct Seen {
@@ -585,6 +592,8 @@ PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, 
     s.recv = c.recv;
     s.nfreed = c.nfreed < 0 ? 0 : c.nfreed > kMaxFreed ? kMaxFreed : c.nfreed;
     memcpy(s.freed, c.freed, sizeof s.freed);
+    // (a peer that passed no row called another collective: its `form` differs, kMismatch below)
+    if (row && rows_out) rows_out[q] = c.var;
   }
   board_->consumed[rank_].v.store(k, std::memory_order_release);  // my copies are taken
   // a peer launched this call on its registered windows without waiting for the records: it takes
@@ -623,8 +632,10 @@ PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, 
   for (const Seen& c : recs) {
     all = all && c.eligible;
     aligned = aligned && c.aligned;
-    mismatch = mismatch || c.count != count || c.dtype != dtype || c.op != op || c.form != form;
+    mismatch = mismatch || (!row && c.count != count) || c.dtype != dtype || c.op != op || c.form != form;
   }
+  // ncclAllToAllv: every pair's counts instead of the scalar count (only rows of this collective)
+  if (row && rows_out && !mismatch) mismatch = varblock_matrix_mismatch(nranks_, rows_out) != 0;
   const Decision d = mismatch ? kMismatch : all ? kRead : kFallback;
   *vec_all = aligned;
   if (d != kRead) return d;

@@ -30,6 +30,7 @@
 
 #include "bootstrap.h"
 #include "ipcreg.h"
+#include "varblock.h"
 
 namespace mnccl {
 
@@ -66,9 +67,14 @@ class PeerBuffers {
   // differ in it get kMismatch, as for count / dtype / op (a grid-form rank's DONE could otherwise
   // be met by a persistent peer's pipeline 0 while the other pipelines never start).  Throws
   // std::runtime_error when a peer does not arrive within timeout_s.
+  // `row` (ncclAllToAllv only): this rank's counts, recv displacements and flags, published with its
+  // record; `rows_out` then gets every rank's row (nranks entries, whatever the decision), and the
+  // scalar `count` comparison is replaced by the matrix check (varblock.h): kMismatch when
+  // sendcounts_r[q] != recvcounts_q[r] for some pair.  Calls that pass no row behave as before.
   Decision negotiate(const void* send, const void* recv, bool eligible, uint64_t count, int dtype, int op,
                      double timeout_s, const std::function<void()>& sync_previous, const char** psend,
-                     const char** precv, bool* vec_all, int form = 0);
+                     const char** precv, bool* vec_all, int form = 0, const VarRow* row = nullptr,
+                     VarRow* rows_out = nullptr);
 
   // A registered-window call (Comm::allreduce's fast path): this rank's record for the next call,
   // marked fast with the call's signature, published WITHOUT reading the peers' -- their kernels
@@ -114,7 +120,8 @@ class PeerBuffers {
   template <typename WaitFor>
   Decision negotiate_body(uint64_t k, const void* send, const void* recv, bool eligible, uint64_t count, int dtype,
                           int op, int form, const std::function<void()>& sync_previous, const char** psend,
-                          const char** precv, bool* vec_all, const WaitFor& wait_for);
+                          const char** precv, bool* vec_all, const WaitFor& wait_for, const VarRow* row,
+                          VarRow* rows_out);
   bool describe(const void* p, uint64_t* base, uint64_t* id, ipc::Shared* d);
   char* map_peer(int q, uint64_t base, uint64_t id, int fd, const ipc::Shared& d, std::string* why);
   void sock_addr(int q, void* addr, unsigned* len) const;

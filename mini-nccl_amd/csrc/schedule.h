@@ -134,8 +134,12 @@ MNCCL_HD RingOp ring_op(int n, int r, int k) {
 // the op right after the one that sent it on the rank before, as in the tables above.  Each op
 // touches only one of send and recv, so one `chunk` per op is enough.  The own block reaches the
 // own recv by a device copy before the launch, as the ring's all-gather gets its own chunk.
+//
+// The variable all-to-all (ncclAllToAllv, kCollAllToAllV) has no ring table of its own: off the read
+// schedule it runs the table above on blocks padded to the largest one (Comm::all_to_all_v).
 enum Coll : int {
-  kCollAllReduce = 0, kCollReduceScatter = 1, kCollAllGather = 2, kCollBroadcast = 3, kCollReduce = 4, kCollAllToAll = 5
+  kCollAllReduce = 0, kCollReduceScatter = 1, kCollAllGather = 2, kCollBroadcast = 3, kCollReduce = 4, kCollAllToAll = 5,
+  kCollAllToAllV = 6
 };
 
 MNCCL_HD int coll_num_ops(int coll, int n) {
@@ -233,6 +237,19 @@ MNCCL_HD uint64_t slice_len(uint64_t chunk_bytes, uint64_t slice_bytes, uint64_t
   if (off >= chunk_bytes) return 0;
   const uint64_t rest = chunk_bytes - off;
   return rest < slice_bytes ? rest : slice_bytes;
+}
+
+// ncclAllToAllv on the read schedule (kernels.hip varblock_push): the call's slices are cut for the
+// LARGEST block of the whole matrix, and slice s of the block for one destination covers the bytes
+// [s * slice_bytes, s * slice_bytes + varblock_len) of that block -- 0 once the block is exhausted,
+// and for empty blocks.  varblock_len_at: the same from the slice's byte offset (what the kernel has).
+MNCCL_HD uint64_t varblock_len_at(uint64_t block_bytes, uint64_t slice_bytes, uint64_t off) {
+  if (off >= block_bytes) return 0;
+  const uint64_t rest = block_bytes - off;
+  return rest < slice_bytes ? rest : slice_bytes;
+}
+MNCCL_HD uint64_t varblock_len(uint64_t block_bytes, uint64_t slice_bytes, uint64_t s) {
+  return varblock_len_at(block_bytes, slice_bytes, s * slice_bytes);
 }
 
 // The rooted collectives' slices (ncclBroadcast / ncclReduce): the buffer's `total_bytes` are cut

@@ -10,6 +10,7 @@
 // the read schedule).  mnccl_sim_rooted adds ncclBroadcast / ncclReduce with a root per call (the
 // ring's chain and masked ring, kernels.hip root_relay / root_fold), interleaved with the others.
 // mnccl_sim_mixed adds ncclAllToAll (the ring's hop table, kernels.hip exchange_push) to those five.
+// mnccl_sim_varblock adds ncclAllToAllv (kernels.hip varblock_push; the ring on padded blocks).
 // fp32 only (the schedule does not depend on the element type); ops as reference
 // mini_nccl.cu:38-41 with a = local, b = incoming.
 #include <stdint.h>
@@ -49,6 +50,9 @@ struct World {
   std::vector<std::vector<uint64_t>> tx_seq, rx_seq;  // per rank: [peer * C + w]
   std::vector<uint64_t> sig;           // registered-window call: each rank's START signature (empty: none)
   std::vector<int> mismatch;           // per rank: pipelines that saw a differing signature
+  // ncclAllToAllv (coll 6) on the read schedule: per (source r, destination q), at [r * n + q], the
+  // block's bytes and its byte offsets in r's send and in q's recv (kernels.h VarBlockArgs)
+  const uint64_t *vbytes = nullptr, *vsrc = nullptr, *vdst = nullptr;
 
   // message `seq` from src to dst on pipeline w (schedule.h msg_slot_off: the receiver's scratch)
   char* slot(int src, int dst, int w, uint64_t seq) {
@@ -196,6 +200,17 @@ bool read_step(World& W, Prog& P) {
       memcpy((char*)W.recv[q] + mine, (const char*)W.send[r] + (uint64_t)q * W.chunk_bytes + soff, (size_t)len);
     }
   };
+  // kernels.hip varblock_push: slice `it` of the call's largest-block geometry; of the block for each
+  // destination it covers schedule.h varblock_len bytes (0 once that block is exhausted)
+  auto varexchange = [&](uint32_t it) {
+    const uint64_t s = (uint64_t)it * W.A + w, soff = s * W.slice;
+    for (int k = 0; k < n; ++k) {
+      const int q = k < n - 1 ? direct_peer(n, r, 1 + (w % (n - 1) + k) % (n - 1)) : r;
+      const size_t i = (size_t)r * n + q;
+      const uint64_t len = varblock_len(W.vbytes[i], W.slice, s);
+      if (len) memcpy((char*)W.recv[q] + W.vdst[i] + soff, (const char*)W.send[r] + W.vsrc[i] + soff, (size_t)len);
+    }
+  };
   switch (P.j) {
     case 0:
       // START (kernels.hip read_kernel).  A registered-window call's signature is stored with it but
@@ -234,6 +249,7 @@ bool read_step(World& W, Prog& P) {
         if (W.coll == kCollAllGather) push(P.it++);
         else if (W.coll == kCollBroadcast) relay(P.it++);
         else if (W.coll == kCollAllToAll) exchange(P.it++);
+        else if (W.coll == kCollAllToAllV) varexchange(P.it++);
         else fold(P.it++);
       }
       if (P.it >= W.iters) P.j = 3;
@@ -330,6 +346,7 @@ int run_call(World& W, int code, int coll, uint64_t count, const float* const* s
   W.root = root;
   W.total_bytes = rooted ? count * 4 : 0;
   W.chunk_bytes = chunk * 4;
+  if (coll == kCollAllToAllV) W.chunk_bytes = count;  // (run_var_call: the largest block, in bytes)
   W.send.assign(send, send + n);
   W.recv.assign(recv, recv + n);
   W.own.assign((size_t)n, 1);
@@ -375,6 +392,7 @@ int run_call(World& W, int code, int coll, uint64_t count, const float* const* s
         if (s != d) memcpy(d, s, (size_t)W.chunk_bytes);
         continue;
       }
+      if (coll == kCollAllToAllV) continue;  // read schedule only: the kernel moves the own block too
       if (coll == kCollAllToAll) {
         // no pointer shift and no in-place form; the ring moves the blocks between ranks only, the
         // own block reaches the own recv by a copy before the launch (Comm::collective)
@@ -442,6 +460,66 @@ int run_call(World& W, int code, int coll, uint64_t count, const float* const* s
         W.tx_seq[r][(size_t)mod_n(r + 1, n) * channels + w] += (uint64_t)W.iters * coll_tx_msgs(coll, n, r, root);
         W.rx_seq[r][(size_t)mod_n(r - 1, n) * channels + w] += (uint64_t)W.iters * coll_rx_msgs(coll, n, r, root);
       }
+    }
+  return 0;
+}
+
+// One ncclAllToAllv call on the state W, as Comm::all_to_all_v runs it.  counts / sdispls / rdispls:
+// n x n, in elements of esz bytes -- [r * n + q] is rank r's entry for peer q.  The caller has checked
+// the matrix (varblock.h).  The geometry follows M, the largest block in bytes.  Read (code 2):
+// kernels.hip varblock_push through read_step.  Ring (code 0): the blocks packed at q * Mpad of a
+// stage, the ring's all-to-all with chunk Mpad into a second stage, unpacked into recv at rdispls;
+// the own block one direct copy.
+int run_var_call(World& W, int code, int esz, const uint64_t* counts, const uint64_t* sdispls, const uint64_t* rdispls,
+                 const char* const* send, char* const* recv, uint64_t slice_bytes, uint64_t min_slice,
+                 uint64_t schedule_seed, uint64_t& rng, uint64_t& steps) {
+  const int n = W.n;
+  if (code != 0 && code != 2) return -2;
+  uint64_t M = 0;
+  for (int i = 0; i < n * n; ++i) M = counts[i] * (uint64_t)esz > M ? counts[i] * (uint64_t)esz : M;
+  if (n == 1) {
+    if (M) memcpy(recv[0] + rdispls[0] * esz, send[0] + sdispls[0] * esz, (size_t)M);
+    return 0;
+  }
+  if (M == 0) return 0;  // nothing launched
+  if (code == 2) {
+    std::vector<uint64_t> vb((size_t)n * n), vs((size_t)n * n), vd((size_t)n * n);
+    for (int r = 0; r < n; ++r)
+      for (int q = 0; q < n; ++q) {
+        vb[(size_t)r * n + q] = counts[(size_t)r * n + q] * (uint64_t)esz;
+        vs[(size_t)r * n + q] = sdispls[(size_t)r * n + q] * (uint64_t)esz;
+        vd[(size_t)r * n + q] = rdispls[(size_t)q * n + r] * (uint64_t)esz;  // rank q's displacement for source r
+      }
+    W.vbytes = vb.data();
+    W.vsrc = vs.data();
+    W.vdst = vd.data();
+    const int rc = run_call(W, 2, kCollAllToAllV, M, (const float* const*)send, (float* const*)recv, slice_bytes, min_slice,
+                            schedule_seed, rng, steps);
+    W.vbytes = W.vsrc = W.vdst = nullptr;
+    return rc;
+  }
+  const uint64_t Mpad = (M + 15) & ~(uint64_t)15;
+  std::vector<std::vector<char>> in((size_t)n, std::vector<char>((size_t)(n * Mpad), (char)0x5c)),
+      out((size_t)n, std::vector<char>((size_t)(n * Mpad), (char)0x5c));
+  std::vector<const float*> sp((size_t)n);
+  std::vector<float*> rp((size_t)n);
+  for (int r = 0; r < n; ++r) {
+    for (int q = 0; q < n; ++q)
+      if (q != r && counts[(size_t)r * n + q])
+        memcpy(in[(size_t)r].data() + (size_t)q * Mpad, send[r] + sdispls[(size_t)r * n + q] * esz,
+               (size_t)(counts[(size_t)r * n + q] * esz));
+    sp[(size_t)r] = (const float*)in[(size_t)r].data();
+    rp[(size_t)r] = (float*)out[(size_t)r].data();
+  }
+  const int rc = run_call(W, 0, kCollAllToAll, Mpad / 4, sp.data(), rp.data(), slice_bytes, min_slice, schedule_seed, rng,
+                          steps);
+  if (rc != 0) return rc;
+  for (int r = 0; r < n; ++r)
+    for (int q = 0; q < n; ++q) {
+      const uint64_t c = counts[(size_t)q * n + r] * (uint64_t)esz;  // what q sent to r
+      if (!c) continue;
+      const char* from = q == r ? send[r] + sdispls[(size_t)r * n + r] * esz : out[(size_t)r].data() + (size_t)q * Mpad;
+      memcpy(recv[r] + rdispls[(size_t)r * n + q] * esz, from, (size_t)c);
     }
   return 0;
 }
@@ -602,6 +680,41 @@ int mnccl_sim_mixed(int n, int calls, const int* coll, const int* sched, const u
     if (counts[call] == 0) return -2;
     const int rc = run_call(W, sched[call], c, counts[call], send + (size_t)call * n, recv + (size_t)call * n, slice_bytes,
                             min_slice, schedule_seed, rng, steps, roots[call]);
+    if (rc != 0) return rc;
+  }
+  if (steps_out) *steps_out = steps;
+  return 0;
+}
+
+// mnccl_sim_mixed with ncclAllToAllv (schedule.h Coll 6): any of the seven collectives may follow any
+// other, on either schedule, on the one communicator state.  For a call of collective 6, counts[i] is
+// ignored and vcounts / vsdispls / vrdispls + i * n * n hold the call's n x n matrices in elements of
+// esz bytes ([r * n + q]: rank r's sendcounts[q] / sdispls[q] / rdispls[q]; recvcounts are the
+// transpose -- the caller checks that with mnccl_varblock_matrix_mismatch); send / recv are bytes.
+int mnccl_sim_varblock(int n, int calls, const int* coll, const int* sched, const uint64_t* counts, const int* roots,
+                       const float* const* send, float* const* recv, int esz, const uint64_t* vcounts,
+                       const uint64_t* vsdispls, const uint64_t* vrdispls, int op, uint64_t slice_bytes,
+                       uint64_t min_slice, int channels, int slots, uint64_t schedule_seed, uint64_t* steps_out) {
+  if (n < 1 || n > 16 || channels < 1 || slots < 1 || slice_bytes < 4 || slice_bytes % 4 || calls < 0) return -2;
+  if (esz != 1 && esz != 2 && esz != 4 && esz != 8) return -2;
+  World W;
+  init_world(W, n, channels, slots, op, slice_bytes);
+  uint64_t steps = 0;
+  uint64_t rng = schedule_seed * 6364136223846793005ull + 1442695040888963407ull;
+  for (int call = 0; call < calls; ++call) {
+    const int c = coll[call];
+    if (c < kCollAllReduce || c > kCollAllToAllV || (c != kCollAllReduce && sched[call] != 0 && sched[call] != 2)) return -2;
+    int rc;
+    if (c == kCollAllToAllV) {
+      const size_t m = (size_t)call * n * n;
+      rc = run_var_call(W, sched[call], esz, vcounts + m, vsdispls + m, vrdispls + m,
+                        (const char* const*)(send + (size_t)call * n), (char* const*)(recv + (size_t)call * n), slice_bytes,
+                        min_slice, schedule_seed, rng, steps);
+    } else {
+      if (counts[call] == 0) return -2;
+      rc = run_call(W, sched[call], c, counts[call], send + (size_t)call * n, recv + (size_t)call * n, slice_bytes,
+                    min_slice, schedule_seed, rng, steps, roots[call]);
+    }
     if (rc != 0) return rc;
   }
   if (steps_out) *steps_out = steps;
@@ -776,6 +889,29 @@ int mnccl_board_selftest(int rank, int nranks, const char* ip, int port, int sce
     fprintf(stderr, "board selftest rank %d: %s\n", rank, e.what());
     return -1;
   }
+}
+
+// csrc/varblock.h, the host-side rules of ncclAllToAllv, for the CPU suite: one rank's local checks
+// (a VarLocal verdict; the buffers are only compared, never dereferenced) and the matrix check on
+// n x n counts ([r * n + q]; 0, or 1 + r * n + q of the first pair that differs)
+int mnccl_varblock_check_local(int n, int esz, const void* send, const size_t* sendcounts, const size_t* sdispls,
+                               const void* recv, const size_t* recvcounts, const size_t* rdispls) {
+  if (n < 1 || n > mnccl::kVarMaxRanks || esz < 1) return -2;
+  return mnccl::varblock_check_local(n, esz, send, sendcounts, sdispls, recv, recvcounts, rdispls);
+}
+int mnccl_varblock_matrix_mismatch(int n, const uint64_t* sendcounts, const uint64_t* recvcounts) {
+  if (n < 1 || n > mnccl::kVarMaxRanks) return -2;
+  mnccl::VarRow rows[mnccl::kVarMaxRanks];
+  memset(rows, 0, sizeof rows);
+  for (int r = 0; r < n; ++r)
+    for (int q = 0; q < n; ++q) {
+      rows[r].sendcounts[q] = sendcounts[(size_t)r * n + q];
+      rows[r].recvcounts[q] = recvcounts[(size_t)r * n + q];
+    }
+  return mnccl::varblock_matrix_mismatch(n, rows);
+}
+uint64_t mnccl_varblock_len(uint64_t block_bytes, uint64_t slice_bytes, uint64_t s) {
+  return mnccl::varblock_len(block_bytes, slice_bytes, s);
 }
 
 // Config::from_env() rendered to text; -1 if the environment is invalid.

@@ -83,6 +83,8 @@ SIGNATURES = {
     "ncclBroadcast": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclReduce": (_I, [_VP, _VP, _SZ, _I, _I, _I, _VP, _VP]),
     "ncclAllToAll": (_I, [_VP, _VP, _SZ, _I, _VP, _VP]),
+    "ncclAllToAllv": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ),
+                           _I, _VP, _VP]),
     "mncclLocalReduce": (_I, [_VP, _VP, _VP, _SZ, _I, _I, _VP]),
     "mncclCommGetAsyncError": (_I, [_VP, ctypes.POINTER(_I)]),
     "mncclCommGetInfo": (_I, [_VP, ctypes.POINTER(CommInfo)]),
@@ -166,6 +168,15 @@ class Comm:
         """ncclAllToAll: send and recv each hold nranks * count elements; block q of this rank's send
         becomes block `rank` of rank q's recv (no in-place form).  Returns the ncclResult_t."""
         return load().ncclAllToAll(send_ptr, recv_ptr, count, dtype, self.handle, stream)
+
+    def all_to_all_v(self, send_ptr, sendcounts, sdispls, recv_ptr, recvcounts, rdispls, dtype=ncclFloat, stream=0):
+        """ncclAllToAllv: elements [sdispls[q], sdispls[q] + sendcounts[q]) of this rank's send become
+        elements [rdispls[r], rdispls[r] + recvcounts[r]) of rank q's recv.  The four arguments are
+        Python sequences of nranks element counts / displacements (read before the call returns);
+        a rank whose counts are all zero may pass 0 / None for its buffers.  Returns the ncclResult_t."""
+        arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
+        return load().ncclAllToAllv(send_ptr, arrays[0], arrays[1], recv_ptr, arrays[2], arrays[3], dtype, self.handle,
+                                    stream)
 
     def rank(self):
         r = ctypes.c_int()
