@@ -37,6 +37,13 @@
  *   ncclAllToAllv        the same exchange with a count and a displacement per peer on both sides
  *                        (expert-parallel dispatch / combine: every rank sends every peer a different
  *                        number of tokens, possibly none).
+ *
+ * and NCCL's point-to-point calls (pipeline parallelism, halo exchanges, batch_isend_irecv):
+ *
+ *   ncclSend / ncclRecv  `count` elements from one rank to another, byte for byte, with no host
+ *                        rendezvous: two ranks exchange while the others do nothing.
+ *   ncclGroupStart / ncclGroupEnd   several sends and recvs as one launch in which all progress
+ *                        concurrently.
  */
 #ifndef MINI_NCCL_EXT_H_
 #define MINI_NCCL_EXT_H_
@@ -67,7 +74,8 @@ extern "C" {
    GPU (MINI_NCCL_WINDOW_RENDEZVOUS); still 600: ncclReduceScatter and ncclAllGather were added
    without a change to anything above -- a caller detects them by symbol; still 600: ncclBroadcast
    and ncclReduce were added the same way; still 600: ncclAllToAll was added the same way; still 600:
-   ncclAllToAllv was added the same way (detected by symbol) */
+   ncclAllToAllv was added the same way (detected by symbol); still 600: ncclSend, ncclRecv,
+   ncclGroupStart and ncclGroupEnd were added the same way */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -306,6 +314,70 @@ ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, nc
 ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                            const size_t recvcounts[], const size_t rdispls[], ncclDataType_t datatype, ncclComm_t comm,
                            hipStream_t stream);
+
+/* Point to point, NCCL's names and signatures.
+ *
+ * Data.  The `count` elements of an ncclSend arrive, byte for byte, in the matching ncclRecv on `peer`
+ * (no arithmetic: any datatype ncclAllGather takes, by element size).  The sends from rank a to rank b
+ * match the recvs on b from a in call order.  Count and datatype must agree on both ends, as in NCCL;
+ * a disagreement is the caller's error and ends at the watchdog like any other stuck call.
+ *
+ * Groups.  Group state is per thread and groups nest by a depth counter.  An ungrouped ncclSend /
+ * ncclRecv is a group of one.  Inside a group a call only records its operation and returns
+ * ncclSuccess or its argument error; the outermost ncclGroupEnd launches every recorded operation as
+ * ONE kernel launch in which all of them progress concurrently -- every directed pair (the sends to
+ * one peer, the recvs from one peer) on waves of its own -- and then behaves exactly as a collective
+ * does: blocking mode, stream ordering after the communicator's previous call, sticky errors, the
+ * watchdog.  ncclGroupEnd with no open group is ncclInvalidUsage.  Every operation of a group must
+ * name the same communicator and the same stream; one that does not is ncclInvalidUsage at that call.
+ * Any error inside a group poisons it: ncclGroupEnd returns the first error, launches nothing, and
+ * leaves the communicator usable.  A group may hold several sends to one peer and several recvs from
+ * one peer: they run in call order.  At most 64 operations fit in a group (kMaxGroupOps); one more is
+ * ncclInvalidUsage.  DEFERRED COLLECTIVES ARE OUT OF SCOPE: ncclAllReduce, ncclReduceScatter,
+ * ncclAllGather, ncclBroadcast, ncclReduce, ncclAllToAll or ncclAllToAllv called while a group is open
+ * return ncclInvalidUsage (after their NULL and count == 0 checks) with nothing launched, and the
+ * group stays open and clean; with no group open they behave exactly as before.
+ *
+ * Self.  Inside a group, a send to the own rank pairs with a recv from the own rank, in order: one
+ * device copy inside the same launch.  Unequal byte sizes, or a self send or recv left unpaired at
+ * ncclGroupEnd, is ncclInvalidUsage.  Outside a group peer == rank is ncclInvalidUsage, because it
+ * could never complete.  With nranks == 1 only the self pair exists.
+ *
+ * Checks, in this order (no exception crosses the boundary):
+ *  1. a NULL comm, or a NULL buffer with count != 0: ncclInvalidArgument;
+ *  2. count == 0: ncclSuccess, nothing recorded and nothing moves -- both ends skip it, so matching
+ *     stays consistent;
+ *  3. an unsupported datatype: ncclInternalError, before the communicator is read;
+ *  4. with the communicator, peer outside [0, nranks): ncclInvalidArgument;
+ *  5. a byte size that overflows size_t: ncclInvalidArgument;
+ *  6. a recv range overlapping another recv range, or any send range, of the same group:
+ *     ncclInvalidArgument;
+ *  7. a buffer that is neither device memory of this rank's GPU nor pinned host memory:
+ *     ncclInvalidArgument.  Pinned host memory is reached through its device mapping.  PAGEABLE HOST
+ *     MEMORY IS NOT STAGED for these calls.
+ *
+ * The deadlock rule, as NCCL states it.  Two ranks that each send to the other and then receive,
+ * ungrouped, deadlock: they must put the send and the recv into one group.  An ungrouped ncclSend
+ * returns (blocking mode), or its kernel ends (stream-ordered mode), only once its last slice is in
+ * the receiver's scratch, and a message larger than the pair's scratch slots (slots x slot_bytes x the
+ * message's pipelines) waits for the matching ncclRecv to drain them.  A shorter send MAY complete
+ * before its recv is called; nothing promises it.
+ *
+ * Capture.  There is no host rendezvous and the message counters live on the device, so a group
+ * captured into a HIP graph replays correctly; count, pointers and peers are baked into the graph.
+ *
+ * Transport.  The transfer runs the ring's scratch protocol between the two ranks -- the sender
+ * stores slices of at most slot_bytes into its region of the receiver's scratch and raises READY, the
+ * receiver copies them out and returns a CREDIT -- so mncclCommInfo_t.last_algo reports mncclAlgoRing.
+ * A message's slices and pipelines are a function of its byte count and the communicator's
+ * rank-uniform configuration only.  A zero-copy form that pushes straight into the peer's recvbuff
+ * needs a pairwise rendezvous and is not part of this interface yet. */
+ncclResult_t ncclSend(const void* sendbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
+                      hipStream_t stream);
+ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
+                      hipStream_t stream);
+ncclResult_t ncclGroupStart(void);
+ncclResult_t ncclGroupEnd(void);
 
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream);

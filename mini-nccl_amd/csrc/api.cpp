@@ -21,6 +21,7 @@
 #include "kernels.h"
 #include "mini_nccl_api.h"
 #include "mini_nccl_ext.h"
+#include "p2p.h"
 
 using mnccl::Comm;
 
@@ -32,6 +33,21 @@ bool dtype_ok(ncclDataType_t t) {
   return t == ncclFloat || t == ncclDouble || t == ncclInt32 || t == ncclFloat16 || t == ncclBfloat16;
 }
 bool op_ok(ncclRedOp_t op) { return op == ncclSum || op == ncclProd || op == ncclMax || op == ncclMin; }
+
+// ncclGroupStart / ncclGroupEnd: the group being recorded, one per thread (ranks may run as threads
+// of one process).  Groups nest by a depth counter; the outermost ncclGroupEnd launches.  The first
+// error of an operation poisons the group: ncclGroupEnd returns it and launches nothing.
+struct GroupState {
+  int depth = 0;
+  ncclResult_t err = ncclSuccess;
+  Comm* comm = nullptr;  // the communicator and stream every operation of the group must name
+  hipStream_t stream = nullptr;
+  mnccl::P2pGroup ops;
+};
+thread_local GroupState g_group;
+
+// a collective called while a group is open: deferred collectives are out of scope
+bool group_open() { return g_group.depth > 0; }
 
 struct RoctxRange {
   explicit RoctxRange(const char* m) { roctxRangePushA(m); }
@@ -103,6 +119,7 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
                            ncclRedOp_t op, ncclComm_t comm, hipStream_t stream) {
   if (!comm || !sendbuff || !recvbuff) return ncclInvalidArgument;  // api.cpp:139
   if (count == 0) return ncclSuccess;                               // api.cpp:140
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclAllReduce");
   if (!dtype_ok(datatype) || !op_ok(op)) {
     // the reference throws inside get_type_size / to_internal_op -> ncclInternalError (:182-185)
@@ -126,6 +143,7 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
                                ncclRedOp_t op, ncclComm_t comm, hipStream_t stream) {
   if (!comm || !sendbuff || !recvbuff) return ncclInvalidArgument;
   if (recvcount == 0) return ncclSuccess;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclReduceScatter");
   if (!dtype_ok(datatype) || !op_ok(op)) {
     fprintf(stderr, "[Mini-NCCL] ReduceScatter Internal Error: unsupported %s\n", dtype_ok(datatype) ? "RedOp" : "DataType");
@@ -145,6 +163,7 @@ ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcoun
                            ncclComm_t comm, hipStream_t stream) {
   if (!comm || !sendbuff || !recvbuff) return ncclInvalidArgument;
   if (sendcount == 0) return ncclSuccess;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclAllGather");
   if (!dtype_ok(datatype)) {
     fprintf(stderr, "[Mini-NCCL] AllGather Internal Error: unsupported DataType\n");
@@ -167,6 +186,7 @@ ncclResult_t ncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, n
                            ncclComm_t comm, hipStream_t stream) {
   if (!comm) return ncclInvalidArgument;
   if (count == 0) return ncclSuccess;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclBroadcast");
   if (!dtype_ok(datatype)) {
     fprintf(stderr, "[Mini-NCCL] Broadcast Internal Error: unsupported DataType\n");
@@ -186,6 +206,7 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
                         int root, ncclComm_t comm, hipStream_t stream) {
   if (!comm) return ncclInvalidArgument;
   if (count == 0) return ncclSuccess;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclReduce");
   if (!dtype_ok(datatype) || !op_ok(op)) {
     fprintf(stderr, "[Mini-NCCL] Reduce Internal Error: unsupported %s\n", dtype_ok(datatype) ? "RedOp" : "DataType");
@@ -207,6 +228,7 @@ ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, nc
                           hipStream_t stream) {
   if (!comm || !sendbuff || !recvbuff) return ncclInvalidArgument;
   if (count == 0) return ncclSuccess;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclAllToAll");
   if (!dtype_ok(datatype)) {
     fprintf(stderr, "[Mini-NCCL] AllToAll Internal Error: unsupported DataType\n");
@@ -229,6 +251,7 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
                            const size_t recvcounts[], const size_t rdispls[], ncclDataType_t datatype, ncclComm_t comm,
                            hipStream_t stream) {
   if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclAllToAllv");
   if (!dtype_ok(datatype)) {
     fprintf(stderr, "[Mini-NCCL] AllToAllv Internal Error: unsupported DataType\n");
@@ -239,6 +262,83 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
                                                        (int)datatype, stream);
   } catch (const std::exception& e) {
     fprintf(stderr, "[Mini-NCCL] AllToAllv Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
+// Point to point (mini_nccl_ext.h): the checks in the header's order.  Inside a group a call only
+// records its operation; outside, it is a group of one and launches at once.
+static ncclResult_t p2p_call(bool send, const void* buff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
+                             hipStream_t stream) {
+  GroupState& gs = g_group;
+  const bool grouped = gs.depth > 0;
+  auto fail = [&](ncclResult_t rc) {
+    if (grouped && gs.err == ncclSuccess) gs.err = rc;
+    return rc;
+  };
+  if (!comm || (!buff && count != 0)) return fail(ncclInvalidArgument);
+  if (count == 0) return ncclSuccess;  // both ends skip it: nothing recorded, matching stays consistent
+  RoctxRange range(send ? "mini_ncclSend" : "mini_ncclRecv");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] %s Internal Error: unsupported DataType\n", send ? "Send" : "Recv");
+    return fail(ncclInternalError);
+  }
+  Comm* c = reinterpret_cast<Comm*>(comm);
+  try {
+    if (!grouped) {
+      mnccl::P2pGroup one;
+      const ncclResult_t rc = c->p2p_validate(one, false, send, peer, buff, count, (int)datatype);
+      return rc != ncclSuccess ? rc : c->p2p_group(one, stream);
+    }
+    if (gs.comm && (gs.comm != c || gs.stream != stream)) {
+      fprintf(stderr, "[Mini-NCCL] %s: every operation of a group must name the same communicator and stream\n",
+              send ? "ncclSend" : "ncclRecv");
+      return fail(ncclInvalidUsage);
+    }
+    const ncclResult_t rc = c->p2p_validate(gs.ops, true, send, peer, buff, count, (int)datatype);
+    if (rc != ncclSuccess) return fail(rc);
+    gs.comm = c;
+    gs.stream = stream;
+    return ncclSuccess;
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] %s Internal Error: %s\n", send ? "Send" : "Recv", e.what());
+    return fail(ncclInternalError);
+  } catch (...) {
+    return fail(ncclSystemError);
+  }
+}
+
+ncclResult_t ncclSend(const void* sendbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
+                      hipStream_t stream) {
+  return p2p_call(true, sendbuff, count, datatype, peer, comm, stream);
+}
+
+ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
+                      hipStream_t stream) {
+  return p2p_call(false, recvbuff, count, datatype, peer, comm, stream);
+}
+
+ncclResult_t ncclGroupStart(void) {
+  ++g_group.depth;
+  return ncclSuccess;
+}
+
+ncclResult_t ncclGroupEnd(void) {
+  GroupState& gs = g_group;
+  if (gs.depth == 0) return ncclInvalidUsage;
+  if (--gs.depth > 0) return ncclSuccess;
+  // the outermost end: take the group and leave the thread's state clean whatever happens below
+  const GroupState done = gs;
+  gs = GroupState();
+  if (done.err != ncclSuccess) return done.err;  // poisoned: nothing is launched
+  if (done.ops.nops == 0 || !done.comm) return ncclSuccess;
+  RoctxRange range("mini_ncclGroupEnd");
+  try {
+    return done.comm->p2p_group(done.ops, done.stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] GroupEnd Internal Error: %s\n", e.what());
     return ncclInternalError;
   } catch (...) {
     return ncclSystemError;

@@ -241,6 +241,7 @@ void Comm::exchange_and_map() {
       most = std::max(most, same);
     }
     run_pipes_ = resident_pipes(wave_channels(), geo_.waves, cus, most, kMinWavesPerSimd);
+    p2p_pipes_ = mnccl::p2p_pipes(nranks_, wave_channels(), cus, most, kMinWavesPerSimd);
     if (run_pipes_ < wave_channels() && rank_ == 0)
       fprintf(stderr, "[Mini-NCCL] %d rank(s) share a GPU of %d CUs: calls launch at most %d of the communicator's %d "
               "pipelines, so every rank's waves stay resident together\n", most, cus, run_pipes_, wave_channels());
@@ -1153,6 +1154,66 @@ ncclResult_t Comm::all_to_all_v(const void* send, const size_t* sendcounts, cons
       hip_check(hipMemcpyAsync(r0 + rdispls[rank_] * (size_t)esz, s0 + sdispls[rank_] * (size_t)esz,
                                sendcounts[rank_] * (size_t)esz, hipMemcpyDefault, stream), "own block");
   }
+  return end_call(scope, stream, seq);
+}
+
+// One ncclSend / ncclRecv against the group recorded so far (the caller -- api.cpp -- made the NULL,
+// count == 0 and datatype checks): p2p.h's checks in their order, then the buffer's memory.
+ncclResult_t Comm::p2p_validate(P2pGroup& g, bool grouped, bool send, int peer, const void* buf, size_t count,
+                                int dtype) {
+  const char* const name = send ? "ncclSend" : "ncclRecv";
+  uint64_t bytes = 0;
+  const int v = p2p_check_op(g, nranks_, send, peer, buf, count, dtype_size(dtype), &bytes);
+  if (v != kP2pOk) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s: %s\n", rank_, name,
+            v == kP2pPeerRange  ? "peer is outside [0, nranks)"
+            : v == kP2pOverflow ? "count times the element size overflows size_t"
+                                : "the buffer overlaps a recv buffer of the same group (or, a recv, any buffer of it)");
+    return ncclInvalidArgument;
+  }
+  const void* kptr = buf;
+  bool local = false;
+  int cur_dev = device_;
+  if (hipGetDevice(&cur_dev) != hipSuccess) (void)hipGetLastError();
+  if (cur_dev != device_) hip_check(hipSetDevice(device_), "hipSetDevice");
+  const Reach how = reach(buf, &kptr, &local);
+  if (cur_dev != device_) hipSetDevice(cur_dev);
+  if (!(how == Reach::kMapped || (how == Reach::kDevice && local))) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s: the buffer is neither device memory of this rank's GPU nor pinned host "
+            "memory (pageable host memory is not staged for point-to-point calls)\n", rank_, name);
+    return ncclInvalidArgument;
+  }
+  if (!grouped && peer == rank_) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s to / from the own rank outside a group could never complete\n", rank_, name);
+    return ncclInvalidUsage;
+  }
+  if (p2p_append(g, send, peer, buf, (uint64_t)(uintptr_t)kptr, bytes) != kP2pOk) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s: more than %d operations in one group\n", rank_, name, kMaxGroupOps);
+    return ncclInvalidUsage;
+  }
+  return ncclSuccess;
+}
+
+// The outermost ncclGroupEnd (an ungrouped call is a group of one): one launch, no host rendezvous.
+ncclResult_t Comm::p2p_group(const P2pGroup& g, hipStream_t stream) {
+  if (sticky_ != ncclSuccess) return sticky_;
+  if (check_status() != ncclSuccess) return sticky_;
+  P2pArgs a;
+  const int v = p2p_build(g, rank_, p2p_pipes_, wave_slice(), &a);
+  if (v != kP2pOk) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: ncclGroupEnd: %s\n", rank_,
+            v == kP2pSelfSize ? "a send to the own rank and the recv it pairs with differ in bytes"
+                              : "a send to the own rank without a recv from it in the group, or the reverse");
+    return ncclInvalidUsage;
+  }
+  if (p2p_launch_waves(a) == 0) return ncclSuccess;
+  const CallScope scope = begin_call(stream);
+  uint32_t seq = ++call_seq_;
+  if (seq == 0) seq = ++call_seq_;
+  int A = 0;
+  const CollParams p = make_params(0, nullptr, nullptr, 0, seq, nullptr, nullptr, 0, 0, kCollAllReduce, 0, 0, &A);
+  hip_check(launch_p2p(p, a, stream), "kernel launch");
+  last_algo_ = 0;  // the ring's scratch protocol
   return end_call(scope, stream, seq);
 }
 

@@ -13,6 +13,7 @@
 #include "config.h"
 #include "kernels.h"
 #include "mini_nccl_api.h"
+#include "p2p.h"
 #include "peerbuf.h"
 #include "schedule.h"
 
@@ -74,6 +75,20 @@ class Comm {
   // rendezvous decides against it, the ring's all-to-all on blocks padded to the largest one.
   ncclResult_t all_to_all_v(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
                             const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream);
+
+  // Point to point (NCCL's ncclSend / ncclRecv inside ncclGroupStart / ncclGroupEnd; api.cpp keeps
+  // the group per thread, p2p.h its rules).  p2p_validate: one operation against the group recorded
+  // so far -- the peer's range, the byte size, the overlaps (p2p.h p2p_check_op), then the buffer's
+  // memory: device memory of this rank's GPU as is, pinned host memory through its device mapping
+  // (reach), anything else ncclInvalidArgument -- and appends it; outside a group peer == rank is
+  // ncclInvalidUsage.  p2p_group: every recorded operation as ONE launch of kernels.hip p2p_kernel on
+  // the ring's scratch protocol, with no host rendezvous, between begin_call and end_call as any
+  // collective; a self send or recv left unpaired, or paired with another size, is ncclInvalidUsage
+  // with nothing launched.  last_algo reports the ring.
+  ncclResult_t p2p_validate(P2pGroup& g, bool grouped, bool send, int peer, const void* buf, size_t count, int dtype);
+  ncclResult_t p2p_group(const P2pGroup& g, hipStream_t stream);
+  // pipelines one point-to-point message may use (schedule.h p2p_pipes; the same on every rank)
+  int p2p_pipes() const { return p2p_pipes_; }
 
   int rank() const { return rank_; }
   int nranks() const { return nranks_; }
@@ -190,6 +205,7 @@ class Comm {
   bool window_fast_ = true;                 // window calls skip the host rendezvous (MINI_NCCL_WINDOW_RENDEZVOUS)
   int run_pipes_ = 0;                       // 0 until exchange_and_map: run_pipes()
   int ranks_on_device_ = 1;
+  int p2p_pipes_ = 1;                       // schedule.h p2p_pipes (exchange_and_map)
   bool topo_read_ = true;        // auto may run the read schedule (every pair: same GPU or 1 xGMI hop)
   std::string topo_why_ = "read: one rank";
   int peer_link_[kMaxRanks] = {}, peer_hops_[kMaxRanks] = {};

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "p2p.h"
+
 namespace mnccl {
 
 // Element types the kernels are instantiated for (subset of ncclDataType_t values).
@@ -104,6 +106,13 @@ struct VarBlockArgs {
 // every rank), p.peer_recv every rank's recv.  By element size (2 / 4 / 8 from dtype): no arithmetic.
 hipError_t launch_varblock(int dtype, int channels, int threads, const CollParams& p, const VarBlockArgs& v,
                            hipStream_t stream);
+// ncclSend / ncclRecv (kernels.hip p2p_kernel): one launch for a whole group.  p: the communicator's
+// mailbox, scratch, counters, control words and timeout as every kernel gets them (send / recv and
+// the call geometry unused); a (p2p.h P2pArgs, a second by-value argument): per directed pair the
+// operations in order, plus the self copies.  One 64-thread workgroup per wave: p2p_launch_waves(a)
+// of them, wave b serving pair b / a.pipes on pipeline b % a.pipes.  Refuses an empty launch, more
+// pairs or pipelines than the layout holds, and pairs on a communicator of one rank.
+hipError_t launch_p2p(const CollParams& p, const P2pArgs& a, hipStream_t stream);
 // the read schedule's push form for large calls as three launches (start, grid fold, done):
 // schedule.h read_grid_fits(p.chunk_bytes, p.n, kReadGridFloor) (2 <= n <= 8, whole 16-byte vectors), p.go set
 // vectors: 0 = schedule.h read_grid_vectors; 1 / 2 / 4 (MINI_NCCL_GRID_VECTORS) for fp32 Sum only

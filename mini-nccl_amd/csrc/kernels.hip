@@ -27,6 +27,10 @@
 //  varblock_push  the variable all-to-all (ncclAllToAllv) on the same protocol: exchange_push with a
 //                 length and two offsets per destination, the slices cut for the largest block of
 //                 the whole matrix.  Its fallback is the ring's all-to-all on padded blocks.
+//  p2p_kernel     point to point (ncclSend / ncclRecv, one launch per group): a send is the sender's
+//                 half of one ring hop to an arbitrary peer, a recv the receiver's half, on the
+//                 ring's scratch, flags and counters; every directed pair of the group on waves of
+//                 its own, one per pipeline, so no wave ever waits for two peers.
 //  read_start / read_grid / read_done   the read schedule's push form as three launches (the
 //                 runtime form mncclAlgoReadGrid, for large calls): a grid of one-batch workgroups
 //                 between a one-wave START and a one-wave DONE.
@@ -1339,6 +1343,112 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) varblock_push(C
   });
 }
 
+// ---------------------------------------------------------------- point to point
+// ncclSend / ncclRecv (p2p_kernel): a send is the sender's half of one ring hop to an arbitrary
+// peer, a recv the receiver's half, on the scratch protocol of the file header -- the peer's region
+// of the receiver's scratch (one per peer: schedule.h region_index), the pair's monotone READY /
+// CREDIT words and its device-side counters, which continue across calls, schedules and graph
+// replays.  No host rendezvous: two ranks exchange while the others do nothing.
+//
+// One launch runs a whole group (p2p.h P2pArgs, the second by-value argument).  Every directed pair
+// present in the group -- the sends to one peer, or the recvs from one peer -- gets its OWN waves,
+// one per pipeline, and a pair's waves run that pair's operations one after another; no wave ever
+// serves two pairs.  (A wave that alternated a send slice and a recv slice would deadlock against a
+// peer that receives and then sends ungrouped as soon as the message outgrows the slots.)  With at
+// most 2 (n - 1) pairs x schedule.h p2p_pipes waves the launch stays inside the resident budget:
+// all its waves are resident together.  A message's slices and pipelines follow from its byte count
+// and the rank-uniform configuration alone (schedule.h p2p_msg_pipes), so both ends agree without
+// talking.  Each end picks the 16-byte or the element path from ITS OWN pointer: the slot holds
+// plain bytes at an aligned offset, so the two ends may differ; no arithmetic, so the element path
+// moves 2-byte elements whatever the datatype (every supported size is a multiple).
+//
+// Sender, per slice: wait for the CREDIT of message seq - slots; load its own bytes and store them
+// into the peer's slot (sc0 sc1: move<kSend>); drain; lane 0 publishes READY.  Receiver, per slice:
+// poll READY; load the slot (sc0 sc1) and store into recv (move<kCopy>); drain; lane 0 returns the
+// CREDIT.  Every spin is wait_ge_spin's: bounded, abort-aware, the first give-up claims the status
+// and raises the peer's ABORT word.  A self pair is one copy by waves of their own.
+typedef _Float16 P2pElem;  // the element path's 2-byte unit (moved, never used for arithmetic)
+
+// a 64-bit value every lane holds alike, moved to scalar registers: the counter a wave loads from
+// memory then keeps its slice loop, its waits and its slot descriptors wave-uniform
+__device__ __forceinline__ u64 uniform64(u64 v) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return ((u64)hi << 32) | lo;
+}
+
+// the self copies, spread over the launch's self waves: wave k of K takes batches k, k + K, ...
+__device__ __forceinline__ void p2p_self_copies(const P2pArgs& a, int k, int lane) {
+  const int K = a.self_waves;
+  for (int c = 0; c < a.nself; ++c) {
+    const int i = a.self_first + 2 * c;
+    const char* src = reinterpret_cast<const char*>(a.ptr[i]);
+    char* dst = reinterpret_cast<char*>(a.ptr[i + 1]);
+    const u64 bytes = a.bytes[i];
+    const u64 nvec = a.vec[i] ? bytes >> 4 : 0;
+    for (u64 v = (u64)k * 64 + (u64)lane; v < nvec; v += (u64)K * 64) st_g16(dst + v * 16, ld_g16(src + v * 16));
+    if (k == 0)
+      for (u64 b = nvec * 16 + (u64)lane; b < bytes; b += 64) dst[b] = src[b];
+  }
+}
+
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) p2p_kernel(CollParams p, P2pArgs a) {
+  signal_start(p);
+  const int lane = threadIdx.x & 63;
+  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+  const int nwaves = a.npairs * a.pipes;
+  if (b >= nwaves) {
+    p2p_self_copies(a, b - nwaves, lane);
+    return;
+  }
+  // C: the communicator's pipelines (mailbox, scratch and counter layout); w: this wave's pipeline
+  const int pair = b / a.pipes, w = b % a.pipes, C = p.pipes;
+  const int n = p.n, r = p.rank, K = p.nslots;
+  const int peer = a.pair_peer[pair], first = a.pair_first[pair], count = a.pair_count[pair];
+  const bool sends = a.pair_send[pair] != 0;
+  const Ctl ctl{p.status, p.host_abort, p.mbox + mbox_abort(n, C), p.timeout_ticks, p.mbox, p.claim};
+  u64* ctr = (sends ? p.tx_seq : p.rx_seq) + (u64)peer * C + w;
+  u64 seq = uniform64(*ctr);
+  // the word this wave waits on (in this rank's mailbox) and the one it raises (in the peer's)
+  const u64* wait_word = p.mbox + (sends ? mbox_credit(n, C, peer, w) : mbox_ready(C, peer, w));
+  u64* raise_word = p.peer_mbox[peer] + (sends ? mbox_ready(C, r, w) : mbox_credit(n, C, r, w));
+  const u64 slot = p.slot_bytes;
+  for (int i = first; i < first + count; ++i) {
+    const u64 bytes = a.bytes[i], nsl = p2p_nslices(bytes, slot);
+    const int A = p2p_msg_pipes(bytes, slot, a.p2p_pipes);
+    if (w >= A) continue;  // this message uses fewer pipelines: the pair's counters on w stay
+    char* local = reinterpret_cast<char*>(a.ptr[i]);
+    const bool vec = a.vec[i] != 0;
+    for (u64 s = (u64)w; s < nsl; s += (u64)A) {
+      const uint32_t len = (uint32_t)slice_len(bytes, slot, s);
+      // sender: the slot is free once message seq - slots was consumed; receiver: the message landed
+      const bool ok = sends ? (seq + 1 <= (u64)K || wave_wait_ge(wait_word, seq + 1 - K, ctl, lane))
+                            : wave_wait_ge(wait_word, seq + 1, ctl, lane);
+      if (!ok) {
+        if (lane == 0) st_sys(p.peer_mbox[peer] + mbox_abort(n, C), abort_word(p));
+        return;
+      }
+      char* at = local + s * slot;
+      if (sends) {
+        const rsrc_t out = make_rsrc(msg_slot(p, C, r, peer, w, seq), len);
+        if (vec) move<P2pElem, kSum, true, kSend>(at, at, out, out, len, lane);
+        else move<P2pElem, kSum, false, kSend>(at, at, out, out, len, lane);
+      } else {
+        acquire_sys(p.sys_fence);
+        const rsrc_t in = make_rsrc(msg_slot(p, C, peer, r, w, seq), len);
+        if (vec) move<P2pElem, kSum, true, kCopy>(at, at, in, in, len, lane);
+        else move<P2pElem, kSum, false, kCopy>(at, at, in, in, len, lane);
+      }
+      drain_stores();  // every load of the slot has returned and every store has landed
+      ++seq;
+      if (lane == 0) {
+        if (sends) publish(raise_word, seq, p.sys_fence);
+        else st_sys(raise_word, seq);
+      }
+    }
+  }
+  if (lane == 0) *ctr = seq;
+}
+
 // ---------------------------------------------------------------- read schedule, grid form
 // mncclAlgoReadGrid / MINI_NCCL_ALGO=read_grid, and auto's large read calls since 5.1
 // (schedule.h read_grid_form): the push form of a large call (read_grid_fits) as three launches on
@@ -1774,6 +1884,28 @@ hipError_t launch_varblock(int dtype, int C, int nt, const CollParams& p, const 
     hipLaunchKernelGGL(varblock_push<decltype(e)::value>, dim3(C), dim3(nt), 0, st, p, v);
     return hipGetLastError();
   });
+}
+
+hipError_t launch_p2p(const CollParams& p, const P2pArgs& a, hipStream_t st) {
+  const int waves = p2p_launch_waves(a);
+  // the shapes the kernel assumes, checked before anything is launched: every index it forms from
+  // the argument stays inside the argument's arrays and the communicator's layout
+  if (waves < 1 || a.npairs < 0 || a.npairs > kP2pMaxPairs || a.nself < 0 || a.self_waves < 0 ||
+      a.self_waves > kP2pMaxSelfWaves || (a.nself == 0) != (a.self_waves == 0) || a.self_first < 0 ||
+      a.self_first + 2 * a.nself > kMaxGroupOps)
+    return hipErrorInvalidValue;
+  if (a.npairs > 0) {
+    if (p.n < 2 || p.n > kMaxRanks || p.nslots < 1 || !p.mbox || !p.tx_seq || !p.rx_seq || a.pipes < 1 ||
+        a.pipes > a.p2p_pipes || a.p2p_pipes > p.pipes || p.slot_bytes == 0 || p.slot_bytes > kMaxSlice)
+      return hipErrorInvalidValue;
+    for (int i = 0; i < a.npairs; ++i)
+      if (a.pair_peer[i] >= p.n || a.pair_peer[i] == p.rank || a.pair_count[i] < 1 ||
+          a.pair_first[i] + a.pair_count[i] > a.self_first || !p.peer_mbox[a.pair_peer[i]] ||
+          !p.peer_scratch[a.pair_peer[i]])
+        return hipErrorInvalidValue;
+  }
+  hipLaunchKernelGGL(p2p_kernel, dim3((unsigned)waves), dim3(64), 0, st, p, a);
+  return hipGetLastError();
 }
 
 // One grid launch; which (G, V) exist: the rule's pairs (schedule.h read_grid_vectors: V = 1 up to

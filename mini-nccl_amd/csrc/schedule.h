@@ -433,12 +433,48 @@ MNCCL_HD int topology_blocks_read(int n, const int* link, const int* hops) {
 // of its peers, so the waves a call launches on the most crowded GPU -- `most` ranks on a GPU of
 // `cus` CUs, each CU's 4 SIMDs keeping `waves_per_simd` of the kernels' waves resident -- must all
 // fit at once: min(P, cus x 4 x waves_per_simd / most), whole workgroups of `waves`, at least one.
-MNCCL_HD int resident_pipes(int P, int waves, int cus, int most, int waves_per_simd) {
+// resident_cap: that budget alone, whole workgroups of `waves`, at least one.
+MNCCL_HD int resident_cap(int waves, int cus, int most, int waves_per_simd) {
   if (most < 1) most = 1;
   if (waves < 1) waves = 1;
   int cap = cus * 4 * waves_per_simd / most / waves * waves;
   if (cap < waves) cap = waves;
+  return cap;
+}
+MNCCL_HD int resident_pipes(int P, int waves, int cus, int most, int waves_per_simd) {
+  const int cap = resident_cap(waves, cus, most, waves_per_simd);
   return P < cap ? P : cap;
+}
+
+// Point-to-point (ncclSend / ncclRecv, kernels.hip p2p_kernel).  Both ends of a message must agree
+// on its slices and pipelines without talking, so a message's geometry is a function of its byte
+// count and the communicator's rank-uniform configuration only -- never of what else its group
+// holds, nor of a pointer's alignment.
+//  * p2p_pipes: the pipelines one message may use.  A launch gives every directed pair present in
+//    its group one wave per pipeline, a rank can have 2 (n - 1) directed pairs busy at once, and all
+//    of a launch's waves must be resident together on the most crowded GPU: the resident budget
+//    (resident_cap for one-wave workgroups: the cap, not its minimum with the communicator's
+//    pipelines) divided by 2 (n - 1), clamped to [1, C].  One rank: only the self pair exists.
+//  * a message of `bytes` is cut into ceil(bytes / slot_bytes) slices, slice s of slice_len(bytes,
+//    slot_bytes, s) bytes; it uses pipelines 0 .. A - 1, A = min(p2p_pipes, nslices), and pipeline w
+//    carries slices w, w + A, ..., one message each on the pair's own READY / CREDIT / slot /
+//    counter entries (mbox_ready, mbox_credit, msg_slot_off, tx_seq / rx_seq at [peer * C + w]).
+MNCCL_HD int p2p_pipes(int n, int C, int cus, int most, int waves_per_simd) {
+  if (C < 1) C = 1;
+  if (n < 2) return 1;
+  const int per = resident_cap(1, cus, most, waves_per_simd) / (2 * (n - 1));
+  return per < 1 ? 1 : per < C ? per : C;
+}
+MNCCL_HD uint64_t p2p_nslices(uint64_t bytes, uint64_t slot_bytes) { return (bytes + slot_bytes - 1) / slot_bytes; }
+MNCCL_HD int p2p_msg_pipes(uint64_t bytes, uint64_t slot_bytes, int pipes) {
+  const uint64_t ns = p2p_nslices(bytes, slot_bytes);
+  return ns < (uint64_t)pipes ? (int)ns : pipes;
+}
+// slices pipeline w of a message carries: what the pair's counters on w advance by
+MNCCL_HD uint64_t p2p_pipe_msgs(uint64_t bytes, uint64_t slot_bytes, int pipes, int w) {
+  const uint64_t ns = p2p_nslices(bytes, slot_bytes);
+  const uint64_t A = (uint64_t)p2p_msg_pipes(bytes, slot_bytes, pipes);
+  return (uint64_t)w < A ? (ns - (uint64_t)w + A - 1) / A : 0;
 }
 
 // Whether a read-schedule call launches in the grid form (kernels.hip read_start / read_grid /

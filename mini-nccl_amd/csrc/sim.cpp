@@ -11,6 +11,8 @@
 // ring's chain and masked ring, kernels.hip root_relay / root_fold), interleaved with the others.
 // mnccl_sim_mixed adds ncclAllToAll (the ring's hop table, kernels.hip exchange_push) to those five.
 // mnccl_sim_varblock adds ncclAllToAllv (kernels.hip varblock_push; the ring on padded blocks).
+// mnccl_sim_p2p adds ncclSend / ncclRecv groups (kernels.hip p2p_kernel, one wave per (pair, pipeline)
+// from p2p.h's argument builder), every rank running its own list of launches, between collectives.
 // fp32 only (the schedule does not depend on the element type); ops as reference
 // mini_nccl.cu:38-41 with a = local, b = incoming.
 #include <stdint.h>
@@ -18,6 +20,7 @@
 
 #include <vector>
 
+#include "p2p.h"
 #include "schedule.h"
 
 using namespace mnccl;
@@ -524,9 +527,198 @@ int run_var_call(World& W, int code, int esz, const uint64_t* counts, const uint
   return 0;
 }
 
+// ---- point to point (kernels.hip p2p_kernel) ----
+// One wave of a launch: pair `pair` of the launch's argument on pipeline w, at operation i, slice s.
+struct P2pWave {
+  int pair, w, i;
+  uint64_t s, seq;
+  bool done = false;
+};
+
+struct P2pLaunch {
+  P2pArgs a;
+  std::vector<P2pWave> waves;
+};
+
+// the launch's waves as the kernel maps them (wave b: pair b / pipes, pipeline b % pipes); the self
+// copies happen at once (their waves wait for nobody)
+void p2p_start(World& W, int r, P2pLaunch& L) {
+  const P2pArgs& a = L.a;
+  for (int c = 0; c < a.nself; ++c) {
+    const int i = a.self_first + 2 * c;
+    memcpy((void*)(uintptr_t)a.ptr[i + 1], (const void*)(uintptr_t)a.ptr[i], (size_t)a.bytes[i]);
+  }
+  L.waves.clear();
+  for (int b = 0; b < a.npairs * a.pipes; ++b) {
+    P2pWave v;
+    v.pair = b / a.pipes;
+    v.w = b % a.pipes;
+    v.i = a.pair_first[v.pair];
+    v.s = (uint64_t)v.w;
+    const int peer = a.pair_peer[v.pair];
+    v.seq = (a.pair_send[v.pair] ? W.tx_seq : W.rx_seq)[r][(size_t)peer * W.C + v.w];
+    L.waves.push_back(v);
+  }
+}
+
+// One slice of one wave (or its end: the counter written back); false if its wait is unsatisfied.
+bool p2p_step(World& W, int r, const P2pArgs& a, P2pWave& v) {
+  const int peer = a.pair_peer[v.pair], w = v.w, K = W.K;
+  const bool sends = a.pair_send[v.pair] != 0;
+  const int last = a.pair_first[v.pair] + a.pair_count[v.pair];
+  for (;;) {
+    if (v.i >= last) {
+      (sends ? W.tx_seq : W.rx_seq)[r][(size_t)peer * W.C + w] = v.seq;
+      v.done = true;
+      return true;
+    }
+    const uint64_t bytes = a.bytes[v.i], nsl = p2p_nslices(bytes, W.slot_bytes);
+    const int A = p2p_msg_pipes(bytes, W.slot_bytes, a.p2p_pipes);
+    if (w >= A || v.s >= nsl) {  // the next operation of the pair
+      ++v.i;
+      v.s = (uint64_t)w;
+      continue;
+    }
+    const uint64_t len = slice_len(bytes, W.slot_bytes, v.s);
+    char* at = (char*)(uintptr_t)a.ptr[v.i] + v.s * W.slot_bytes;
+    if (sends) {
+      if (v.seq + 1 > (uint64_t)K && W.credit(r, peer, w) < v.seq + 1 - K) return false;
+      memcpy(W.slot(r, peer, w, v.seq), at, (size_t)len);
+      W.ready(peer, r, w) = ++v.seq;
+    } else {
+      if (W.ready(r, peer, w) < v.seq + 1) return false;
+      memcpy(at, W.slot(peer, r, w, v.seq), (size_t)len);
+      W.credit(peer, r, w) = ++v.seq;
+    }
+    v.s += (uint64_t)A;
+    return true;
+  }
+}
+
+// One point-to-point phase: rank r runs launches[r] one after another (stream order), the ranks
+// independently of each other.  0, -1 on no progress.
+int run_p2p_phase(World& W, std::vector<std::vector<P2pLaunch>>& launches, uint64_t schedule_seed, uint64_t& rng,
+                  uint64_t& steps) {
+  const int n = W.n;
+  std::vector<size_t> cur((size_t)n, 0);
+  for (int r = 0; r < n; ++r)
+    if (!launches[(size_t)r].empty()) p2p_start(W, r, launches[(size_t)r][0]);
+  for (;;) {
+    bool any = false, all_done = true;
+    const int r0 = schedule_seed ? (int)((rng >> 33) % (uint64_t)n) : 0;
+    for (int k = 0; k < n; ++k) {
+      const int r = (r0 + k) % n;
+      if (cur[(size_t)r] >= launches[(size_t)r].size()) continue;
+      all_done = false;
+      P2pLaunch& L = launches[(size_t)r][cur[(size_t)r]];
+      bool launch_done = true;
+      const size_t nw = L.waves.size();
+      const size_t w0 = schedule_seed && nw ? (size_t)((rng >> 20) % nw) : 0;
+      for (size_t j = 0; j < nw; ++j) {
+        P2pWave& v = L.waves[(w0 + j) % nw];
+        if (v.done) continue;
+        int burst = 1;
+        if (schedule_seed) {
+          rng = rng * 6364136223846793005ull + 1442695040888963407ull;
+          burst = 1 + (int)((rng >> 40) % 4);
+        }
+        for (int b = 0; b < burst && !v.done; ++b) {
+          if (!p2p_step(W, r, L.a, v)) break;
+          any = true;
+          ++steps;
+        }
+        launch_done = launch_done && v.done;
+      }
+      if (launch_done) {  // the kernel ended: the rank's next launch starts
+        any = true;
+        if (++cur[(size_t)r] < launches[(size_t)r].size()) p2p_start(W, r, launches[(size_t)r][cur[(size_t)r]]);
+      }
+    }
+    if (schedule_seed) rng = rng * 6364136223846793005ull + 1442695040888963407ull;
+    if (all_done) return 0;
+    if (!any) return -1;
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+// csrc/schedule.h point-to-point geometry, exported for the host-logic tests
+int mnccl_resident_cap(int waves, int cus, int most, int waves_per_simd) { return resident_cap(waves, cus, most, waves_per_simd); }
+int mnccl_p2p_pipes(int n, int channels, int cus, int most, int waves_per_simd) {
+  return p2p_pipes(n, channels, cus, most, waves_per_simd);
+}
+int mnccl_p2p_msg_pipes(uint64_t bytes, uint64_t slot_bytes, int pipes) { return p2p_msg_pipes(bytes, slot_bytes, pipes); }
+uint64_t mnccl_p2p_pipe_msgs(uint64_t bytes, uint64_t slot_bytes, int pipes, int w) {
+  return p2p_pipe_msgs(bytes, slot_bytes, pipes, w);
+}
+int mnccl_p2p_max_group_ops(void) { return kMaxGroupOps; }
+
+// Point-to-point groups between collectives on one simulated communicator state.  The run is a list
+// of phases: phase_coll[i] >= 0 is one collective call (schedule.h Coll 0..5 on schedule
+// phase_sched[i] over phase_count[i] elements, rank r's buffers csend / crecv[i * n + r], as
+// mnccl_sim_mixed; root 0), phase_coll[i] == -1 a point-to-point phase.  The operations of all
+// point-to-point phases are listed flat, sorted by (phase, rank, launch): operation k belongs to
+// launch op_launch[k] of rank op_rank[k] in phase op_phase[k] -- a launch is one group, or one
+// ungrouped call -- and is a send (op_send[k] != 0) or recv of op_bytes[k] bytes at op_ptr[k] with
+// peer op_peer[k].  Within a phase every rank runs its launches in order, independently of the other
+// ranks, each launch with kernels.hip p2p_kernel's wave-per-(pair, pipeline) mapping (p2p.h
+// p2p_build with `pipes` = schedule.h p2p_pipes) on the real slot / flag / counter layout.
+// counters_out (2 * n * n * channels words): every rank's tx then rx counters, [r][peer * channels + w].
+// Returns 0, -1 on no progress, -2 on bad arguments, -3 when a group fails p2p.h's checks.
+int mnccl_sim_p2p(int n, int channels, int slots, uint64_t slot_bytes, int pipes, int nphases, const int* phase_coll,
+                  const int* phase_sched, const uint64_t* phase_count, const float* const* csend, float* const* crecv,
+                  int op, int nops, const int* op_phase, const int* op_rank, const int* op_launch, const int* op_send,
+                  const int* op_peer, void* const* op_ptr, const uint64_t* op_bytes, uint64_t schedule_seed,
+                  uint64_t* counters_out, uint64_t* steps_out) {
+  if (n < 1 || n > 16 || channels < 1 || slots < 1 || slot_bytes < 4 || slot_bytes % 4 || nphases < 0 || nops < 0 ||
+      pipes < 1 || pipes > channels)
+    return -2;
+  World W;
+  init_world(W, n, channels, slots, op, slot_bytes);
+  uint64_t steps = 0;
+  uint64_t rng = schedule_seed * 6364136223846793005ull + 1442695040888963407ull;
+  int k = 0;
+  for (int ph = 0; ph < nphases; ++ph) {
+    if (phase_coll[ph] >= 0) {
+      const int c = phase_coll[ph];
+      if (c > kCollAllToAll || phase_count[ph] == 0) return -2;
+      const int rc = run_call(W, phase_sched[ph], c, phase_count[ph], csend + (size_t)ph * n, crecv + (size_t)ph * n,
+                              slot_bytes, 0, schedule_seed, rng, steps);
+      if (rc != 0) return rc;
+      continue;
+    }
+    std::vector<std::vector<P2pLaunch>> launches((size_t)n);
+    while (k < nops && op_phase[k] == ph) {
+      const int r = op_rank[k], l = op_launch[k];
+      if (r < 0 || r >= n) return -2;
+      P2pGroup g;
+      for (; k < nops && op_phase[k] == ph && op_rank[k] == r && op_launch[k] == l; ++k) {
+        if (op_bytes[k] == 0) continue;  // count == 0: nothing recorded
+        uint64_t bytes = 0;
+        if (p2p_check_op(g, n, op_send[k] != 0, op_peer[k], op_ptr[k], (size_t)op_bytes[k], 1, &bytes) != kP2pOk) return -3;
+        if (p2p_append(g, op_send[k] != 0, op_peer[k], op_ptr[k], (uint64_t)(uintptr_t)op_ptr[k], bytes) != kP2pOk) return -3;
+      }
+      P2pLaunch L;
+      if (p2p_build(g, r, pipes, slot_bytes, &L.a) != kP2pOk) return -3;
+      if (p2p_launch_waves(L.a) > 0) launches[(size_t)r].push_back(L);
+    }
+    const int rc = run_p2p_phase(W, launches, schedule_seed, rng, steps);
+    if (rc != 0) return rc;
+  }
+  if (k != nops) return -2;
+  if (counters_out) {
+    const size_t per = (size_t)n * channels;
+    for (int r = 0; r < n; ++r)
+      for (size_t j = 0; j < per; ++j) {
+        counters_out[(size_t)r * per + j] = W.tx_seq[r][j];
+        counters_out[(size_t)n * per + (size_t)r * per + j] = W.rx_seq[r][j];
+      }
+  }
+  if (steps_out) *steps_out = steps;
+  return 0;
+}
 
 // csrc/schedule.h one-shot geometry, exported for the host-logic tests
 uint64_t mnccl_oneshot_slice(uint64_t chunk_bytes, int n, int channels, uint64_t slot_bytes) {

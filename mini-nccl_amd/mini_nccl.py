@@ -85,6 +85,10 @@ SIGNATURES = {
     "ncclAllToAll": (_I, [_VP, _VP, _SZ, _I, _VP, _VP]),
     "ncclAllToAllv": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ),
                            _I, _VP, _VP]),
+    "ncclSend": (_I, [_VP, _SZ, _I, _I, _VP, _VP]),
+    "ncclRecv": (_I, [_VP, _SZ, _I, _I, _VP, _VP]),
+    "ncclGroupStart": (_I, []),
+    "ncclGroupEnd": (_I, []),
     "mncclLocalReduce": (_I, [_VP, _VP, _VP, _SZ, _I, _I, _VP]),
     "mncclCommGetAsyncError": (_I, [_VP, ctypes.POINTER(_I)]),
     "mncclCommGetInfo": (_I, [_VP, ctypes.POINTER(CommInfo)]),
@@ -178,6 +182,16 @@ class Comm:
         return load().ncclAllToAllv(send_ptr, arrays[0], arrays[1], recv_ptr, arrays[2], arrays[3], dtype, self.handle,
                                     stream)
 
+    def send(self, send_ptr, count, dtype=ncclFloat, peer=0, stream=0):
+        """ncclSend: `count` elements to rank `peer`; inside a group (group_start / group) it is only
+        recorded.  Returns the ncclResult_t."""
+        return load().ncclSend(send_ptr, count, dtype, peer, self.handle, stream)
+
+    def recv(self, recv_ptr, count, dtype=ncclFloat, peer=0, stream=0):
+        """ncclRecv: `count` elements from rank `peer`, matching its sends to this rank in call order.
+        Returns the ncclResult_t."""
+        return load().ncclRecv(recv_ptr, count, dtype, peer, self.handle, stream)
+
     def rank(self):
         r = ctypes.c_int()
         check(load().ncclCommUserRank(self.handle, ctypes.byref(r)))
@@ -240,6 +254,33 @@ class Comm:
             self.handle = ctypes.c_void_p()
             return code
         return ncclSuccess
+
+
+def group_start():
+    """ncclGroupStart: open (or nest) this thread's group.  Returns the ncclResult_t."""
+    return load().ncclGroupStart()
+
+
+def group_end():
+    """ncclGroupEnd: the outermost one launches every recorded send / recv as one kernel launch.
+    Returns the ncclResult_t (the group's first error, if an operation failed)."""
+    return load().ncclGroupEnd()
+
+
+class group:
+    """``with mini_nccl.group() as g: comm.send(...); comm.recv(...)`` -- ncclGroupStart on entry,
+    ncclGroupEnd on exit; ``g.rc`` is ncclGroupEnd's ncclResult_t (nothing raises)."""
+
+    def __init__(self):
+        self.rc = None
+
+    def __enter__(self):
+        group_start()
+        return self
+
+    def __exit__(self, *exc):
+        self.rc = group_end()
+        return False
 
 
 def local_reduce(out_ptr, local_ptr, incoming_ptr, count, dtype=ncclFloat, op=ncclSum, stream=0):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Times ncclReduceScatter, ncclAllGather, ncclBroadcast, ncclReduce, ncclAllToAll and ncclAllToAllv
-beside ncclAllReduce on one communicator.
+"""Times ncclReduceScatter, ncclAllGather, ncclBroadcast, ncclReduce, ncclAllToAll, ncclAllToAllv and
+grouped ncclSend / ncclRecv beside ncclAllReduce on one communicator.
 
     python tools/coll_bench.py --gpus 4 [--same-device] [--bytes N] [--rounds R] [--calls K] [--warmup W]
                                [--kinds all_reduce,reduce_scatter,...]
@@ -22,6 +22,14 @@ persistent form (mncclAlgoRead), fp32 Sum, stream-ordered (MINI_NCCL_BLOCKING=0)
     all_to_all_v_skew  ncclAllToAllv on a skewed matrix from a seeded generator (--skew-seed: each
                     pair's block is 0, 1/20, 1/4, 1/2 or 1 chunk, contiguous displacements), reported
                     as skew_moved_bytes (every block, the own ones included) and skew_moved_GBps
+    all_to_all_ring    all_to_all forced onto the ring (mncclAlgoRing): the scratch protocol the
+                    point-to-point calls run, as a collective
+    p2p_neighbor    group{ncclSend -> r + 1, ncclRecv <- r - 1} of all n chunks: a bidirectional
+                    neighbour exchange, `bytes` out and `bytes` in per rank
+    p2p_all_pairs   one group of n - 1 sends (chunk q to rank q) and n - 1 recvs (chunk q from rank q):
+                    the all-to-all without its own block, through the peers' scratch
+                    (both p2p rows also as p2p_sent_GBps: the bytes a rank sends over the time; no
+                    threshold is set on them -- ratios p2p_all_pairs_over_all_to_all[_ring] beside)
 
 (broadcast: every rank loads one chunk of the root's send and stores it into all n recvs; reduce:
 every rank loads its chunk from all n sends and stores it into the root's recv -- on the one-GPU
@@ -53,7 +61,7 @@ for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "mini-nccl_amd")):
         sys.path.insert(0, p)
 
 KINDS = ("all_reduce", "reduce_scatter", "all_gather", "broadcast", "reduce", "all_to_all", "all_to_all_v",
-         "all_to_all_v_skew")
+         "all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs")
 
 
 def skew_matrix(n, chunk, seed):
@@ -72,6 +80,26 @@ def v_call(M, comm, send, recv, C, rank, stream):
     args = (arr(sc), arr(starts(sc)), arr(rc), arr(starts(rc)))
     f = M.load().ncclAllToAllv
     return lambda: f(send, args[0], args[1], recv, args[2], args[3], M.ncclFloat, comm.handle, stream)
+
+
+def p2p_call(M, comm, ops, stream):
+    """One group of (send?, pointer, elements, peer) operations, fp32; the group's result code."""
+    L = M.load()
+    def run():
+        L.ncclGroupStart()
+        for send, ptr, count, peer in ops:
+            (L.ncclSend if send else L.ncclRecv)(ptr, count, M.ncclFloat, peer, comm.handle, stream)
+        return L.ncclGroupEnd()
+    return run
+
+
+def ring_all_to_all(M, comm, send, recv, chunk, stream):
+    def run():
+        comm.set_algo(M.ALGO_RING)
+        rc = comm.all_to_all(send, recv, chunk, M.ncclFloat, stream)
+        comm.set_algo(M.ALGO_READ)
+        return rc
+    return run
 
 
 def rank_main(a):
@@ -101,6 +129,11 @@ def rank_main(a):
         "all_to_all_v": v_call(M, comm, big_a.ptr, big_b.ptr, [[chunk] * n] * n, a.rank, st.handle),
         "all_to_all_v_skew": v_call(M, comm, big_a.ptr, big_b.ptr, skew_matrix(n, chunk, a.skew_seed).tolist(), a.rank,
                                     st.handle),
+        "all_to_all_ring": ring_all_to_all(M, comm, big_a.ptr, big_b.ptr, chunk, st.handle),
+        "p2p_neighbor": p2p_call(M, comm, [(True, big_a.ptr, n * chunk, (a.rank + 1) % n),
+                                           (False, big_b.ptr, n * chunk, (a.rank - 1) % n)], st.handle),
+        "p2p_all_pairs": p2p_call(M, comm, [(True, big_a.ptr + 4 * chunk * q, chunk, q) for q in range(n) if q != a.rank] +
+                                  [(False, big_b.ptr + 4 * chunk * q, chunk, q) for q in range(n) if q != a.rank], st.handle),
     }
     kinds = tuple(a.kinds.split(","))
     e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
@@ -197,7 +230,7 @@ def main():
         "ms": {k: round(v, 4) for k, v in med.items()},
         "rounds_ms": {k: [round(x, 4) for x in v] for k, v in rounds.items()},
         "hbm_bytes": {k: (2 * n if k in ("all_reduce", "all_to_all", "all_to_all_v") else n + 1) * chunk_bytes
-                      for k in kinds if k != "all_to_all_v_skew"},
+                      for k in kinds if k not in ("all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs")},
         "ratio": dict([(f"{k}_over_all_reduce", round(med[k] / med["all_reduce"], 4)) for k in kinds if k != "all_reduce"] +
                       [(f"{k}_over_{y}", round(med[k] / med[y], 4))
                        for k, y in (("reduce", "reduce_scatter"), ("broadcast", "all_gather"), ("all_to_all", "all_gather"))
@@ -214,6 +247,15 @@ def main():
         moved = int(skew_matrix(n, chunk_bytes // 4, a.skew_seed).sum()) * 4  # over all ranks, own blocks included
         res["skew_seed"], res["skew_moved_bytes"] = a.skew_seed, moved
         res["skew_moved_GBps"] = round(moved / (med["all_to_all_v_skew"] * 1e-3) / 1e9, 2)
+    # the point-to-point rows: the bytes one rank sends over the time, and the all-pairs group beside
+    # the all-to-all on both schedules (one-GPU proxy numbers when co-located; no threshold)
+    sent = {"p2p_neighbor": n * chunk_bytes, "p2p_all_pairs": (n - 1) * chunk_bytes}
+    p2p = {k: round(sent[k] / (med[k] * 1e-3) / 1e9, 2) for k in sent if k in med}
+    if p2p:
+        res["p2p_sent_GBps"] = p2p
+    for y in ("all_to_all", "all_to_all_ring"):
+        if "p2p_all_pairs" in med and y in med:
+            res["ratio"][f"p2p_all_pairs_over_{y}"] = round(med["p2p_all_pairs"] / med[y], 4)
     if "all_gather" in rounds:
         res["all_gather_spread"] = round((max(rounds["all_gather"]) - min(rounds["all_gather"])) / med["all_gather"], 4)
     print(json.dumps(res))
