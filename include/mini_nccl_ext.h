@@ -44,6 +44,11 @@
  *                        rendezvous: two ranks exchange while the others do nothing.
  *   ncclGroupStart / ncclGroupEnd   several sends and recvs as one launch in which all progress
  *                        concurrently.
+ *
+ * and NCCL's user-created reduction op (gradient averaging, a loss scale folded into the reduction):
+ *
+ *   ncclRedOpCreatePreMulSum / ncclRedOpDestroy   a sum whose inputs are multiplied by one scalar on
+ *                        their way into the fold, inside the reducing kernels.
  */
 #ifndef MINI_NCCL_EXT_H_
 #define MINI_NCCL_EXT_H_
@@ -75,7 +80,8 @@ extern "C" {
    without a change to anything above -- a caller detects them by symbol; still 600: ncclBroadcast
    and ncclReduce were added the same way; still 600: ncclAllToAll was added the same way; still 600:
    ncclAllToAllv was added the same way (detected by symbol); still 600: ncclSend, ncclRecv,
-   ncclGroupStart and ncclGroupEnd were added the same way */
+   ncclGroupStart and ncclGroupEnd were added the same way; still 600: ncclRedOpCreatePreMulSum and
+   ncclRedOpDestroy were added the same way */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -378,6 +384,61 @@ ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int
                       hipStream_t stream);
 ncclResult_t ncclGroupStart(void);
 ncclResult_t ncclGroupEnd(void);
+
+/* Pre-multiplied sums (NCCL's ncclRedOpCreatePreMulSum / ncclRedOpDestroy: names, argument order and
+ * enum values are NCCL's; detected by symbol, MNCCL_VERSION stays 600).  ncclAvg itself is still
+ * rejected with ncclInternalError; an op created with the scalar 1 / nranks is its replacement.
+ *
+ * ncclRedOpCreatePreMulSum creates a reduction op of `comm` that ncclAllReduce, ncclReduceScatter and
+ * ncclReduce accept wherever they accept ncclSum.  *scalar is ONE value of `datatype`, read on the
+ * host before the call returns (ncclScalarHostImmediate, the only residence supported:
+ * ncclScalarDevice is ncclInvalidUsage).  The handle written to *op is a value >= MNCCL_FIRST_USER_OP
+ * that belongs to this communicator; at most 16 are live per communicator, and a destroyed handle's
+ * value may be handed out again.  The scalar travels to the kernels BY VALUE in the launch arguments:
+ * the op may be destroyed as soon as the last call using it has been issued -- with
+ * MINI_NCCL_BLOCKING=0 before the call has run, and for a call captured into a HIP graph before the
+ * graph is replayed.  mncclLocalReduce has no communicator and accepts the four built-in ops only.
+ *
+ * Result, bit for bit.  With s the scalar, every rank's input element x first becomes
+ * y = round(s * x), ONE correctly rounded multiplication in the datatype's arithmetic: the IEEE
+ * product for ncclFloat and ncclDouble; for ncclFloat16 and ncclBfloat16 the product, which is exact
+ * in float, rounded to nearest even into the type; two's-complement wrap for ncclInt32.  The y are
+ * then reduced exactly as ncclSum reduces them -- for chunk c, acc = y_c, then acc = y_q + acc for
+ * q = c+1 ... c-1 (mod nranks) -- so the call equals the ncclSum call on buffers scaled beforehand,
+ * on every schedule; the product and the sum are two roundings, never a fused multiply-add.  Two
+ * things follow from the definition: ncclAllReduce's unreduced tail (count % nranks elements) keeps
+ * the rank's own input UNSCALED, as it is outside the reduction; and with nranks == 1 the call is no
+ * plain copy: recv = round(s * send) over all `count` elements, in place or not.
+ *
+ * THE SCALAR MUST BE THE SAME ON EVERY RANK.  NCCL permits a scalar per rank; this library does not:
+ * on the read schedule rank c multiplies its peers' inputs with its own copy of the scalar.  Ranks
+ * are compared by the op's kind and the scalar's bits, never by the handle's value, so they may
+ * create their ops in different orders.  Wherever a call is negotiated (the read schedule's
+ * rendezvous, ncclReduce's included) a difference is ncclInvalidUsage on every rank with nothing
+ * written and the communicator still usable; on registered windows launched without a rendezvous the
+ * scalar is part of the signature the kernels compare, with the consequences documented at
+ * mncclCommRegister (ncclInvalidUsage on every rank, the communicator no longer usable).  The forced
+ * ring negotiates nothing and cannot see a difference.
+ *
+ * Schedules.  The ring, the persistent read kernels, the grid form and the registered-window launch
+ * apply the scale inside their folds: no extra pass over the buffer.  The one-shot schedule has no
+ * form for these ops: a call that mncclAlgoAuto or a forced mncclAlgoOneShot would run one-shot runs
+ * as a call the one-shot does not fit -- the read schedule where every rank can share its buffers,
+ * else the ring -- and mncclCommInfo_t.last_algo reports what ran.
+ *
+ * Checks of ncclRedOpCreatePreMulSum, in this order: NULL comm, op or scalar: ncclInvalidArgument;
+ * an unsupported datatype: ncclInternalError; the communicator's sticky error is returned;
+ * ncclScalarDevice (or any other residence): ncclInvalidUsage; a 17th live op: ncclInvalidUsage.
+ * ncclRedOpDestroy: NULL comm: ncclInvalidArgument; a built-in or unknown handle: ncclInvalidArgument.
+ * In a collective: ops 0 - 4 are checked as before, before the communicator is read; a value from
+ * MNCCL_FIRST_USER_OP up is looked up in the communicator: an unknown handle is ncclInternalError
+ * like any unsupported op, a handle created for another datatype ncclInvalidArgument, nothing
+ * launched or negotiated.  No exception crosses the boundary. */
+typedef enum { ncclScalarDevice = 0, ncclScalarHostImmediate = 1 } ncclScalarResidence_t;
+#define MNCCL_FIRST_USER_OP 5
+ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataType_t datatype,
+                                      ncclScalarResidence_t residence, ncclComm_t comm);
+ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm);
 
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream);

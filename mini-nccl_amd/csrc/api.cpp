@@ -34,6 +34,29 @@ bool dtype_ok(ncclDataType_t t) {
 }
 bool op_ok(ncclRedOp_t op) { return op == ncclSum || op == ncclProd || op == ncclMax || op == ncclMin; }
 
+// The op of a collective that folds, after its datatype was found supported.  The four built-ins as
+// they are and ncclAvg refused, both before the communicator is read; a value from
+// MNCCL_FIRST_USER_OP up is looked up in the communicator: a handle of ncclRedOpCreatePreMulSum
+// becomes kPreMulSum with its scalar's bits, an unknown one is ncclInternalError like any unsupported
+// op, one created for another datatype ncclInvalidArgument.
+ncclResult_t resolve_op(const char* what, const Comm* c, ncclDataType_t datatype, ncclRedOp_t op, int* kop,
+                        uint64_t* scalar) {
+  *scalar = 0;
+  *kop = (int)op;
+  if (op_ok(op)) return ncclSuccess;
+  int made_for = 0;
+  if ((int)op < MNCCL_FIRST_USER_OP || !c->redop_find((int)op, &made_for, scalar)) {
+    fprintf(stderr, "[Mini-NCCL] %s Internal Error: unsupported RedOp\n", what);
+    return ncclInternalError;
+  }
+  if (made_for != (int)datatype) {
+    fprintf(stderr, "[Mini-NCCL] %s: the op was created for another datatype\n", what);
+    return ncclInvalidArgument;
+  }
+  *kop = mnccl::kPreMulSum;
+  return ncclSuccess;
+}
+
 // ncclGroupStart / ncclGroupEnd: the group being recorded, one per thread (ranks may run as threads
 // of one process).  Groups nest by a depth counter; the outermost ncclGroupEnd launches.  The first
 // error of an operation poisons the group: ncclGroupEnd returns it and launches nothing.
@@ -121,13 +144,17 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
   if (count == 0) return ncclSuccess;                               // api.cpp:140
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclAllReduce");
-  if (!dtype_ok(datatype) || !op_ok(op)) {
+  if (!dtype_ok(datatype)) {
     // the reference throws inside get_type_size / to_internal_op -> ncclInternalError (:182-185)
-    fprintf(stderr, "[Mini-NCCL] AllReduce Internal Error: unsupported %s\n", dtype_ok(datatype) ? "RedOp" : "DataType");
+    fprintf(stderr, "[Mini-NCCL] AllReduce Internal Error: unsupported DataType\n");
     return ncclInternalError;
   }
+  int kop = 0;
+  uint64_t scalar = 0;
+  const ncclResult_t orc = resolve_op("AllReduce", reinterpret_cast<const Comm*>(comm), datatype, op, &kop, &scalar);
+  if (orc != ncclSuccess) return orc;
   try {
-    return reinterpret_cast<Comm*>(comm)->allreduce(sendbuff, recvbuff, count, (int)datatype, (int)op, stream);
+    return reinterpret_cast<Comm*>(comm)->allreduce(sendbuff, recvbuff, count, (int)datatype, kop, stream, scalar);
   } catch (const std::exception& e) {
     fprintf(stderr, "[Mini-NCCL] AllReduce Internal Error: %s\n", e.what());
     return ncclInternalError;
@@ -145,12 +172,16 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
   if (recvcount == 0) return ncclSuccess;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclReduceScatter");
-  if (!dtype_ok(datatype) || !op_ok(op)) {
-    fprintf(stderr, "[Mini-NCCL] ReduceScatter Internal Error: unsupported %s\n", dtype_ok(datatype) ? "RedOp" : "DataType");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] ReduceScatter Internal Error: unsupported DataType\n");
     return ncclInternalError;
   }
+  int kop = 0;
+  uint64_t scalar = 0;
+  const ncclResult_t orc = resolve_op("ReduceScatter", reinterpret_cast<const Comm*>(comm), datatype, op, &kop, &scalar);
+  if (orc != ncclSuccess) return orc;
   try {
-    return reinterpret_cast<Comm*>(comm)->reduce_scatter(sendbuff, recvbuff, recvcount, (int)datatype, (int)op, stream);
+    return reinterpret_cast<Comm*>(comm)->reduce_scatter(sendbuff, recvbuff, recvcount, (int)datatype, kop, stream, scalar);
   } catch (const std::exception& e) {
     fprintf(stderr, "[Mini-NCCL] ReduceScatter Internal Error: %s\n", e.what());
     return ncclInternalError;
@@ -208,12 +239,16 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
   if (count == 0) return ncclSuccess;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclReduce");
-  if (!dtype_ok(datatype) || !op_ok(op)) {
-    fprintf(stderr, "[Mini-NCCL] Reduce Internal Error: unsupported %s\n", dtype_ok(datatype) ? "RedOp" : "DataType");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] Reduce Internal Error: unsupported DataType\n");
     return ncclInternalError;
   }
+  int kop = 0;
+  uint64_t scalar = 0;
+  const ncclResult_t orc = resolve_op("Reduce", reinterpret_cast<const Comm*>(comm), datatype, op, &kop, &scalar);
+  if (orc != ncclSuccess) return orc;
   try {
-    return reinterpret_cast<Comm*>(comm)->reduce(sendbuff, recvbuff, count, (int)datatype, (int)op, root, stream);
+    return reinterpret_cast<Comm*>(comm)->reduce(sendbuff, recvbuff, count, (int)datatype, kop, root, stream, scalar);
   } catch (const std::exception& e) {
     fprintf(stderr, "[Mini-NCCL] Reduce Internal Error: %s\n", e.what());
     return ncclInternalError;
@@ -343,6 +378,35 @@ ncclResult_t ncclGroupEnd(void) {
   } catch (...) {
     return ncclSystemError;
   }
+}
+
+// User-created reduction ops (mini_nccl_ext.h): the checks in the header's order.  The scalar is read
+// here, on the host, before the call returns.
+ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataType_t datatype,
+                                      ncclScalarResidence_t residence, ncclComm_t comm) {
+  if (!comm || !op || !scalar) return ncclInvalidArgument;
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] RedOpCreatePreMulSum Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  Comm* c = reinterpret_cast<Comm*>(comm);
+  if (c->sticky_error() != ncclSuccess) return c->sticky_error();
+  if (residence != ncclScalarHostImmediate) {
+    fprintf(stderr, "[Mini-NCCL] ncclRedOpCreatePreMulSum: only ncclScalarHostImmediate is supported (the scalar travels "
+            "to the kernels by value)\n");
+    return ncclInvalidUsage;
+  }
+  uint64_t bits = 0;
+  memcpy(&bits, scalar, (size_t)mnccl::dtype_size((int)datatype));  // (little-endian: the low bytes)
+  int h = 0;
+  const ncclResult_t rc = c->redop_create(&h, (int)datatype, bits);
+  if (rc == ncclSuccess) *op = (ncclRedOp_t)h;
+  return rc;
+}
+
+ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm) {
+  if (!comm) return ncclInvalidArgument;
+  return reinterpret_cast<Comm*>(comm)->redop_destroy((int)op);
 }
 
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,

@@ -599,10 +599,11 @@ static int persistent_kernel(int algo, int coll) {
 
 void Comm::launch(int algo, const void* send, void* recv, size_t chunk_bytes, int dtype, int op, hipStream_t stream,
                   uint32_t seq, bool vec, const char* const* psend, const char* const* precv,
-                  size_t tail_bytes, uint64_t sig, int coll, int root, size_t total_bytes) {
+                  size_t tail_bytes, uint64_t sig, int coll, int root, size_t total_bytes, uint64_t scalar) {
   int A = 0;
-  const CollParams p = make_params(algo, send, recv, chunk_bytes, seq, psend, precv, tail_bytes, sig, coll, root,
-                                   total_bytes, &A);
+  CollParams p = make_params(algo, send, recv, chunk_bytes, seq, psend, precv, tail_bytes, sig, coll, root,
+                             total_bytes, &A);
+  p.scale = op == kPreMulSum ? scalar : 0;  // by value: the op may be destroyed once the call is issued
   const int n = nranks_;
   const int nt = cfg_.threads, wg = A / geo_.waves;
   // mncclAlgoReadGrid: the push form's large calls as start / grid fold / done (the same on every
@@ -682,7 +683,7 @@ CollParams Comm::make_params(int algo, const void* send, void* recv, size_t chun
 // n * count elements, the other buffer one chunk of `count`.  ncclAllToAll (coll 5): both buffers
 // hold n blocks of `count` elements, and a chunk is one block.
 ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
-                              hipStream_t stream, int root) {
+                              hipStream_t stream, int root, uint64_t scalar) {
   if (sticky_ != ncclSuccess) return sticky_;
   if (check_status() != ncclSuccess) return sticky_;
   const int esz = dtype_size(dtype);
@@ -762,7 +763,10 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
   const size_t chunk_bytes = chunk * (size_t)esz;
   if (n == 1 || chunk == 0) {
     // nRanks == 1 returns after the copy (mini_nccl.cu:66); chunk == 0 moves no slice
-    if (send != recv) hip_check(hipMemcpyAsync(recv, send, bytes, hipMemcpyDefault, stream), "copy");
+    // (kPreMulSum on one rank is no copy: every element is scaled; with chunk == 0 on more ranks the
+    // whole all-reduce is its unreduced tail, which keeps the raw input)
+    if (n == 1 && op == kPreMulSum) scale_one_rank(send, recv, count, dtype, scalar, scope, stream);
+    else if (send != recv) hip_check(hipMemcpyAsync(recv, send, bytes, hipMemcpyDefault, stream), "copy");
   } else {
     const size_t mine = (size_t)rank_ * chunk_bytes;  // a half's chunk of this rank in the larger buffer
     // Where the kernel reads and writes: device memory as is; pinned / registered host
@@ -782,8 +786,12 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // function of the call's size and the rank-uniform config up to the read rendezvous, which
     // all ranks decide alike.
     // (the halves have no one-shot form: read where an all-reduce's larger calls would, else the ring)
-    const bool oneshot = !half && !rooted && !a2a && algo_ == 3 && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), true);
-    const bool small = !half && !rooted && !a2a && auto_ && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), false);
+    // (nor has a pre-multiplied sum: the one-shot kernel folds the four built-in ops only, so such a
+    // call is one the one-shot does not fit -- the read schedule where it can run, else the ring; the
+    // op's kind is the same on every rank, like the call's size)
+    const bool os_form = !half && !rooted && !a2a && op != kPreMulSum;
+    const bool oneshot = os_form && algo_ == 3 && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), true);
+    const bool small = os_form && auto_ && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), false);
     // (auto, and a forced one-shot's larger calls, only where the topology allows the read
     // schedule: classify_topology; MINI_NCCL_ALGO=read forces it anywhere)
     const bool read_sched = !oneshot &&
@@ -808,7 +816,10 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       // (FNV-1a over the words)
       uint64_t sig = 1469598103934665603ull;
       const uint64_t mode = auto_ ? ~0ull : (uint64_t)algo_;
-      for (uint64_t v : {win_s->id, os, win_r->id, orv, (uint64_t)count, (uint64_t)dtype, (uint64_t)op, mode})
+      // (a kPreMulSum op by its kind and its scalar's bits, never by its handle: ranks may create
+      // their ops in different orders; for the built-in ops the scalar is 0)
+      const uint64_t sbits = op == kPreMulSum ? scalar : 0;
+      for (uint64_t v : {win_s->id, os, win_r->id, orv, (uint64_t)count, (uint64_t)dtype, (uint64_t)op, mode, sbits})
         for (int b = 0; b < 8; ++b) sig = (sig ^ ((v >> (8 * b)) & 0xff)) * 1099511628211ull;
       sig |= 1;  // never 0 (0 = a negotiated call)
       try {
@@ -823,7 +834,8 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       const size_t tail = send != recv && bytes > body ? bytes - body : 0;
       seq = ++call_seq_;
       if (seq == 0) seq = ++call_seq_;
-      launch(2, send, recv, chunk_bytes, dtype, op, stream, seq, vec_w, psend, precv, tail, sig);
+      launch(2, send, recv, chunk_bytes, dtype, op, stream, seq, vec_w, psend, precv, tail, sig, kCollAllReduce, 0, 0,
+             scalar);
       ++window_calls_;
       return end_call(scope, stream, seq);
     }
@@ -886,7 +898,11 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
                             // (and a rooted one's root: ranks that differ in it get kMismatch too)
                             half || rooted || a2a ? ((auto_ ? 0xff : algo_) | coll << 8 | (rooted ? root << 16 : 0))
                             : auto_        ? -1
-                                           : algo_);
+                                           : algo_,
+                            nullptr, nullptr,
+                            // (a kPreMulSum op is compared by its kind and its scalar's bits, never by
+                            // its handle: ranks that differ in the scalar get kMismatch)
+                            op == kPreMulSum ? scalar : 0);
       } catch (const PeerGaveUp& e) {
         return rendezvous_failed(e, true, cur_dev);
       } catch (const std::exception& e) {
@@ -902,8 +918,9 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
         return sticky_;
       }
       if (d == PeerBuffers::kMismatch) {
-        fprintf(stderr, "[Mini-NCCL] rank %d: ranks called %s with different count / datatype / op / schedule "
-                "(mncclCommSetAlgo), different collectives, or a different root\n", rank_, coll_name);
+        fprintf(stderr, "[Mini-NCCL] rank %d: ranks called %s with different count / datatype / op (or a different "
+                "ncclRedOpCreatePreMulSum scalar) / schedule (mncclCommSetAlgo), different collectives, or a different "
+                "root\n", rank_, coll_name);
         if (cur_dev != device_) hipSetDevice(cur_dev);
         return ncclInvalidUsage;
       }
@@ -928,13 +945,62 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       hip_check(hipMemcpyAsync((char*)krecv + mine, (const char*)ksend + mine, chunk_bytes, hipMemcpyDefault, stream),
                 "own block");
     launch(algo, ksend, krecv, chunk_bytes, dtype, op, stream, seq, vec, psend, precv, tail, 0, coll, root,
-           rooted ? bytes : 0);
+           rooted ? bytes : 0, scalar);
     // (Reduce: only the root's recv is written -- the others' stands for their send)
     if (rr == Reach::kStaged && (coll != kCollReduce || is_root))
       hip_check(hipMemcpyAsync(recv, krecv, coll == kCollReduceScatter ? chunk_bytes : bytes, hipMemcpyDefault, stream),
                 "stage out");
   }
   return end_call(scope, stream, seq);
+}
+
+// One rank, kPreMulSum: the buffers as the kernels reach them (device memory as is, pinned host
+// memory through its mapping, pageable host memory through the stage), one launch of the scale kernel.
+void Comm::scale_one_rank(const void* send, void* recv, size_t count, int dtype, uint64_t scalar, const CallScope& sc,
+                          hipStream_t stream) {
+  const size_t bytes = count * (size_t)dtype_size(dtype);
+  const void* ksend = send;
+  void* krecv = recv;
+  bool local = false;
+  const Reach rs = reach(send, &ksend, &local), rr = reach(recv, (const void**)&krecv, &local);
+  if (rs == Reach::kStaged || rr == Reach::kStaged) {
+    if (sc.capturing()) throw std::runtime_error("pageable host buffers cannot be captured into a HIP graph");
+    ensure_stage(bytes, stream);
+    if (rs == Reach::kStaged) {
+      hip_check(hipMemcpyAsync(stage_, send, bytes, hipMemcpyDefault, stream), "stage in");
+      ksend = stage_;
+    }
+    if (rr == Reach::kStaged) krecv = stage_;
+  }
+  hip_check(launch_scale(dtype, krecv, ksend, count, scalar, stream), "scale kernel");
+  if (rr == Reach::kStaged) hip_check(hipMemcpyAsync(recv, krecv, bytes, hipMemcpyDefault, stream), "stage out");
+}
+
+ncclResult_t Comm::redop_create(int* op, int dtype, uint64_t scalar) {
+  for (int i = 0; i < kMaxUserOps; ++i)
+    if (!user_ops_[i].live) {
+      user_ops_[i].live = true;
+      user_ops_[i].dtype = dtype;
+      user_ops_[i].scalar = scalar;
+      *op = kFirstUserOp + i;
+      return ncclSuccess;
+    }
+  fprintf(stderr, "[Mini-NCCL] rank %d: ncclRedOpCreatePreMulSum: %d ops are live on this communicator already\n", rank_,
+          kMaxUserOps);
+  return ncclInvalidUsage;
+}
+
+ncclResult_t Comm::redop_destroy(int op) {
+  if (op < kFirstUserOp || op >= kFirstUserOp + kMaxUserOps || !user_ops_[op - kFirstUserOp].live) return ncclInvalidArgument;
+  user_ops_[op - kFirstUserOp].live = false;
+  return ncclSuccess;
+}
+
+bool Comm::redop_find(int op, int* dtype, uint64_t* scalar) const {
+  if (op < kFirstUserOp || op >= kFirstUserOp + kMaxUserOps || !user_ops_[op - kFirstUserOp].live) return false;
+  *dtype = user_ops_[op - kFirstUserOp].dtype;
+  *scalar = user_ops_[op - kFirstUserOp].scalar;
+  return true;
 }
 
 Comm::CallScope Comm::begin_call(hipStream_t stream) {

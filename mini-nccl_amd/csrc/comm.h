@@ -28,8 +28,11 @@ class Comm {
   Comm& operator=(const Comm&) = delete;
 
   // The hot path: returns an ncclResult_t; throws only on HIP runtime errors.
-  ncclResult_t allreduce(const void* send, void* recv, size_t count, int dtype, int op, hipStream_t stream) {
-    return collective(kCollAllReduce, send, recv, count, dtype, op, stream);
+  // op: one of the four built-ins, or kPreMulSum with `scalar` the bits of the op's scalar (api.cpp
+  // resolves a handle of redop_create before it calls; also reduce_scatter and reduce below)
+  ncclResult_t allreduce(const void* send, void* recv, size_t count, int dtype, int op, hipStream_t stream,
+                         uint64_t scalar = 0) {
+    return collective(kCollAllReduce, send, recv, count, dtype, op, stream, 0, scalar);
   }
   // The all-reduce's two halves (NCCL's ncclReduceScatter / ncclAllGather; `count` per rank): send
   // holds n * count elements and recv gets chunk `rank` of their all-reduce, bit for bit; recv holds
@@ -37,8 +40,9 @@ class Comm {
   // (kernels.hip scatter_fold / gather_push) where an all-reduce would run it, else the ring's
   // halves (schedule.h coll_op); no one-shot, no grid form, no registered windows.  In place as
   // NCCL defines it; any other overlap of the two buffers is ncclInvalidArgument.
-  ncclResult_t reduce_scatter(const void* send, void* recv, size_t count, int dtype, int op, hipStream_t stream) {
-    return collective(kCollReduceScatter, send, recv, count, dtype, op, stream);
+  ncclResult_t reduce_scatter(const void* send, void* recv, size_t count, int dtype, int op, hipStream_t stream,
+                              uint64_t scalar = 0) {
+    return collective(kCollReduceScatter, send, recv, count, dtype, op, stream, 0, scalar);
   }
   ncclResult_t all_gather(const void* send, void* recv, size_t count, int dtype, hipStream_t stream) {
     return collective(kCollAllGather, send, recv, count, dtype, kSum, stream);
@@ -54,9 +58,22 @@ class Comm {
   ncclResult_t broadcast(const void* send, void* recv, size_t count, int dtype, int root, hipStream_t stream) {
     return collective(kCollBroadcast, send, recv, count, dtype, kSum, stream, root);
   }
-  ncclResult_t reduce(const void* send, void* recv, size_t count, int dtype, int op, int root, hipStream_t stream) {
-    return collective(kCollReduce, send, recv, count, dtype, op, stream, root);
+  ncclResult_t reduce(const void* send, void* recv, size_t count, int dtype, int op, int root, hipStream_t stream,
+                      uint64_t scalar = 0) {
+    return collective(kCollReduce, send, recv, count, dtype, op, stream, root, scalar);
   }
+
+  // User-created reduction ops (NCCL's ncclRedOpCreatePreMulSum / ncclRedOpDestroy): a handle is
+  // kFirstUserOp + a slot of this communicator's table, at most kMaxUserOps live, a destroyed slot
+  // handed out again.  A slot keeps the datatype the op was created for and the scalar's bits; a
+  // call copies the bits into its kernel argument, so the op may be destroyed once the call is
+  // issued.  redop_create: ncclInvalidUsage when the table is full.  redop_destroy: ncclInvalidArgument
+  // for a built-in or unknown handle.  redop_find: false for an unknown handle.
+  static constexpr int kFirstUserOp = 5, kMaxUserOps = 16;
+  ncclResult_t redop_create(int* op, int dtype, uint64_t scalar);
+  ncclResult_t redop_destroy(int op);
+  bool redop_find(int op, int* dtype, uint64_t* scalar) const;
+  ncclResult_t sticky_error() const { return sticky_; }
 
   // The all-to-all (RCCL's ncclAllToAll; `count` elements per block, n blocks in both buffers):
   // block q of this rank's send becomes block `rank` of rank q's recv, byte for byte.  The schedule
@@ -153,7 +170,7 @@ class Comm {
   void launch(int algo, const void* send, void* recv, size_t chunk_bytes, int dtype, int op, hipStream_t stream,
               uint32_t seq, bool vec, const char* const* psend = nullptr, const char* const* precv = nullptr,
               size_t tail_bytes = 0, uint64_t sig = 0, int coll = kCollAllReduce, int root = 0,
-              size_t total_bytes = 0);
+              size_t total_bytes = 0, uint64_t scalar = 0);
   CollParams make_params(int algo, const void* send, void* recv, size_t chunk_bytes, uint32_t seq,
                          const char* const* psend, const char* const* precv, size_t tail_bytes, uint64_t sig, int coll,
                          int root, size_t total_bytes, int* pipes);
@@ -173,7 +190,10 @@ class Comm {
   // the one call path of the six collectives; count: the all-reduce's and the rooted ones', per
   // rank for the halves, per block for the all-to-all
   ncclResult_t collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
-                          hipStream_t stream, int root = 0);
+                          hipStream_t stream, int root = 0, uint64_t scalar = 0);
+  // a kPreMulSum call on a communicator of one rank: recv = round(scalar * send) over `count` elements
+  void scale_one_rank(const void* send, void* recv, size_t count, int dtype, uint64_t scalar, const CallScope& sc,
+                      hipStream_t stream);
   // one rendezvous failure of the read schedule, reported like the kernel's (sticky, peers aborted)
   ncclResult_t rendezvous_failed(const std::exception& e, bool peer_gave_up, int cur_dev);
   struct Window {
@@ -241,6 +261,12 @@ class Comm {
   bool have_last_ = false;
   ncclResult_t sticky_ = ncclSuccess;
   bool warned_capture_ = false;
+  struct UserOp {
+    bool live = false;
+    int dtype = 0;
+    uint64_t scalar = 0;
+  };
+  UserOp user_ops_[kMaxUserOps];
 };
 
 // 1-GPU local reduce (mini_nccl_ext.h): no communicator needed.

@@ -9,7 +9,11 @@ namespace mnccl {
 
 // Element types the kernels are instantiated for (subset of ncclDataType_t values).
 enum DType : int { kI32 = 2, kF16 = 6, kF32 = 7, kF64 = 8, kBF16 = 9 };
-enum RedOp : int { kSum = 0, kProd = 1, kMax = 2, kMin = 3 };
+enum RedOp : int { kSum = 0, kProd = 1, kMax = 2, kMin = 3,
+                   // a handle of ncclRedOpCreatePreMulSum, resolved: the sum of inputs scaled by
+                   // CollParams::scale where they enter a fold (kernels.hip Scale); the communicator
+                   // calls only (launch_local_reduce refuses it)
+                   kPreMulSum = 5 };
 
 // Everything a ring / read kernel needs; passed by value as the kernel argument.
 struct CollParams {
@@ -56,6 +60,10 @@ struct CollParams {
   // (schedule.h rooted_len); unused (0) by the other collectives
   uint64_t total_bytes;       // count * element size
   int32_t root;
+  // kPreMulSum: the scalar's bits, one value of the call's datatype in the low bytes -- by value, so
+  // the op may be destroyed once the call is issued (captured into a graph too); 0 and unread for
+  // every other op.  After everything else: every other offset is what it was
+  uint64_t scale;
 };
 
 constexpr int kMaxRanks = 16;
@@ -88,6 +96,7 @@ enum PersistentKernel : int {
 
 // Launchers return hipSuccess or the launch error; dtype/op must be supported
 // (checked by the caller).  vec = 16-byte path (all offsets 16-byte aligned).
+// op: one of the four built-ins, or kPreMulSum for the kernels that fold (p.scale the scalar).
 // launch_persistent refuses a p.coll that is not the kernel's, a root outside [0, n) for the
 // rooted kernels and n < 2 for the all-to-all; the kernels that only copy ignore op.
 hipError_t launch_persistent(int kernel, int dtype, int op, bool vec, int channels, int threads,
@@ -117,7 +126,10 @@ hipError_t launch_p2p(const CollParams& p, const P2pArgs& a, hipStream_t stream)
 // schedule.h read_grid_fits(p.chunk_bytes, p.n, kReadGridFloor) (2 <= n <= 8, whole 16-byte vectors), p.go set
 // vectors: 0 = schedule.h read_grid_vectors; 1 / 2 / 4 (MINI_NCCL_GRID_VECTORS) for fp32 Sum only
 hipError_t launch_read_grid(int dtype, int op, const CollParams& p, hipStream_t stream, int vectors = 0);
-// out[i] = op(local[i], incoming[i]) for i < count
+// out[i] = round(scale * in[i]) for i < count, one rounding in the datatype's arithmetic (a
+// kPreMulSum call on a communicator of one rank); out may be in
+hipError_t launch_scale(int dtype, void* out, const void* in, uint64_t count, uint64_t scale, hipStream_t stream);
+// out[i] = op(local[i], incoming[i]) for i < count (the four built-in ops)
 hipError_t launch_local_reduce(int dtype, int op, void* out, const void* local,
                                const void* incoming, uint64_t count, hipStream_t stream);
 

@@ -116,7 +116,68 @@ template <> struct Op<bf16_t, kProd> { __device__ static bf16_t f(bf16_t a, bf16
 template <> struct Op<bf16_t, kMax> { __device__ static bf16_t f(bf16_t a, bf16_t b) { return (bf2f(a) > bf2f(b)) ? a : b; } };
 template <> struct Op<bf16_t, kMin> { __device__ static bf16_t f(bf16_t a, bf16_t b) { return (bf2f(a) < bf2f(b)) ? a : b; } };
 
+
+// kPreMulSum (ncclRedOpCreatePreMulSum): the sum of inputs that were scaled on their way in.  Every
+// rank's input element becomes y = round_T(s * x) where it enters a fold (prescale below) -- ONE
+// correctly rounded multiplication in T's arithmetic (f16: the f16 product; bf16: the f32 product,
+// exact, rounded to nearest even; int32: two's-complement wrap) -- and the y are then summed exactly
+// as kSum sums them, packed adds included.  s is the call's scalar, the same on every rank, by
+// value in CollParams::scale (wave-uniform: it stays in SGPRs).  The product and the sum stay two
+// roundings: the ring scales a chunk in one message body and adds to it in another, so a fold that
+// fused them would disagree with it.  hipcc contracts a * b + c by default; the pragma keeps the
+// multiplication out of that, here only -- every other kernel compiles as it did.
+template <typename T> struct Op<T, kPreMulSum> : Op<T, kSum> {};
+
+template <typename T> struct Scale;
+template <> struct Scale<float> {
+  __device__ static float f(u64 s, float x) {
+#pragma clang fp contract(off)
+    return __uint_as_float((uint32_t)s) * x;
+  }
+};
+template <> struct Scale<double> {
+  __device__ static double f(u64 s, double x) {
+#pragma clang fp contract(off)
+    return __longlong_as_double((long long)s) * x;
+  }
+};
+template <> struct Scale<_Float16> {
+  __device__ static _Float16 f(u64 s, _Float16 x) {
+#pragma clang fp contract(off)
+    return __builtin_bit_cast(_Float16, (uint16_t)s) * x;
+  }
+};
+template <> struct Scale<bf16_t> {
+  __device__ static bf16_t f(u64 s, bf16_t x) {
+#pragma clang fp contract(off)
+    bf16_t sb;
+    sb.v = (uint16_t)s;
+    return f2bf(bf2f(sb) * bf2f(x));
+  }
+};
+template <> struct Scale<int32_t> {
+  __device__ static int32_t f(u64 s, int32_t x) { return (int32_t)((uint32_t)s * (uint32_t)x); }
+};
+
 template <typename T> struct alignas(16) Pack16 { T x[16 / sizeof(T)]; };
+
+// an input on its way into a fold: scaled for kPreMulSum, untouched (and no code) for every other op
+template <typename T, int OPC>
+__device__ __forceinline__ T prescale(T x, u64 s) {
+  if constexpr (OPC == kPreMulSum) return Scale<T>::f(s, x);
+  else return x;
+}
+template <typename T, int OPC>
+__device__ __forceinline__ v4u prescale16(v4u a, u64 s) {
+  if constexpr (OPC == kPreMulSum) {
+    Pack16<T> pa = __builtin_bit_cast(Pack16<T>, a);
+#pragma unroll
+    for (int i = 0; i < (int)(16 / sizeof(T)); ++i) pa.x[i] = Scale<T>::f(s, pa.x[i]);
+    return __builtin_bit_cast(v4u, pa);
+  } else {
+    return a;
+  }
+}
 
 template <typename T, int OPC>
 __device__ __forceinline__ v4u reduce16(v4u a, v4u b) {
@@ -381,10 +442,11 @@ template <> struct KindBits<kForward> { static constexpr int v = kHasIn | kSends
 constexpr int kU = 8;  // 16-byte vectors per lane per batch: 8 KiB per wave in flight per stream
 
 template <typename T, int OPC, int KIND>
-__device__ __forceinline__ void vec_one(const char* lsrc, char* ldst, rsrc_t in, rsrc_t out, uint32_t i) {
+__device__ __forceinline__ void vec_one(const char* lsrc, char* ldst, rsrc_t in, rsrc_t out, uint32_t i, u64 sc) {
   constexpr int B = KindBits<KIND>::v;
   v4u l, x, v;
-  if (B & kHasLocal) l = ld_g16(lsrc + (size_t)i * 16);
+  // (the local operand is this rank's input: kPreMulSum scales it here, prescale16)
+  if (B & kHasLocal) l = prescale16<T, OPC>(ld_g16(lsrc + (size_t)i * 16), sc);
   if (B & kHasIn) x = ld_slot16(in, i * 16);
   if (B & kReduces) v = reduce16<T, OPC>(l, x);
   else if (B & kHasIn) v = x;
@@ -395,14 +457,14 @@ __device__ __forceinline__ void vec_one(const char* lsrc, char* ldst, rsrc_t in,
 
 template <typename T, int OPC, int KIND>
 __device__ __forceinline__ void move_scalar(const char* __restrict__ lsrc, char* __restrict__ ldst, rsrc_t in,
-                                            rsrc_t out, uint32_t nbytes, int lane, uint32_t off0);
+                                            rsrc_t out, uint32_t nbytes, int lane, uint32_t off0, u64 sc);
 
 // 16-byte vectors over the message, then its last (nbytes % 16) bytes element by element.
 // The local side (send / recv) may be element- but not 16-byte-aligned (4-byte-aligned
 // dwordx4 accesses are valid on gfx950); the slot side is always 16-byte-aligned.
 template <typename T, int OPC, int KIND, int UB = kU>
 __device__ __forceinline__ void move_vec(const char* __restrict__ lsrc, char* __restrict__ ldst, rsrc_t in,
-                                         rsrc_t out, uint32_t nbytes, int lane) {
+                                         rsrc_t out, uint32_t nbytes, int lane, u64 sc) {
   constexpr int B = KindBits<KIND>::v;
   const uint32_t nvec = nbytes >> 4;
   uint32_t b = 0;
@@ -418,6 +480,7 @@ __device__ __forceinline__ void move_vec(const char* __restrict__ lsrc, char* __
     for (int u = 0; u < UB; ++u) {
       const uint32_t i = b + (uint32_t)(u * 64 + lane);
       v4u v;
+      if (B & kHasLocal) l[u] = prescale16<T, OPC>(l[u], sc);
       if (B & kReduces) v = reduce16<T, OPC>(l[u], x[u]);
       else if (B & kHasIn) v = x[u];
       else v = l[u];
@@ -425,20 +488,20 @@ __device__ __forceinline__ void move_vec(const char* __restrict__ lsrc, char* __
       if (B & kSends) st_slot16(out, i * 16, v);
     }
   }
-  for (uint32_t i = b + (uint32_t)lane; i < nvec; i += 64) vec_one<T, OPC, KIND>(lsrc, ldst, in, out, i);
-  if (nbytes & 15u) move_scalar<T, OPC, KIND>(lsrc, ldst, in, out, nbytes, lane, nvec * 16);
+  for (uint32_t i = b + (uint32_t)lane; i < nvec; i += 64) vec_one<T, OPC, KIND>(lsrc, ldst, in, out, i, sc);
+  if (nbytes & 15u) move_scalar<T, OPC, KIND>(lsrc, ldst, in, out, nbytes, lane, nvec * 16, sc);
 }
 
 // elements [off0 / sizeof(T), nbytes / sizeof(T)) of the message, one per lane
 template <typename T, int OPC, int KIND>
 __device__ __forceinline__ void move_scalar(const char* __restrict__ lsrc, char* __restrict__ ldst, rsrc_t in,
-                                            rsrc_t out, uint32_t nbytes, int lane, uint32_t off0) {
+                                            rsrc_t out, uint32_t nbytes, int lane, uint32_t off0, u64 sc) {
   constexpr int B = KindBits<KIND>::v;
   typedef typename Scal<sizeof(T)>::U U;
   const uint32_t ne = nbytes / sizeof(T);
   for (uint32_t i = off0 / sizeof(T) + lane; i < ne; i += 64) {
     U l = 0, x = 0, v;
-    if (B & kHasLocal) l = reinterpret_cast<const U*>(lsrc)[i];
+    if (B & kHasLocal) l = __builtin_bit_cast(U, prescale<T, OPC>(reinterpret_cast<const T*>(lsrc)[i], sc));
     if (B & kHasIn) x = Scal<sizeof(T)>::ld(in, i * (uint32_t)sizeof(T));
     if (B & kReduces) v = __builtin_bit_cast(U, Op<T, OPC>::f(__builtin_bit_cast(T, l), __builtin_bit_cast(T, x)));
     else if (B & kHasIn) v = x;
@@ -449,9 +512,10 @@ __device__ __forceinline__ void move_scalar(const char* __restrict__ lsrc, char*
 }
 
 template <typename T, int OPC, bool VEC, int KIND, int UB = kU>
-__device__ __forceinline__ void move(const char* lsrc, char* ldst, rsrc_t in, rsrc_t out, uint32_t nbytes, int lane) {
-  if (VEC) move_vec<T, OPC, KIND, UB>(lsrc, ldst, in, out, nbytes, lane);
-  else move_scalar<T, OPC, KIND>(lsrc, ldst, in, out, nbytes, lane, 0);
+__device__ __forceinline__ void move(const char* lsrc, char* ldst, rsrc_t in, rsrc_t out, uint32_t nbytes, int lane,
+                                     u64 sc = 0) {
+  if (VEC) move_vec<T, OPC, KIND, UB>(lsrc, ldst, in, out, nbytes, lane, sc);
+  else move_scalar<T, OPC, KIND>(lsrc, ldst, in, out, nbytes, lane, 0, sc);
 }
 
 // the ABORT word a giving-up rank writes into its peers' mailboxes: its rank + 1 (never 0) and
@@ -506,8 +570,13 @@ __device__ __forceinline__ WaveId wave_id() {
 // their watchdogs fired).  With one rank per GPU this costs nothing.  (kernels.h
 // kMinWavesPerSimd; Comm caps a call's pipelines so that every rank's waves fit, Comm::run_pipes.)
 
+// The kernels that fold have their code in a *_body function and two entry points: the one named
+// for the four built-in ops, and a `scaled_*` one for kPreMulSum (the resource budget of the
+// built-in kernels is checked by name, tests/test_kernel_resources.py; the scaled ones have the
+// same budget, tests/test_premul_cpu.py).  (__restrict__: the argument is the kernel's own copy; without
+// it the ring kernels took one register more than they had as kernels of their own.)
 template <typename T, int OPC, bool VEC>
-__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) ring_kernel(CollParams p) {
+__device__ __forceinline__ void ring_body(const CollParams& __restrict__ p) {
   signal_start(p);
   const WaveId id = wave_id();
   // C: the communicator's pipelines (mailbox, scratch and counter layout); A: the ones this call
@@ -560,12 +629,12 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) ring_kernel(Col
         const char* lsrc = p.send + coff;
         char* ldst = p.recv + coff;
         switch (o.kind) {
-          case kSend: move<T, OPC, VEC, kSend>(lsrc, ldst, in, out, len, lane); break;
-          case kReduceSend: move<T, OPC, VEC, kReduceSend>(lsrc, ldst, in, out, len, lane); break;
-          case kReduceCopySend: move<T, OPC, VEC, kReduceCopySend>(lsrc, ldst, in, out, len, lane); break;
-          case kCopySend: move<T, OPC, VEC, kCopySend>(lsrc, ldst, in, out, len, lane); break;
-          case kForward: move<T, OPC, VEC, kForward>(lsrc, ldst, in, out, len, lane); break;
-          default: move<T, OPC, VEC, kCopy>(lsrc, ldst, in, out, len, lane); break;
+          case kSend: move<T, OPC, VEC, kSend>(lsrc, ldst, in, out, len, lane, p.scale); break;
+          case kReduceSend: move<T, OPC, VEC, kReduceSend>(lsrc, ldst, in, out, len, lane, p.scale); break;
+          case kReduceCopySend: move<T, OPC, VEC, kReduceCopySend>(lsrc, ldst, in, out, len, lane, p.scale); break;
+          case kCopySend: move<T, OPC, VEC, kCopySend>(lsrc, ldst, in, out, len, lane, p.scale); break;
+          case kForward: move<T, OPC, VEC, kForward>(lsrc, ldst, in, out, len, lane, p.scale); break;
+          default: move<T, OPC, VEC, kCopy>(lsrc, ldst, in, out, len, lane, p.scale); break;
         }
       }
       drain_stores();  // every load of the slot has returned and every store has landed
@@ -579,6 +648,15 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) ring_kernel(Col
     *tx_ctr = tx_base + (u64)p.iters * mpi_tx;
     *rx_ctr = rx_base + (u64)p.iters * mpi_rx;
   }
+}
+
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) ring_kernel(CollParams p) {
+  ring_body<T, OPC, VEC>(p);
+}
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scaled_ring(CollParams p) {
+  ring_body<T, kPreMulSum, VEC>(p);
 }
 
 constexpr int kMaxWaves = kMaxThreads / 64;
@@ -600,10 +678,10 @@ __device__ __forceinline__ void read_fold_scalar(const CollParams& p, uint64_t c
   const rsrc_t out = make_rsrc(p.recv + coff, nbytes);
   const uint32_t ne = nbytes / sizeof(T);
   for (uint32_t i = off0 / sizeof(T) + lane; i < ne; i += 64) {
-    T acc = reinterpret_cast<const T*>(p.send + coff)[i];
+    T acc = prescale<T, OPC>(reinterpret_cast<const T*>(p.send + coff)[i], p.scale);
     for (int k = 1; k < n; ++k) {
       const rsrc_t in = make_rsrc(p.peer_send[direct_peer(n, r, k)] + coff, nbytes);
-      acc = Op<T, OPC>::f(__builtin_bit_cast(T, Scal<sizeof(T)>::ld(in, i * (uint32_t)sizeof(T))), acc);
+      acc = Op<T, OPC>::f(prescale<T, OPC>(__builtin_bit_cast(T, Scal<sizeof(T)>::ld(in, i * (uint32_t)sizeof(T))), p.scale), acc);
     }
     Scal<sizeof(T)>::st(out, i * (uint32_t)sizeof(T), __builtin_bit_cast(Us, acc));
   }
@@ -638,6 +716,8 @@ __device__ __forceinline__ void read_fold_wide(const CollParams& p, uint64_t cof
     v4u acc[kWideV];
 #pragma unroll
     for (int u = 0; u < kWideV; ++u) acc[u] = ld_nt16(loc, (b + (uint32_t)(u * 64 + lane)) * 16);
+#pragma unroll
+    for (int u = 0; u < kWideV; ++u) acc[u] = prescale16<T, OPC>(acc[u], p.scale);
     for (int k0 = 1; k0 < n; k0 += kWideG) {  // ring order: groups in turn, peers in turn
       v4u x[kWideG][kWideV];
 #pragma unroll
@@ -651,7 +731,7 @@ __device__ __forceinline__ void read_fold_wide(const CollParams& p, uint64_t cof
       for (int g = 0; g < kWideG; ++g)
         if (k0 + g < n) {
 #pragma unroll
-          for (int u = 0; u < kWideV; ++u) acc[u] = reduce16<T, OPC>(x[g][u], acc[u]);
+          for (int u = 0; u < kWideV; ++u) acc[u] = reduce16<T, OPC>(prescale16<T, OPC>(x[g][u], p.scale), acc[u]);
         }
     }
 #pragma unroll
@@ -713,11 +793,14 @@ __device__ __forceinline__ void read_fold_all(const CollParams& p, uint64_t coff
     for (int u = 0; u < V; ++u) a[u] = ld_nt16(loc, (b + (uint32_t)(u * 64 + lane)) * 16);
   };
   auto fold_store = [&](v4u(&x)[G][V], v4u(&a)[V], uint32_t b) {
+    // (kPreMulSum: every operand is some rank's input -- the own slice and every peer's are scaled)
+#pragma unroll
+    for (int u = 0; u < V; ++u) a[u] = prescale16<T, OPC>(a[u], p.scale);
 #pragma unroll
     for (int g = 0; g < G; ++g)
       if (g + 1 < n) {
 #pragma unroll
-        for (int u = 0; u < V; ++u) a[u] = reduce16<T, OPC>(x[g][u], a[u]);
+        for (int u = 0; u < V; ++u) a[u] = reduce16<T, OPC>(prescale16<T, OPC>(x[g][u], p.scale), a[u]);
       }
 #pragma unroll
     for (int u = 0; u < V; ++u) st_slot16(out, (b + (uint32_t)(u * 64 + lane)) * 16, a[u]);
@@ -770,7 +853,9 @@ __device__ __forceinline__ uint32_t read_fold(const CollParams& p, uint64_t coff
     if (nbytes & 15u) read_fold_scalar<T, OPC>(p, coff, nbytes, lane, nvec * 16);
     return nvec * 16;
   }
-  constexpr int U = kReadFoldU;
+  // (kPreMulSum on int32: half the batch -- with 16 vectors per stream the 32-bit multiplies spilled
+  // 36 registers to scratch at the 256-register bound)
+  constexpr int U = OPC == kPreMulSum && std::is_same<T, int32_t>::value ? kReadFoldU / 2 : kReadFoldU;
   const rsrc_t out = make_rsrc(p.recv + coff, nbytes);
   const char* lsrc = p.send + coff;
   uint32_t b = 0;
@@ -779,6 +864,8 @@ __device__ __forceinline__ uint32_t read_fold(const CollParams& p, uint64_t coff
     v4u acc[U], cur[U], nxt[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) acc[u] = ld_g16(lsrc + (size_t)(b + (uint32_t)(u * 64 + lane)) * 16);
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc[u] = prescale16<T, OPC>(acc[u], p.scale);
     {
       const rsrc_t in = make_rsrc(p.peer_send[direct_peer(n, r, 1)] + coff, nbytes);
 #pragma unroll
@@ -791,7 +878,7 @@ __device__ __forceinline__ uint32_t read_fold(const CollParams& p, uint64_t coff
         for (int u = 0; u < U; ++u) nxt[u] = ld_slot16(in, (b + (uint32_t)(u * 64 + lane)) * 16);
       }
 #pragma unroll
-      for (int u = 0; u < U; ++u) acc[u] = reduce16<T, OPC>(cur[u], acc[u]);
+      for (int u = 0; u < U; ++u) acc[u] = reduce16<T, OPC>(prescale16<T, OPC>(cur[u], p.scale), acc[u]);
 #pragma unroll
       for (int u = 0; u < U; ++u) cur[u] = nxt[u];
     }
@@ -829,7 +916,7 @@ __device__ __forceinline__ void read_push_rest(const CollParams& p, uint64_t cof
 // DONE also returns credits for every message (the counters continue across calls, whatever the
 // schedule).
 template <typename T, int OPC, bool VEC>
-__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) read_kernel(CollParams p) {
+__device__ __forceinline__ void read_body(const CollParams& p) {
   signal_start(p);
   const WaveId id = wave_id();
   // C: the communicator's pipelines (mailbox and counter layout); A: the ones this call runs
@@ -891,6 +978,15 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) read_kernel(Col
 aborted:
   if (lane == 0)
     for (int k = 1; k < n; ++k) st_sys(p.peer_mbox[direct_peer(n, r, k)] + mbox_abort(n, C), abort_word(p, seen));
+}
+
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) read_kernel(CollParams p) {
+  read_body<T, OPC, VEC>(p);
+}
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scaled_read(CollParams p) {
+  read_body<T, kPreMulSum, VEC>(p);
 }
 
 // ---------------------------------------------------------------- the read schedule's two halves
@@ -967,6 +1063,11 @@ template <typename T, int OPC, bool VEC>
 __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scatter_fold(CollParams p) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, OPC, VEC, false>(p, coff, len, lane); });
+}
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scaled_scatter(CollParams p) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, kPreMulSum, VEC, false>(p, coff, len, lane); });
 }
 
 // ---------------------------------------------------------------- copy and push
@@ -1100,6 +1201,12 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) root_fold(CollP
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   read_half<true>(p, s_tx, s_rx,
                   [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, OPC, VEC, false>(p, coff, len, lane); });
+}
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scaled_root(CollParams p) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half<true>(p, s_tx, s_rx,
+                  [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, kPreMulSum, VEC, false>(p, coff, len, lane); });
 }
 
 // Broadcast: rank r copies its slices of chunk r from the root's send -- sc0 sc1 loads over the
@@ -1511,10 +1618,12 @@ __global__ void __launch_bounds__(64) read_grid_kernel(CollParams p) {
 #pragma unroll
   for (int u = 0; u < V; ++u) a[u] = ld_nt16(loc, (uint32_t)(u * 64 + lane) * 16);
 #pragma unroll
+  for (int u = 0; u < V; ++u) a[u] = prescale16<T, OPC>(a[u], p.scale);
+#pragma unroll
   for (int g = 0; g < G; ++g)
     if (g + 1 < n) {
 #pragma unroll
-      for (int u = 0; u < V; ++u) a[u] = reduce16<T, OPC>(x[g][u], a[u]);
+      for (int u = 0; u < V; ++u) a[u] = reduce16<T, OPC>(prescale16<T, OPC>(x[g][u], p.scale), a[u]);
     }
 #pragma unroll
   for (int u = 0; u < V; ++u) st_slot16(out, (uint32_t)(u * 64 + lane) * 16, a[u]);
@@ -1694,6 +1803,15 @@ __global__ void __launch_bounds__(256) local_reduce_scalar(T* __restrict__ out, 
   for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = Op<T, OPC>::f(a[i], b[i]);
 }
 
+// kPreMulSum on a communicator of one rank: the call is no copy but out[i] = round_T(s * in[i]), the
+// same single rounding the folds apply (Scale).  out may be in (in place): an element is read and
+// written by one thread.
+template <typename T>
+__global__ void __launch_bounds__(256) scale_kernel(T* out, const T* in, u64 n, u64 s) {
+  const u64 stride = (u64)gridDim.x * blockDim.x;
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = Scale<T>::f(s, in[i]);
+}
+
 // ---------------------------------------------------------------- link probe
 struct ProbeArgs {
   char* local;
@@ -1857,19 +1975,26 @@ static hipError_t launch_on(K kernel, int C, int nt, const CollParams& p, hipStr
 hipError_t launch_persistent(int kernel, int dtype, int op, bool vec, int C, int nt, const CollParams& p,
                              hipStream_t st) {
   const bool root_ok = p.root >= 0 && p.root < p.n;
-#define FOLDS(K)                                                                                              \
-  for_type_op_vec(dtype, op, vec, [&](auto t, auto o, auto v) {                                              \
+  // K: the kernel of the four built-in ops; S: its entry point for kPreMulSum (no op parameter)
+#define FOLDS(K, S)                                                                                           \
+  (op == kPreMulSum ? for_dtype(dtype, [&](auto t) {                                                          \
+    return for_vec(vec, [&](auto v) { return launch_on(S<typename decltype(t)::type, decltype(v)::value>, C, nt, p, st); }); \
+  }) : for_type_op_vec(dtype, op, vec, [&](auto t, auto o, auto v) {                                          \
     return launch_on(K<typename decltype(t)::type, decltype(o)::value, decltype(v)::value>, C, nt, p, st);   \
-  })
+  }))
 #define COPIES(K) \
   for_size_vec(dtype, vec, [&](auto e, auto v) { return launch_on(K<decltype(e)::value, decltype(v)::value>, C, nt, p, st); })
   switch (kernel) {
-    case kKernelRing: return FOLDS(ring_kernel);
-    case kKernelRead: return FOLDS(read_kernel);
-    case kKernelOneshot: return FOLDS(oneshot_kernel);
-    case kKernelScatterFold: return p.coll == kCollReduceScatter ? FOLDS(scatter_fold) : hipErrorInvalidValue;
+    case kKernelRing: return FOLDS(ring_kernel, scaled_ring);
+    case kKernelRead: return FOLDS(read_kernel, scaled_read);
+        // (no one-shot form of kPreMulSum: Comm::collective routes such a call to the read schedule or the ring)
+    case kKernelOneshot:
+      return op == kPreMulSum ? hipErrorInvalidValue : for_type_op_vec(dtype, op, vec, [&](auto t, auto o, auto v) {
+        return launch_on(oneshot_kernel<typename decltype(t)::type, decltype(o)::value, decltype(v)::value>, C, nt, p, st);
+      });
+    case kKernelScatterFold: return p.coll == kCollReduceScatter ? FOLDS(scatter_fold, scaled_scatter) : hipErrorInvalidValue;
     case kKernelGatherPush: return p.coll == kCollAllGather ? COPIES(gather_push) : hipErrorInvalidValue;
-    case kKernelRootFold: return p.coll == kCollReduce && root_ok ? FOLDS(root_fold) : hipErrorInvalidValue;
+    case kKernelRootFold: return p.coll == kCollReduce && root_ok ? FOLDS(root_fold, scaled_root) : hipErrorInvalidValue;
     case kKernelRootRelay: return p.coll == kCollBroadcast && root_ok ? COPIES(root_relay) : hipErrorInvalidValue;
     case kKernelExchangePush: return p.coll == kCollAllToAll && p.n >= 2 ? COPIES(exchange_push) : hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
@@ -1955,7 +2080,9 @@ hipError_t launch_read_grid(int dtype, int op, const CollParams& p, hipStream_t 
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   e = for_dtype(dtype, [&](auto t) {
-    return for_op(op, [&](auto o) { return read_grid_for<typename decltype(t)::type, decltype(o)::value>(p, st, vectors); });
+    using T = typename decltype(t)::type;
+    if (op == kPreMulSum) return read_grid_for<T, kPreMulSum>(p, st, vectors);
+    return for_op(op, [&](auto o) { return read_grid_for<T, decltype(o)::value>(p, st, vectors); });
   });
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(read_done_kernel, dim3(1), dim3(64), 0, st, p);
@@ -1969,6 +2096,16 @@ hipError_t launch_local_reduce(int dtype, int op, void* out, const void* local, 
     return for_op(op, [&](auto o) {
       return local_for<typename decltype(t)::type, decltype(o)::value>(out, local, incoming, count, st);
     });
+  });
+}
+
+hipError_t launch_scale(int dtype, void* out, const void* in, uint64_t count, uint64_t scale, hipStream_t st) {
+  if (count == 0) return hipSuccess;
+  return for_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(scale_kernel<T>, dim3((unsigned)std::min<u64>((count + 255) / 256, 16384)), dim3(256), 0, st, (T*)out,
+                       (const T*)in, (u64)count, (u64)scale);
+    return hipGetLastError();
   });
 }
 

@@ -61,6 +61,7 @@ struct alignas(64) CallRec {
   // kernel checks the call's signature on the device
   int32_t fast;
   uint64_t sig;
+  uint64_t scalar;  // the bits of a pre-multiplied sum's scalar (negotiate's `scalar`; 0 otherwise)
   // second round (only when some rank may have to open a new mapping): the call whose mapping
   // outcome map_ok reports, stored after it (release)
   alignas(64) std::atomic<uint64_t> mapped;
@@ -375,6 +376,7 @@ void PeerBuffers::publish_fast(uint64_t count, int dtype, int op, uint64_t sig, 
   me.nfreed = 0;  // frees wait for this rank's next negotiated record
   me.fast = 1;
   me.sig = sig;
+  me.scalar = 0;  // (part of the signature the kernels compare)
   me.seq.store(k, std::memory_order_release);
   board_->consumed[rank_].v.store(k, std::memory_order_release);  // nothing of this call to read
 }
@@ -383,7 +385,7 @@ PeerBuffers::Decision PeerBuffers::negotiate(const void* send, const void* recv,
                                              int dtype, int op, double timeout_s,
                                              const std::function<void()>& sync_previous, const char** psend,
                                              const char** precv, bool* vec_all, int form, const VarRow* row,
-                                             VarRow* rows_out) {
+                                             VarRow* rows_out, uint64_t scalar) {
   const uint64_t k = ++seq_;
   const double t0 = now_s();
   // spins until ready() -- bounded by the peer q giving up and by the rendezvous limit
@@ -400,7 +402,7 @@ PeerBuffers::Decision PeerBuffers::negotiate(const void* send, const void* recv,
   };
   try {
     return negotiate_body(k, send, recv, eligible, count, dtype, op, form, sync_previous, psend, precv, vec_all,
-                          wait_for, row, rows_out);
+                          wait_for, row, rows_out, scalar);
   } catch (...) {
     // this rank gives up (a peer that never came or gave up itself): say so on the board, so
     // every peer waiting in a rendezvous with it fails at once instead of at its own limit (the
@@ -530,7 +532,7 @@ PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, 
                                                   uint64_t count, int dtype, int op, int form,
                                                   const std::function<void()>& sync_previous, const char** psend,
                                                   const char** precv, bool* vec_all, const WaitFor& wait_for,
-                                                  const VarRow* row, VarRow* rows_out) {
+                                                  const VarRow* row, VarRow* rows_out, uint64_t scalar) {
   auto wait = [&](const std::atomic<uint64_t>& v, uint64_t want, int q, const char* what) {
     wait_for([&] { return v.load(std::memory_order_acquire) >= want; }, q, what);
   };
@@ -555,6 +557,7 @@ PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, 
   me.form = form;
   me.fast = 0;
   me.sig = 0;
+  me.scalar = scalar;
   me.eligible = ok ? 1 : 0;
   me.aligned = ((sd.raw | rd.raw) % 4 == 0) ? 1 : 0;
   me.send = sd;
@@ -570,7 +573,7 @@ PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, 
   me.seq.store(k, std::memory_order_release);
 
   struct Seen {
-    uint64_t count;
+    uint64_t count, scalar;
     int32_t dtype, op, eligible, aligned, fast, form;
     BufDesc send, recv;
     int32_t nfreed;
@@ -582,6 +585,7 @@ PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, 
     if (q != rank_) wait(c.seq, k, q, "reach");
     Seen& s = recs[(size_t)q];
     s.count = c.count;
+    s.scalar = c.scalar;
     s.dtype = c.dtype;
     s.op = c.op;
     s.eligible = c.eligible;
@@ -632,7 +636,7 @@ PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, 
   for (const Seen& c : recs) {
     all = all && c.eligible;
     aligned = aligned && c.aligned;
-    mismatch = mismatch || (!row && c.count != count) || c.dtype != dtype || c.op != op || c.form != form;
+    mismatch = mismatch || (!row && c.count != count) || c.dtype != dtype || c.op != op || c.scalar != scalar || c.form != form;
   }
   // ncclAllToAllv: every pair's counts instead of the scalar count (only rows of this collective)
   if (row && rows_out && !mismatch) mismatch = varblock_matrix_mismatch(nranks_, rows_out) != 0;

@@ -65,7 +65,9 @@ class PeerBuffers {
   // kernel (before a freed peer allocation's mapping is closed).  `form`: the kernel form this
   // rank would launch for the call (Comm: its schedule choice, mncclCommSetAlgo) -- ranks that
   // differ in it get kMismatch, as for count / dtype / op (a grid-form rank's DONE could otherwise
-  // be met by a persistent peer's pipeline 0 while the other pipelines never start).  Throws
+  // be met by a persistent peer's pipeline 0 while the other pipelines never start).  `scalar`: the
+  // bits of a pre-multiplied sum's scalar (0 for the built-in ops), compared like `op`: the read
+  // schedule lets a rank scale its peers' inputs, so the scalar must be the same everywhere.  Throws
   // std::runtime_error when a peer does not arrive within timeout_s.
   // `row` (ncclAllToAllv only): this rank's counts, recv displacements and flags, published with its
   // record; `rows_out` then gets every rank's row (nranks entries, whatever the decision), and the
@@ -74,7 +76,7 @@ class PeerBuffers {
   Decision negotiate(const void* send, const void* recv, bool eligible, uint64_t count, int dtype, int op,
                      double timeout_s, const std::function<void()>& sync_previous, const char** psend,
                      const char** precv, bool* vec_all, int form = 0, const VarRow* row = nullptr,
-                     VarRow* rows_out = nullptr);
+                     VarRow* rows_out = nullptr, uint64_t scalar = 0);
 
   // A registered-window call (Comm::allreduce's fast path): this rank's record for the next call,
   // marked fast with the call's signature, published WITHOUT reading the peers' -- their kernels
@@ -121,7 +123,7 @@ class PeerBuffers {
   Decision negotiate_body(uint64_t k, const void* send, const void* recv, bool eligible, uint64_t count, int dtype,
                           int op, int form, const std::function<void()>& sync_previous, const char** psend,
                           const char** precv, bool* vec_all, const WaitFor& wait_for, const VarRow* row,
-                          VarRow* rows_out);
+                          VarRow* rows_out, uint64_t scalar);
   bool describe(const void* p, uint64_t* base, uint64_t* id, ipc::Shared* d);
   char* map_peer(int q, uint64_t base, uint64_t id, int fd, const ipc::Shared& d, std::string* why);
   void sock_addr(int q, void* addr, unsigned* len) const;

@@ -35,6 +35,10 @@ ncclFloat16, ncclFloat, ncclDouble, ncclBfloat16 = 6, 7, 8, 9
 # ncclRedOp_t (reference :43-49)
 ncclSum, ncclProd, ncclMax, ncclMin, ncclAvg = 0, 1, 2, 3, 4
 
+# ncclScalarResidence_t and the first handle of a user-created op (ncclRedOpCreatePreMulSum)
+ncclScalarDevice, ncclScalarHostImmediate = 0, 1
+MNCCL_FIRST_USER_OP = 5
+
 # mncclAlgo_t (mncclAlgoDirect = 1 was removed in mncclVersion 400)
 ALGO_AUTO, ALGO_RING, ALGO_READ, ALGO_ONESHOT, ALGO_READ_GRID = -1, 0, 2, 3, 4
 
@@ -89,6 +93,8 @@ SIGNATURES = {
     "ncclRecv": (_I, [_VP, _SZ, _I, _I, _VP, _VP]),
     "ncclGroupStart": (_I, []),
     "ncclGroupEnd": (_I, []),
+    "ncclRedOpCreatePreMulSum": (_I, [ctypes.POINTER(_I), _VP, _I, _I, _VP]),
+    "ncclRedOpDestroy": (_I, [_I, _VP]),
     "mncclLocalReduce": (_I, [_VP, _VP, _VP, _SZ, _I, _I, _VP]),
     "mncclCommGetAsyncError": (_I, [_VP, ctypes.POINTER(_I)]),
     "mncclCommGetInfo": (_I, [_VP, ctypes.POINTER(CommInfo)]),
@@ -133,6 +139,32 @@ def check(code, what="mini-nccl"):
     if code != ncclSuccess:
         raise NcclError(code, what)
     return code
+
+
+def scalar_bytes(scalar, dtype):
+    """One value of `dtype` as a ctypes buffer (what ncclRedOpCreatePreMulSum reads through its
+    `scalar` pointer).  A number is converted to the datatype, rounded to nearest even.  For
+    ncclBfloat16 alone an integer (a Python int or a numpy integer such as numpy.uint16) is taken as
+    the 16 bits themselves, since numpy has no bfloat16 scalar to pass."""
+    import numbers
+    import struct
+    if dtype == ncclFloat:
+        raw = struct.pack("<f", float(scalar))
+    elif dtype == ncclDouble:
+        raw = struct.pack("<d", float(scalar))
+    elif dtype == ncclInt32:
+        raw = struct.pack("<i", int(scalar))
+    elif dtype == ncclFloat16:
+        raw = struct.pack("<e", float(scalar))
+    elif dtype == ncclBfloat16:
+        if isinstance(scalar, numbers.Integral):
+            raw = struct.pack("<H", int(scalar))
+        else:
+            u = struct.unpack("<I", struct.pack("<f", float(scalar)))[0]
+            raw = struct.pack("<H", ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) & 0xFFFF)
+    else:
+        raw = bytes(8)  # an unsupported datatype: the library refuses it before it reads the scalar
+    return ctypes.create_string_buffer(raw, 8)
 
 
 class Comm:
@@ -191,6 +223,28 @@ class Comm:
         """ncclRecv: `count` elements from rank `peer`, matching its sends to this rank in call order.
         Returns the ncclResult_t."""
         return load().ncclRecv(recv_ptr, count, dtype, peer, self.handle, stream)
+
+    def redop_premul_sum_rc(self, scalar, dtype=ncclFloat, residence=ncclScalarHostImmediate):
+        """ncclRedOpCreatePreMulSum's result code (does not raise) and the handle.  `scalar`: as
+        scalar_bytes takes it (a number; for ncclBfloat16 an integer is the 16 bits)."""
+        buf = scalar_bytes(scalar, dtype)
+        op = ctypes.c_int(-1)
+        rc = load().ncclRedOpCreatePreMulSum(ctypes.byref(op), ctypes.cast(buf, ctypes.c_void_p), dtype, residence,
+                                             self.handle)
+        return rc, op.value
+
+    def redop_premul_sum(self, scalar, dtype=ncclFloat):
+        """ncclRedOpCreatePreMulSum: an op of this communicator that all_reduce, reduce_scatter and
+        reduce accept in place of ncclSum; every input is multiplied by `scalar` (one value of
+        `dtype`, the same on every rank) on its way into the sum.  Returns the handle."""
+        rc, op = self.redop_premul_sum_rc(scalar, dtype)
+        check(rc, "ncclRedOpCreatePreMulSum")
+        return op
+
+    def redop_destroy(self, op):
+        """ncclRedOpDestroy: returns the ncclResult_t.  Allowed as soon as the last call using the op
+        has been issued."""
+        return load().ncclRedOpDestroy(int(op), self.handle)
 
     def rank(self):
         r = ctypes.c_int()
