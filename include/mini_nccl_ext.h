@@ -38,6 +38,12 @@
  *                        (expert-parallel dispatch / combine: every rank sends every peer a different
  *                        number of tokens, possibly none).
  *
+ * and RCCL's rooted data movers (torch.distributed.gather / scatter, metrics or KV blocks collected
+ * on one rank, shards dealt out of one rank):
+ *
+ *   ncclGather           the root's recv = every rank's send, rank q's at element q * sendcount.
+ *   ncclScatter          rank q's recv = block q of the root's send.
+ *
  * and NCCL's point-to-point calls (pipeline parallelism, halo exchanges, batch_isend_irecv):
  *
  *   ncclSend / ncclRecv  `count` elements from one rank to another, byte for byte, with no host
@@ -81,7 +87,8 @@ extern "C" {
    and ncclReduce were added the same way; still 600: ncclAllToAll was added the same way; still 600:
    ncclAllToAllv was added the same way (detected by symbol); still 600: ncclSend, ncclRecv,
    ncclGroupStart and ncclGroupEnd were added the same way; still 600: ncclRedOpCreatePreMulSum and
-   ncclRedOpDestroy were added the same way */
+   ncclRedOpDestroy were added the same way; still 600: ncclGather and ncclScatter were added the
+   same way (detected by symbol) */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -279,6 +286,51 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
 ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclComm_t comm,
                           hipStream_t stream);
 
+/* Gather and scatter, RCCL's names and signatures.
+ *
+ * ncclGather: every rank's sendbuff holds sendcount elements; the root's recvbuff holds nranks *
+ * sendcount, and rank q's block ends up at element q * sendcount of it, byte for byte.  recvbuff is
+ * used on the root only: elsewhere it is ignored, may be NULL and is never touched.  In place on the
+ * root: sendbuff == recvbuff + root * sendcount elements.
+ * ncclScatter: the root's sendbuff holds nranks * recvcount elements and rank q's recvbuff gets block
+ * q of it, byte for byte.  sendbuff is used on the root only: elsewhere it is ignored, may be NULL and
+ * is never read.  In place on the root: recvbuff == sendbuff + root * recvcount elements.
+ * No arithmetic: any datatype ncclAllGather takes, moved by element size; NaN payloads and every other
+ * bit pattern survive.
+ *
+ * Checks, in this order (no exception crosses the boundary):
+ *  1. a NULL comm: ncclInvalidArgument;
+ *  2. a count of 0: ncclSuccess, before the datatype or the communicator is looked at;
+ *  3. a group is open: ncclInvalidUsage, the group stays open and clean (no deferred collectives);
+ *  4. an unsupported datatype: ncclInternalError, before the communicator is read;
+ *  5. with the communicator, each ncclInvalidArgument with nothing launched or negotiated and the
+ *     communicator still usable: root outside [0, nranks); a NULL buffer this rank's role needs
+ *     (ncclGather: sendbuff everywhere and recvbuff on the root; ncclScatter: recvbuff everywhere and
+ *     sendbuff on the root); on the root, byte ranges that overlap without being the in-place form.
+ *     A non-root's unused buffer is not looked at at all;
+ *  6. where the call is negotiated (the read schedule's rendezvous), ranks that disagree on the
+ *     collective, count, datatype or root get ncclInvalidUsage on every rank and the communicator
+ *     stays usable; on a forced ring these are the caller's to keep equal, as for ncclBroadcast.
+ * nranks == 1 is one device copy when the pointers differ.  Blocking mode, stream ordering, graph
+ * capture, sticky errors and the watchdog as for ncclBroadcast; pinned host buffers go through their
+ * device mapping, pageable ones through the stage (in the in-place layout ncclAllGather uses) and
+ * cannot be captured (ncclInvalidUsage).
+ *
+ * Schedules.  The read schedule where an all-reduce's larger calls would run it: column `root` and
+ * row `root` of ncclAllToAll -- every rank pushes its one block straight into block `rank` of the
+ * root's recvbuff (ncclGather), the root pushes block q of its sendbuff straight into rank q's
+ * recvbuff (ncclScatter).  Each block crosses one link once, all nranks - 1 links of the root are
+ * busy for the whole call, nranks blocks move through the root's HBM and no scratch is used (derived
+ * from the schedule, not measured: no run with ranks on distinct GPUs exists).  Otherwise the ring:
+ * a chain in ring direction that ends (ncclGather) or starts (ncclScatter) at the root, the link
+ * behind the root carrying nothing.  mncclCommInfo_t.last_algo reports mncclAlgoRead or
+ * mncclAlgoRing.  No one-shot, grid or registered-window form: a call whose buffers lie in windows is
+ * negotiated like any other and window_calls does not move. */
+ncclResult_t ncclGather(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype, int root,
+                        ncclComm_t comm, hipStream_t stream);
+ncclResult_t ncclScatter(const void* sendbuff, void* recvbuff, size_t recvcount, ncclDataType_t datatype, int root,
+                         ncclComm_t comm, hipStream_t stream);
+
 /* The variable all-to-all, RCCL's name and signature.  Counts and displacements are in elements; the
  * four arrays are host arrays of nranks entries, read before the call returns (a captured call bakes
  * them into the graph).  Elements [sdispls[q], sdispls[q] + sendcounts[q]) of rank r's send become
@@ -340,7 +392,7 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
  * leaves the communicator usable.  A group may hold several sends to one peer and several recvs from
  * one peer: they run in call order.  At most 64 operations fit in a group (kMaxGroupOps); one more is
  * ncclInvalidUsage.  DEFERRED COLLECTIVES ARE OUT OF SCOPE: ncclAllReduce, ncclReduceScatter,
- * ncclAllGather, ncclBroadcast, ncclReduce, ncclAllToAll or ncclAllToAllv called while a group is open
+ * ncclAllGather, ncclBroadcast, ncclReduce, ncclAllToAll, ncclAllToAllv, ncclGather or ncclScatter called while a group is open
  * return ncclInvalidUsage (after their NULL and count == 0 checks) with nothing launched, and the
  * group stays open and clean; with no group open they behave exactly as before.
  *

@@ -279,6 +279,49 @@ ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, nc
   }
 }
 
+// Gather and scatter (mini_nccl_ext.h): the rooted collectives' checks in their order -- the large
+// buffer may be NULL off the root, so the buffers are checked with the root where the
+// communicator's rank and size are known (Comm::collective).
+ncclResult_t ncclGather(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype, int root,
+                        ncclComm_t comm, hipStream_t stream) {
+  if (!comm) return ncclInvalidArgument;
+  if (sendcount == 0) return ncclSuccess;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
+  RoctxRange range("mini_ncclGather");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] Gather Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->gather(sendbuff, recvbuff, sendcount, (int)datatype, root, stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] Gather Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
+ncclResult_t ncclScatter(const void* sendbuff, void* recvbuff, size_t recvcount, ncclDataType_t datatype, int root,
+                         ncclComm_t comm, hipStream_t stream) {
+  if (!comm) return ncclInvalidArgument;
+  if (recvcount == 0) return ncclSuccess;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
+  RoctxRange range("mini_ncclScatter");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] Scatter Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->scatter(sendbuff, recvbuff, recvcount, (int)datatype, root, stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] Scatter Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
 // The variable all-to-all (mini_nccl_ext.h): the communicator and the four arrays, then the
 // datatype; the buffers may be NULL on a rank whose counts are all zero, so they are checked with
 // the counts where the communicator's size is known (Comm::all_to_all_v, varblock.h).

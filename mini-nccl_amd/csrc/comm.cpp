@@ -593,6 +593,8 @@ static int persistent_kernel(int algo, int coll) {
     case kCollReduce: return kKernelRootFold;
     case kCollBroadcast: return kKernelRootRelay;
     case kCollAllToAll: return kKernelExchangePush;
+    case kCollGather: return kKernelCollectPush;
+    case kCollScatter: return kKernelDealPush;
     default: return kKernelRead;
   }
 }
@@ -630,8 +632,9 @@ CollParams Comm::make_params(int algo, const void* send, void* recv, size_t chun
   p.recv = (char*)recv;
   p.coll = coll;
   // the one-chunk buffer of a half, shifted so that chunk `rank` of it is the buffer itself
-  if (coll == kCollReduceScatter) p.recv -= (size_t)rank_ * chunk_bytes;
-  if (coll == kCollAllGather) p.send -= (size_t)rank_ * chunk_bytes;
+  // (gather and scatter alike: the one-block buffer is block `rank` of the root's large one)
+  if (coll == kCollReduceScatter || coll == kCollScatter) p.recv -= (size_t)rank_ * chunk_bytes;
+  if (coll == kCollAllGather || coll == kCollGather) p.send -= (size_t)rank_ * chunk_bytes;
   // the rooted collectives: root_fold stores into the ROOT's recv on every rank (this rank's
   // mapping of it); the ring's broadcast moves the whole buffer as one chunk down the chain
   p.root = root;
@@ -681,7 +684,8 @@ CollParams Comm::make_params(int algo, const void* send, void* recv, size_t chun
 // The call path of ncclAllReduce (coll 0: `count` elements in send and in recv) and of its halves
 // (schedule.h Coll; `count` per rank): ncclReduceScatter's send and ncclAllGather's recv hold
 // n * count elements, the other buffer one chunk of `count`.  ncclAllToAll (coll 5): both buffers
-// hold n blocks of `count` elements, and a chunk is one block.
+// hold n blocks of `count` elements, and a chunk is one block.  ncclGather / ncclScatter (coll 7 / 8):
+// a chunk is one block of `count` elements too; the root's large buffer holds n of them.
 ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
                               hipStream_t stream, int root, uint64_t scalar) {
   if (sticky_ != ncclSuccess) return sticky_;
@@ -693,15 +697,51 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
   const bool half = coll == kCollReduceScatter || coll == kCollAllGather;
   // a2a: ncclAllToAll (`count` elements per block, n blocks in both buffers); the same schedules
   const bool a2a = coll == kCollAllToAll;
-  const bool is_root = rooted && rank_ == root;
+  // gs: ncclGather / ncclScatter (`count` elements per block; the root's large buffer -- Gather's
+  // recv, Scatter's send -- holds n blocks, every rank's other buffer one); the same schedules
+  const bool gs = coll == kCollGather || coll == kCollScatter;
+  const bool is_root = (rooted || gs) && rank_ == root;
   const char* const coll_name = coll == kCollReduceScatter ? "ncclReduceScatter"
                                 : coll == kCollAllGather   ? "ncclAllGather"
                                 : coll == kCollBroadcast   ? "ncclBroadcast"
                                 : coll == kCollReduce      ? "ncclReduce"
                                 : coll == kCollAllToAll    ? "ncclAllToAll"
+                                : coll == kCollGather      ? "ncclGather"
+                                : coll == kCollScatter     ? "ncclScatter"
                                                            : "ncclAllReduce";
   // bytes: the larger buffer's (the all-reduce's and the rooted collectives': both)
-  const size_t bytes = count * (size_t)esz * (half || a2a ? (size_t)nranks_ : 1);
+  const size_t bytes = count * (size_t)esz * (half || a2a || gs ? (size_t)nranks_ : 1);
+  if (gs) {
+    // the caller's errors, in the rooted collectives' order: nothing launched, nothing negotiated
+    if (root < 0 || root >= nranks_) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: root %d is outside [0, %d)\n", rank_, coll_name, root, nranks_);
+      return ncclInvalidArgument;
+    }
+    // the buffers this rank's role needs: the one-block buffer everywhere, the large one on the root
+    const bool need_send = coll == kCollGather || is_root, need_recv = coll == kCollScatter || is_root;
+    if ((need_send && !send) || (need_recv && !recv)) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: %s is NULL\n", rank_, coll_name, need_send && !send ? "sendbuff" : "recvbuff");
+      return ncclInvalidArgument;
+    }
+    if (is_root) {
+      // in place as NCCL defines it (the one-block buffer is block `root` of the large one); any
+      // other overlap of the two byte ranges is the caller's error
+      const size_t cb = count * (size_t)esz;
+      const uintptr_t s0 = (uintptr_t)send, r0 = (uintptr_t)recv;
+      const size_t sb = coll == kCollScatter ? bytes : cb, rb = coll == kCollScatter ? cb : bytes;
+      const bool in_place = coll == kCollScatter ? r0 == s0 + (size_t)rank_ * cb : s0 == r0 + (size_t)rank_ * cb;
+      if (!in_place && s0 < r0 + rb && r0 < s0 + sb) {
+        fprintf(stderr, "[Mini-NCCL] rank %d: %s: send and recv overlap and the call is not in place\n", rank_,
+                coll_name);
+        return ncclInvalidArgument;
+      }
+    } else {
+      // a non-root's large buffer is ignored, never looked at: its one-block buffer stands in for it
+      // in the rendezvous and in the kernel's arguments, as for the rooted pair below
+      if (coll == kCollGather) recv = const_cast<void*>(send);
+      else send = recv;
+    }
+  }
   if (rooted) {
     // the caller's errors, in this order: nothing launched, nothing negotiated
     if (root < 0 || root >= nranks_) {
@@ -758,7 +798,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
   const int n = nranks_;
   uint32_t seq = 0;  // this call's kernel (0: the call launches none)
   // (rooted: ceil -- the trailing chunks are short or empty and there is no unreduced tail)
-  const size_t chunk = half || a2a ? count : rooted ? (count + (size_t)n - 1) / (size_t)n
+  const size_t chunk = half || a2a || gs ? count : rooted ? (count + (size_t)n - 1) / (size_t)n
                        : n > 0 ? count / (size_t)n : 0;  // mini_nccl.cu:69
   const size_t chunk_bytes = chunk * (size_t)esz;
   if (n == 1 || chunk == 0) {
@@ -789,7 +829,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // (nor has a pre-multiplied sum: the one-shot kernel folds the four built-in ops only, so such a
     // call is one the one-shot does not fit -- the read schedule where it can run, else the ring; the
     // op's kind is the same on every rank, like the call's size)
-    const bool os_form = !half && !rooted && !a2a && op != kPreMulSum;
+    const bool os_form = !half && !rooted && !a2a && !gs && op != kPreMulSum;
     const bool oneshot = os_form && algo_ == 3 && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), true);
     const bool small = os_form && auto_ && oneshot_fits(chunk_bytes, n, run_pipes(), wave_slice(), false);
     // (auto, and a forced one-shot's larger calls, only where the topology allows the read
@@ -800,7 +840,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // registered windows: the read schedule with no host rendezvous (no record to wait for, no
     // pointer query) -- every rank promised the same windows and offsets, the kernel checks it
     // (all-reduce only: a half whose buffers lie in windows is negotiated like any other call)
-    const Window* win_s = !half && !rooted && !a2a && read_sched && window_fast_ && !windows_.empty() ? find_window(send, bytes) : nullptr;
+    const Window* win_s = !half && !rooted && !a2a && !gs && read_sched && window_fast_ && !windows_.empty() ? find_window(send, bytes) : nullptr;
     const Window* win_r = win_s ? find_window(recv, bytes) : nullptr;
     if (win_s && win_r) {
       const uint64_t os = (uint64_t)((const char*)send - win_s->base), orv = (uint64_t)((char*)recv - win_r->base);
@@ -854,12 +894,14 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       const size_t a2a_recv = a2a && rs == Reach::kStaged && rr == Reach::kStaged ? (bytes + 255) & ~(size_t)255 : 0;
       ensure_stage(a2a_recv + bytes, stream);
       // a half is staged in its in-place layout: the one-chunk buffer is chunk `rank` of the stage
-      const size_t s_off = coll == kCollAllGather ? mine : 0, r_off = coll == kCollReduceScatter ? mine : a2a_recv;
+      // (gather and scatter too: the one-block buffer is block `rank` of the stage on every rank)
+      const size_t s_off = coll == kCollAllGather || coll == kCollGather ? mine : 0,
+                   r_off = coll == kCollReduceScatter || coll == kCollScatter ? mine : a2a_recv;
       if (rs == Reach::kStaged) {
-        // (Broadcast: only the root's send holds anything -- the others' stands for their recv)
-        if (coll != kCollBroadcast || is_root)
-          hip_check(hipMemcpyAsync(stage_ + s_off, send, coll == kCollAllGather ? chunk_bytes : bytes, hipMemcpyDefault,
-                                   stream), "stage in");
+        // (Broadcast, Scatter: only the root's send holds anything -- the others' stands for their recv)
+        if ((coll != kCollBroadcast && coll != kCollScatter) || is_root)
+          hip_check(hipMemcpyAsync(stage_ + s_off, send, coll == kCollAllGather || coll == kCollGather ? chunk_bytes : bytes,
+                                   hipMemcpyDefault, stream), "stage in");
         ksend = stage_ + s_off;
       }
       if (rr == Reach::kStaged) krecv = stage_ + r_off;  // also in place when send is staged too
@@ -872,7 +914,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // buffer and never touches the tail, api.cpp:173-175 + mini_nccl.cu:69); the kernels
     // write every other element of recv and copy the tail themselves (kernels.hip copy_tail)
     const size_t body = chunk_bytes * (size_t)n;
-    const size_t tail = !half && !rooted && !a2a && ksend != krecv && bytes > body ? bytes - body : 0;
+    const size_t tail = !half && !rooted && !a2a && !gs && ksend != krecv && bytes > body ? bytes - body : 0;
     // 16-byte vector path whenever every message's local base is dword-aligned (vectors may
     // straddle 16-byte boundaries on the local side; each message's last len % 16 bytes go
     // element by element); element-wise path otherwise (2-byte types with odd chunks)
@@ -896,7 +938,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
                             [this] { wait_previous_call(); }, psend, precv, &vec_all,
                             // (with the collective: ranks that call different ones get kMismatch)
                             // (and a rooted one's root: ranks that differ in it get kMismatch too)
-                            half || rooted || a2a ? ((auto_ ? 0xff : algo_) | coll << 8 | (rooted ? root << 16 : 0))
+                            half || rooted || a2a || gs ? ((auto_ ? 0xff : algo_) | coll << 8 | (rooted || gs ? root << 16 : 0))
                             : auto_        ? -1
                                            : algo_,
                             nullptr, nullptr,
@@ -944,12 +986,18 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     if (a2a && algo == 0)
       hip_check(hipMemcpyAsync((char*)krecv + mine, (const char*)ksend + mine, chunk_bytes, hipMemcpyDefault, stream),
                 "own block");
+    // the ring's gather and scatter move the other ranks' blocks only: the root's own block reaches
+    // its place the same way when the call is not in place (collect_push / deal_push store it themselves)
+    if (coll == kCollGather && is_root && algo == 0 && (const char*)ksend != (const char*)krecv + mine)
+      hip_check(hipMemcpyAsync((char*)krecv + mine, ksend, chunk_bytes, hipMemcpyDefault, stream), "root's own block");
+    if (coll == kCollScatter && is_root && algo == 0 && (const char*)krecv != (const char*)ksend + mine)
+      hip_check(hipMemcpyAsync(krecv, (const char*)ksend + mine, chunk_bytes, hipMemcpyDefault, stream), "root's own block");
     launch(algo, ksend, krecv, chunk_bytes, dtype, op, stream, seq, vec, psend, precv, tail, 0, coll, root,
            rooted ? bytes : 0, scalar);
-    // (Reduce: only the root's recv is written -- the others' stands for their send)
-    if (rr == Reach::kStaged && (coll != kCollReduce || is_root))
-      hip_check(hipMemcpyAsync(recv, krecv, coll == kCollReduceScatter ? chunk_bytes : bytes, hipMemcpyDefault, stream),
-                "stage out");
+    // (Reduce, Gather: only the root's recv is written -- the others' stands for their send)
+    if (rr == Reach::kStaged && ((coll != kCollReduce && coll != kCollGather) || is_root))
+      hip_check(hipMemcpyAsync(recv, krecv, coll == kCollReduceScatter || coll == kCollScatter ? chunk_bytes : bytes,
+                               hipMemcpyDefault, stream), "stage out");
   }
   return end_call(scope, stream, seq);
 }

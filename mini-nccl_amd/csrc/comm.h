@@ -84,6 +84,20 @@ class Comm {
     return collective(kCollAllToAll, send, recv, count, dtype, kSum, stream);
   }
 
+  // Gather and scatter (RCCL's ncclGather / ncclScatter; `count` elements per block): the root's
+  // recv gets rank q's send as block q; rank q's recv gets block q of the root's send, byte for
+  // byte.  The large buffer (Gather's recv, Scatter's send) is used on the root only: elsewhere it
+  // is ignored and may be NULL.  The schedule choice is the halves': the read schedule (kernels.hip
+  // collect_push / deal_push), else the ring (schedule.h coll_op).  In place on the root as NCCL
+  // defines it; root outside [0, n), a NULL buffer the role needs, or any other overlap on the
+  // root: ncclInvalidArgument, nothing launched or negotiated.
+  ncclResult_t gather(const void* send, void* recv, size_t count, int dtype, int root, hipStream_t stream) {
+    return collective(kCollGather, send, recv, count, dtype, kSum, stream, root);
+  }
+  ncclResult_t scatter(const void* send, void* recv, size_t count, int dtype, int root, hipStream_t stream) {
+    return collective(kCollScatter, send, recv, count, dtype, kSum, stream, root);
+  }
+
   // The variable all-to-all (RCCL's ncclAllToAllv; counts and displacements in elements, host arrays
   // of n entries read before the call returns): elements [sdispls[q], +sendcounts[q]) of this rank's
   // send become elements [rdispls[r], +recvcounts[r]) of rank q's recv.  A call path of its own
@@ -187,8 +201,8 @@ class Comm {
   // every rank's ncclAllToAllv row where the board is unavailable: over the bootstrap, like
   // mncclCommLinkProbe's records.  False: the ranks disagree on the collective or the datatype
   bool gather_rows(const VarRow& mine, int dtype, VarRow* rows);
-  // the one call path of the six collectives; count: the all-reduce's and the rooted ones', per
-  // rank for the halves, per block for the all-to-all
+  // the one call path of the eight collectives; count: the all-reduce's and the rooted ones', per
+  // rank for the halves, per block for the all-to-all, the gather and the scatter
   ncclResult_t collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
                           hipStream_t stream, int root = 0, uint64_t scalar = 0);
   // a kPreMulSum call on a communicator of one rank: recv = round(scalar * send) over `count` elements

@@ -38,7 +38,9 @@ struct CollParams {
   int32_t coll;            // schedule.h Coll (3 / 4: below): 0 all-reduce, 1 reduce-scatter (recv holds one chunk: the
                            // host passes recv - rank * chunk_bytes), 2 all-gather (send holds one
                            // chunk: the host passes send - rank * chunk_bytes), 5 all-to-all (a chunk is
-                           // one block of the n in send and in recv).  In what was padding:
+                           // one block of the n in send and in recv), 7 gather (send shifted as
+                           // the all-gather's), 8 scatter (recv shifted as the reduce-scatter's;
+                           // a chunk is one block for both).  In what was padding:
                            // the struct's size and every other offset are the all-reduce's
   uint64_t timeout_ticks;  // s_memrealtime ticks (100 MHz)
   int32_t sys_fence;       // system-scope release fence before each ready flag
@@ -92,13 +94,19 @@ enum PersistentKernel : int {
   // block of the n in send and in recv): exchange_push stores block q of send into block `rank` of
   // rank q's recv, for every q (by element size: no arithmetic)
   kKernelExchangePush,
+  // the read schedule's gather and scatter (p.coll 7 / 8; the same persistent form and protocol; a
+  // chunk is one block): collect_push stores send into block `rank` of the ROOT's recv; deal_push,
+  // on the root, stores block q of send into rank q's recv, for every q (by element size)
+  kKernelCollectPush,
+  kKernelDealPush,
 };
 
 // Launchers return hipSuccess or the launch error; dtype/op must be supported
 // (checked by the caller).  vec = 16-byte path (all offsets 16-byte aligned).
 // op: one of the four built-ins, or kPreMulSum for the kernels that fold (p.scale the scalar).
 // launch_persistent refuses a p.coll that is not the kernel's, a root outside [0, n) for the
-// rooted kernels and n < 2 for the all-to-all; the kernels that only copy ignore op.
+// rooted kernels (gather and scatter among them) and n < 2 for the all-to-all, the gather and the
+// scatter; the kernels that only copy ignore op.
 hipError_t launch_persistent(int kernel, int dtype, int op, bool vec, int channels, int threads,
                              const CollParams& p, hipStream_t stream);
 // ncclAllToAllv on the read schedule (kernels.hip varblock_push): the per-destination blocks of this

@@ -24,6 +24,10 @@
 //  exchange_push  the all-to-all (ncclAllToAll) on the same protocol: every rank pushes block q of
 //                 its own send into rank q's recv, so every block crosses one link once.  Its
 //                 fallback is ring_kernel with a table of hops (schedule.h coll_op).
+//  collect_push / deal_push   gather and scatter (ncclGather / ncclScatter) on the same protocol:
+//                 column `root` and row `root` of the all-to-all -- every rank pushes its one block
+//                 into the root's recv; the root pushes block q of its send into rank q's recv.
+//                 Their fallback is ring_kernel with a chain's table (schedule.h coll_op).
 //  varblock_push  the variable all-to-all (ncclAllToAllv) on the same protocol: exchange_push with a
 //                 length and two offsets per destination, the slices cut for the largest block of
 //                 the whole matrix.  Its fallback is the ring's all-to-all on padded blocks.
@@ -600,7 +604,7 @@ __device__ __forceinline__ void ring_body(const CollParams& __restrict__ p) {
   const u64* my_credit = p.mbox + mbox_credit(n, C, next, w);
   u64* out_ready = p.peer_mbox[next] + mbox_ready(C, r, w);
   u64* out_credit = p.peer_mbox[prev] + mbox_credit(n, C, r, w);
-  const int nops = coll_num_ops(coll, n);
+  const int nops = coll_num_ops(coll, n, r, root);  // (gather / scatter: by the rank's place in the chain)
 
   for (uint32_t it = 0; it < p.iters; ++it) {
     const u64 s = (u64)it * A + w;
@@ -1342,6 +1346,139 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) exchange_push(C
   });
 }
 
+// ---------------------------------------------------------------- gather and scatter
+// ncclGather (collect_push) and ncclScatter (deal_push) on device buffers every rank can share, in
+// read_half's protocol message for message: column `root` and row `root` of the all-to-all.  A chunk
+// is one block; the root's large buffer holds n of them.
+//   Gather: pipeline w of rank r loads slice s of its one block from its own send (p.send is
+//   send - r * chunk_bytes, Comm::make_params, as for the all-gather) and pushes it into block r of
+//   the ROOT's recv; the root stores its own block into its own recv unless the call is in place
+//   (p.send == p.recv then).  A non-root writes nothing of its own, and all of its pipelines drive
+//   its one link to the root.
+//   Scatter: the root's pipeline w loads slice s of EVERY block q from its send and pushes it into
+//   rank q's recv -- the destination side gets NO block offset: peer_recv[q] is rank q's recv itself
+//   -- its own block into its own recv (p.recv is recv - r * chunk_bytes, as for the
+//   reduce-scatter; in place p.recv == p.send) unless the call is in place.  The destinations run
+//   in direct_peer order from peer w mod n-1, this rank itself last, so the root's pipelines spread
+//   over all its links.  The other ranks run START ("my recv is writable") and DONE (whose wait
+//   means "my block has landed") only.
+// Pushes, not pulls, for exchange_push's reason; each link into or out of the root carries exactly
+// one block, so relaying through other ranks would gain nothing.  Only rank r ever writes block r
+// of the root's recv (gather); only the root writes any recv (scatter); nobody reads a recv inside
+// the call.  n blocks move through the root's HBM, one through every other rank's (derived from the
+// schedule, not measured: no run with ranks on distinct GPUs exists).
+//
+// 16-byte vectors of one slice, exchange_push_vec's loop over K (source, destination) pairs the
+// caller describes: V vectors per lane per batch, two batches in flight per wave -- the next
+// batch's loads leave before this one is stored, across pairs too, unconditionally (the vmcnt
+// reason read_fold_all explains).  Past the slice the loads fall outside the buffer resource,
+// return 0 and touch nothing; src_of(k) and dst_of(k) for k >= K must be empty resources.  K >= 1.
+constexpr int kDealV = 8;
+
+template <int V, typename Src, typename Dst>
+__device__ __forceinline__ void push_pairs_vec(int K, const Src& src_of, const Dst& dst_of, uint32_t nvec, int lane) {
+  constexpr uint32_t step = 64 * V;
+  auto load = [&](v4u(&x)[V], rsrc_t s, uint32_t b) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) x[u] = ld_nt16(s, (b + (uint32_t)(u * 64 + lane)) * 16);
+  };
+  auto store = [&](v4u(&x)[V], rsrc_t d, uint32_t b) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) st_slot16(d, (b + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+  };
+  int k = 0;       // the batch about to be stored: pair k, vectors from b
+  uint32_t b = 0;
+  rsrc_t src = src_of(0), dst = dst_of(0);
+  v4u xa[V], xb[V];
+  // loads the batch after (k, b) into nxt, stores cur, moves on; false after the last batch
+  auto turn = [&](v4u(&cur)[V], v4u(&nxt)[V]) {
+    int k2 = k;
+    uint32_t b2 = b + step;
+    if (b2 >= nvec) {
+      b2 = 0;
+      src = src_of(++k2);
+    }
+    load(nxt, src, b2);
+    store(cur, dst, b);
+    if (k2 != k) dst = dst_of(k2);
+    k = k2;
+    b = b2;
+    return k < K;
+  };
+  load(xa, src, 0);
+  while (turn(xa, xb) && turn(xb, xa)) {
+  }
+}
+
+// the same pairs' bytes [done, nbytes), element by element
+template <int ESZ, typename Src, typename Dst>
+__device__ __forceinline__ void push_pairs_scalar(int K, const Src& src_of, const Dst& dst_of, uint32_t done,
+                                                  uint32_t nbytes, int lane) {
+  typedef Scal<ESZ> S;
+  const uint32_t ne = nbytes / ESZ;
+  for (int k = 0; k < K; ++k) {
+    const rsrc_t src = src_of(k), dst = dst_of(k);
+    for (uint32_t i = done / ESZ + (uint32_t)lane; i < ne; i += 64) S::st(dst, i * (uint32_t)ESZ, S::ld(src, i * (uint32_t)ESZ));
+  }
+}
+
+// Gather: slice `nbytes` at byte coff = r * chunk_bytes + s * slice_bytes of the root's recv
+template <int ESZ, bool VEC>
+__device__ __forceinline__ void collect_slice(const CollParams& p, uint64_t coff, uint32_t nbytes, int lane) {
+  const bool is_root = p.rank == p.root;
+  if (is_root && p.send == p.recv) return;  // the root in place: its block already is in its recv
+  const char* from = p.send + coff;
+  char* to = (is_root ? p.recv : const_cast<char*>(p.peer_recv[p.root])) + coff;
+  uint32_t span = 0;  // the bytes the one pair's resources cover: the whole vectors, then the slice
+  auto src_of = [&](int k) { return make_rsrc(from, k < 1 ? span : 0u); };
+  auto dst_of = [&](int k) { return make_rsrc(to, k < 1 ? span : 0u); };
+  const uint32_t vb = VEC ? nbytes & ~15u : 0u;
+  span = vb;
+  if (vb) push_pairs_vec<kDealV>(1, src_of, dst_of, vb >> 4, lane);
+  if (vb == nbytes) return;
+  span = nbytes;
+  push_pairs_scalar<ESZ>(1, src_of, dst_of, vb, nbytes, lane);
+}
+
+// Scatter, on the root: slice `nbytes` at byte `soff` of every block
+template <int ESZ, bool VEC>
+__device__ __forceinline__ void deal_slice(const CollParams& p, uint64_t soff, uint32_t nbytes, int lane) {
+  const int n = p.n, r = p.rank, first = wave_id().w % (n - 1);
+  const u64 cb = p.chunk_bytes;
+  const int K = n - 1 + (p.send != p.recv ? 1 : 0);  // in place: the root's block already is in its recv
+  // pair k: the peers in direct_peer order from peer w mod n-1, then this rank itself
+  auto dest = [&](int k) { return k < n - 1 ? direct_peer(n, r, 1 + (first + k) % (n - 1)) : r; };
+  uint32_t span = 0;  // the bytes the pairs' resources cover: the whole vectors, then the slice
+  auto src_of = [&](int k) { return make_rsrc(p.send + (u64)dest(k) * cb + soff, k < K ? span : 0u); };
+  auto dst_of = [&](int k) {
+    return make_rsrc(k < n - 1 ? const_cast<char*>(p.peer_recv[dest(k)]) + soff : p.recv + (u64)r * cb + soff,
+                     k < K ? span : 0u);
+  };
+  const uint32_t vb = VEC ? nbytes & ~15u : 0u;
+  span = vb;
+  if (vb) push_pairs_vec<kDealV>(K, src_of, dst_of, vb >> 4, lane);
+  if (vb == nbytes) return;
+  span = nbytes;
+  push_pairs_scalar<ESZ>(K, src_of, dst_of, vb, nbytes, lane);
+}
+
+// No arithmetic, so by element size only.  launch_persistent refuses a root outside [0, n).
+template <int ESZ, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) collect_push(CollParams p) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { collect_slice<ESZ, VEC>(p, coff, len, lane); });
+}
+
+// read_half hands the slice's offset in chunk `rank`; the slice's offset within a block is what
+// every block shares.
+template <int ESZ, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) deal_push(CollParams p) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) {
+    if (p.rank == p.root) deal_slice<ESZ, VEC>(p, coff - (u64)p.rank * p.chunk_bytes, len, lane);
+  });
+}
+
 // ---------------------------------------------------------------- the variable all-to-all
 // ncclAllToAllv (varblock_push) on device buffers every rank can share, in read_half's protocol
 // message for message: the block this rank sends to rank q has its own length, its own offset in
@@ -1997,6 +2134,8 @@ hipError_t launch_persistent(int kernel, int dtype, int op, bool vec, int C, int
     case kKernelRootFold: return p.coll == kCollReduce && root_ok ? FOLDS(root_fold, scaled_root) : hipErrorInvalidValue;
     case kKernelRootRelay: return p.coll == kCollBroadcast && root_ok ? COPIES(root_relay) : hipErrorInvalidValue;
     case kKernelExchangePush: return p.coll == kCollAllToAll && p.n >= 2 ? COPIES(exchange_push) : hipErrorInvalidValue;
+    case kKernelCollectPush: return p.coll == kCollGather && root_ok && p.n >= 2 ? COPIES(collect_push) : hipErrorInvalidValue;
+    case kKernelDealPush: return p.coll == kCollScatter && root_ok && p.n >= 2 ? COPIES(deal_push) : hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
 #undef COPIES

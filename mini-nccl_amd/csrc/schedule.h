@@ -137,12 +137,33 @@ MNCCL_HD RingOp ring_op(int n, int r, int k) {
 //
 // The variable all-to-all (ncclAllToAllv, kCollAllToAllV) has no ring table of its own: off the read
 // schedule it runs the table above on blocks padded to the largest one (Comm::all_to_all_v).
+//
+// Gather and scatter (ncclGather / ncclScatter; a chunk is one block of `count` elements, the root's
+// large buffer holds n of them; `root` is rank-uniform).  Both are a chain in ring direction, with
+// pos = (r - root) mod n the rank's place in it; the op count and each link's message count depend
+// on pos, and each link's counters advance by what it carried (coll_tx_msgs / coll_rx_msgs).
+//   Gather (blocks travel towards the root, which sits at the chain's end; the link root -> root+1
+//   carries nothing; the host passes send - r * chunk_bytes, as for the all-gather):
+//     pos p >= 1 : kSend of the own block as message 0, then kForward of messages 0 .. p-2 from
+//                  behind, sent on as messages 1 .. p-1 (p ops, p messages sent, p - 1 received)
+//     the root   : kCopy of messages 0 .. n-2 into the blocks of the ranks at pos n-1, n-2, .., 1
+//   Scatter (blocks travel away from the root; the link root-1 -> root carries nothing; the host
+//   passes recv - r * chunk_bytes, as for the reduce-scatter):
+//     the root   : kSend of the blocks for pos n-1, .., 1 as messages 0 .. n-2
+//     pos p >= 1 : kForward of messages 0 .. n-p-2, then kCopy of message n-p-1 into its recv
+//                  (n - p ops and messages received, n - p - 1 sent)
+//   The root's own block reaches its place by a device copy before the launch when the call is not
+//   in place, as the ring's all-gather gets its own chunk.
 enum Coll : int {
   kCollAllReduce = 0, kCollReduceScatter = 1, kCollAllGather = 2, kCollBroadcast = 3, kCollReduce = 4, kCollAllToAll = 5,
-  kCollAllToAllV = 6
+  kCollAllToAllV = 6, kCollGather = 7, kCollScatter = 8
 };
 
-MNCCL_HD int coll_num_ops(int coll, int n) {
+// r, root: gather and scatter only (their op count depends on the rank's place in the chain; the
+// defaults give the root's, the largest)
+MNCCL_HD int coll_num_ops(int coll, int n, int r = 0, int root = 0) {
+  if (coll == kCollGather) return r == root ? n - 1 : mod_n(r - root, n);
+  if (coll == kCollScatter) return r == root ? n - 1 : n - mod_n(r - root, n);
   return coll == kCollReduceScatter ? n + 1
          : coll == kCollAllGather   ? n
          : coll == kCollBroadcast   ? 1
@@ -158,14 +179,38 @@ MNCCL_HD int coll_msgs_per_iter(int coll, int n) {
                                     : ring_msgs_per_iter(n);
 }
 // messages per iteration rank r sends to r+1 / receives from r-1: what its counters advance by
+// (gather and scatter: a link carries as many blocks as lie behind it in the chain)
 MNCCL_HD int coll_tx_msgs(int coll, int n, int r, int root) {
+  if (coll == kCollGather) return mod_n(r - root, n);
+  if (coll == kCollScatter) return n - 1 - mod_n(r - root, n);
   return coll == kCollBroadcast && mod_n(r - root, n) == n - 1 ? 0 : coll_msgs_per_iter(coll, n);
 }
 MNCCL_HD int coll_rx_msgs(int coll, int n, int r, int root) {
+  if (coll == kCollGather) return r == root ? n - 1 : mod_n(r - root, n) - 1;
+  if (coll == kCollScatter) return r == root ? 0 : n - mod_n(r - root, n);
   return coll == kCollBroadcast && r == root ? 0 : coll_msgs_per_iter(coll, n);
 }
 MNCCL_HD RingOp coll_op(int coll, int n, int r, int k, int root = 0) {
   RingOp o;
+  if (coll == kCollGather) {
+    const int pos = mod_n(r - root, n);
+    if (pos == 0) {  // message k is the block of the rank at pos n-1-k
+      o.kind = kCopy; o.chunk = mod_n(root + n - 1 - k, n); o.send_msg = -1; o.recv_msg = k;
+    } else {
+      o.kind = k == 0 ? kSend : kForward; o.chunk = r; o.send_msg = k; o.recv_msg = k - 1;  // (k == 0: -1)
+    }
+    return o;
+  }
+  if (coll == kCollScatter) {
+    const int pos = mod_n(r - root, n);
+    if (pos == 0) {  // message k is the block for the rank at pos n-1-k
+      o.kind = kSend; o.chunk = mod_n(root + n - 1 - k, n); o.send_msg = k; o.recv_msg = -1;
+    } else {
+      const bool last = k == n - pos - 1;
+      o.kind = last ? kCopy : kForward; o.chunk = r; o.send_msg = last ? -1 : k; o.recv_msg = k;
+    }
+    return o;
+  }
   if (coll == kCollBroadcast) {
     const int pos = mod_n(r - root, n);  // place in the chain
     o.kind = pos == 0 ? kSend : pos < n - 1 ? kCopySend : kCopy;

@@ -11,6 +11,8 @@
 // ring's chain and masked ring, kernels.hip root_relay / root_fold), interleaved with the others.
 // mnccl_sim_mixed adds ncclAllToAll (the ring's hop table, kernels.hip exchange_push) to those five.
 // mnccl_sim_varblock adds ncclAllToAllv (kernels.hip varblock_push; the ring on padded blocks).
+// mnccl_sim_all_collectives adds ncclGather / ncclScatter (the ring's chains, kernels.hip collect_push /
+// deal_push) to those seven.
 // mnccl_sim_p2p adds ncclSend / ncclRecv groups (kernels.hip p2p_kernel, one wave per (pair, pipeline)
 // from p2p.h's argument builder), every rank running its own list of launches, between collectives.
 // fp32 only (the schedule does not depend on the element type); ops as reference
@@ -48,6 +50,7 @@ struct World {
   uint32_t iters;
   std::vector<const float*> send;
   std::vector<float*> recv;
+  std::vector<float*> peer_recv;              // every rank's recv as its peers map it (CollParams::peer_recv: unshifted)
   std::vector<std::vector<char>> scratch;     // per rank
   std::vector<std::vector<uint64_t>> mbox;    // per rank
   std::vector<std::vector<uint64_t>> tx_seq, rx_seq;  // per rank: [peer * C + w]
@@ -118,7 +121,7 @@ bool ring_step(World& W, Prog& P) {
   }
   if (o.send_msg >= 0) W.ready(next, r, w) = sseq + 1;
   if (o.recv_msg >= 0) W.credit(prev, r, w) = rseq + 1;
-  if (++P.k == coll_num_ops(W.coll, n)) {
+  if (++P.k == coll_num_ops(W.coll, n, r, W.root)) {
     P.k = 0;
     if (++P.it == W.iters) P.done = true;
   }
@@ -203,6 +206,32 @@ bool read_step(World& W, Prog& P) {
       memcpy((char*)W.recv[q] + mine, (const char*)W.send[r] + (uint64_t)q * W.chunk_bytes + soff, (size_t)len);
     }
   };
+  // kernels.hip collect_push: slice `it` of this rank's one block (W.send[r] is send - r * chunk_bytes)
+  // into block r of the ROOT's recv; the root's own block unless its call is in place (seen from the
+  // shifted pointers, as the kernel does); a non-root writes nothing of its own
+  auto collect = [&](uint32_t it) {
+    const uint64_t s = (uint64_t)it * W.A + w;
+    const uint64_t len = slice_len(W.chunk_bytes, W.slice, s);
+    const uint64_t coff = (uint64_t)r * W.chunk_bytes + s * W.slice;
+    if (!len) return;
+    if (r == W.root && (const void*)W.send[r] == (const void*)W.recv[r]) return;
+    memcpy((char*)W.recv[W.root] + coff, (const char*)W.send[r] + coff, (size_t)len);
+  };
+  // kernels.hip deal_push, on the root only: slice `it` of EVERY block q of its send into rank q's
+  // recv with no block offset on the destination side (W.peer_recv: the unshifted buffers), the
+  // peers in direct_peer order from peer w mod n-1, its own block last (W.recv[r] is recv - r *
+  // chunk_bytes) unless the call is in place
+  auto deal = [&](uint32_t it) {
+    const uint64_t s = (uint64_t)it * W.A + w;
+    const uint64_t len = slice_len(W.chunk_bytes, W.slice, s), soff = s * W.slice;
+    if (!len || r != W.root) return;
+    const int K = n - 1 + ((const void*)W.send[r] != (const void*)W.recv[r] ? 1 : 0);
+    for (int k = 0; k < K; ++k) {
+      const int q = k < n - 1 ? direct_peer(n, r, 1 + (w % (n - 1) + k) % (n - 1)) : r;
+      char* to = k < n - 1 ? (char*)W.peer_recv[(size_t)q] + soff : (char*)W.recv[r] + (uint64_t)r * W.chunk_bytes + soff;
+      memcpy(to, (const char*)W.send[r] + (uint64_t)q * W.chunk_bytes + soff, (size_t)len);
+    }
+  };
   // kernels.hip varblock_push: slice `it` of the call's largest-block geometry; of the block for each
   // destination it covers schedule.h varblock_len bytes (0 once that block is exhausted)
   auto varexchange = [&](uint32_t it) {
@@ -253,6 +282,8 @@ bool read_step(World& W, Prog& P) {
         else if (W.coll == kCollBroadcast) relay(P.it++);
         else if (W.coll == kCollAllToAll) exchange(P.it++);
         else if (W.coll == kCollAllToAllV) varexchange(P.it++);
+        else if (W.coll == kCollGather) collect(P.it++);
+        else if (W.coll == kCollScatter) deal(P.it++);
         else fold(P.it++);
       }
       if (P.it >= W.iters) P.j = 3;
@@ -340,9 +371,10 @@ int run_call(World& W, int code, int coll, uint64_t count, const float* const* s
              int root = 0) {
   const int n = W.n, channels = W.C;
   const bool rooted = coll == kCollBroadcast || coll == kCollReduce;
+  const bool gs = coll == kCollGather || coll == kCollScatter;
   const bool half = coll != kCollAllReduce;  // (the rooted ones too: ring and persistent read only)
   if (code > 4 || code == 3 || (half && code != 0 && code != 2)) return -2;
-  if (rooted && (root < 0 || root >= n)) return -2;
+  if ((rooted || gs) && (root < 0 || root >= n)) return -2;
   const int a = code >= 2 ? 2 : code;  // 0 ring, 1 one-shot, 2 read
   const uint64_t chunk = rooted ? (count + (uint64_t)n - 1) / (uint64_t)n : half ? count : count / (uint64_t)n;
   W.coll = coll;
@@ -353,6 +385,31 @@ int run_call(World& W, int code, int coll, uint64_t count, const float* const* s
   W.send.assign(send, send + n);
   W.recv.assign(recv, recv + n);
   W.own.assign((size_t)n, 1);
+  if (gs) {
+    // Comm::collective: a non-root's large buffer (it may be NULL) is stood in for by its one-block
+    // buffer; one rank: a copy; on the ring the root's own block reaches its place by a copy before
+    // the launch when the call is not in place; then the one-block buffer's pointer shifted by r
+    // blocks (Comm::make_params) -- the peers' mappings of a recv stay unshifted
+    for (int r = 0; r < n; ++r) {
+      if (r == root) continue;
+      if (coll == kCollGather) W.recv[r] = const_cast<float*>(W.send[r]);
+      else W.send[r] = W.recv[r];
+    }
+    if (n == 1) {
+      if ((const void*)send[0] != (const void*)recv[0]) memcpy(recv[0], send[0], (size_t)W.chunk_bytes);
+      return 0;
+    }
+    W.peer_recv = W.recv;
+    const uint64_t mine = (uint64_t)root * W.chunk_bytes;
+    const char* s = (const char*)send[root];
+    char* d = (char*)recv[root];
+    if (a == 0 && coll == kCollGather && s != d + mine) memcpy(d + mine, s, (size_t)W.chunk_bytes);
+    if (a == 0 && coll == kCollScatter && d != s + mine) memcpy(d, s + mine, (size_t)W.chunk_bytes);
+    for (int r = 0; r < n; ++r) {
+      if (coll == kCollGather) W.send[r] = (const float*)((const char*)W.send[r] - (uint64_t)r * W.chunk_bytes);
+      else W.recv[r] = (float*)((char*)W.recv[r] - (uint64_t)r * W.chunk_bytes);
+    }
+  }
   if (rooted) {
     // Comm::collective: the buffer a rank's role does not use (it may be NULL) is stood in for by
     // its other buffer; one rank: a copy; the ring's broadcast moves the whole buffer as one chunk
@@ -384,7 +441,7 @@ int run_call(World& W, int code, int coll, uint64_t count, const float* const* s
   W.nslices = (W.chunk_bytes + W.slice - 1) / W.slice;
   W.A = call_pipelines(a == 1 ? W.nslices * (uint64_t)n : W.nslices, channels, 1);  // one-shot: per chunk too
   W.iters = (uint32_t)((W.nslices + (uint64_t)W.A - 1) / (uint64_t)W.A);
-  for (int r = 0; r < n && !rooted; ++r) {
+  for (int r = 0; r < n && !rooted && !gs; ++r) {
     if (half) {
       // Comm::collective: one device copy of the chunk with one rank; the ring's all-gather gets
       // the own chunk by a copy before the launch when the call is not in place; then the
@@ -731,6 +788,8 @@ int mnccl_oneshot_fits(uint64_t chunk_bytes, int n, int channels, uint64_t slot_
 // csrc/schedule.h op tables of the ring and its halves (coll_op; ring_op for comparison), exported
 // for the host-logic tests: out = {kind, chunk, send_msg, recv_msg}
 int mnccl_coll_num_ops(int coll, int n) { return coll_num_ops(coll, n); }
+// ncclGather / ncclScatter: the op count of rank r with the call's root (their chains' depends on both)
+int mnccl_coll_num_ops_at(int coll, int n, int r, int root) { return coll_num_ops(coll, n, r, root); }
 int mnccl_coll_msgs_per_iter(int coll, int n) { return coll_msgs_per_iter(coll, n); }
 // the same with a root (the rooted collectives' tables) and what each rank's counters advance by
 void mnccl_coll_op_rooted(int coll, int n, int r, int k, int root, int* out) {
@@ -898,6 +957,42 @@ int mnccl_sim_varblock(int n, int calls, const int* coll, const int* sched, cons
     if (c < kCollAllReduce || c > kCollAllToAllV || (c != kCollAllReduce && sched[call] != 0 && sched[call] != 2)) return -2;
     int rc;
     if (c == kCollAllToAllV) {
+      const size_t m = (size_t)call * n * n;
+      rc = run_var_call(W, sched[call], esz, vcounts + m, vsdispls + m, vrdispls + m,
+                        (const char* const*)(send + (size_t)call * n), (char* const*)(recv + (size_t)call * n), slice_bytes,
+                        min_slice, schedule_seed, rng, steps);
+    } else {
+      if (counts[call] == 0) return -2;
+      rc = run_call(W, sched[call], c, counts[call], send + (size_t)call * n, recv + (size_t)call * n, slice_bytes,
+                    min_slice, schedule_seed, rng, steps, roots[call]);
+    }
+    if (rc != 0) return rc;
+  }
+  if (steps_out) *steps_out = steps;
+  return 0;
+}
+
+// mnccl_sim_varblock with ncclGather / ncclScatter (schedule.h Coll 7 / 8: counts[i] elements per
+// block; the root's large buffer -- Gather's recv, Scatter's send -- holds n blocks, every rank's other
+// buffer one; a non-root's large buffer may be NULL and must stay untouched) and a root per call: all
+// nine collectives may follow one another, on either schedule, on the one communicator state.  The
+// variable all-to-all's matrices may be NULL when no call is one.
+int mnccl_sim_all_collectives(int n, int calls, const int* coll, const int* sched, const uint64_t* counts, const int* roots,
+                              const float* const* send, float* const* recv, int esz, const uint64_t* vcounts,
+                              const uint64_t* vsdispls, const uint64_t* vrdispls, int op, uint64_t slice_bytes,
+                              uint64_t min_slice, int channels, int slots, uint64_t schedule_seed, uint64_t* steps_out) {
+  if (n < 1 || n > 16 || channels < 1 || slots < 1 || slice_bytes < 4 || slice_bytes % 4 || calls < 0) return -2;
+  if (esz != 1 && esz != 2 && esz != 4 && esz != 8) return -2;
+  World W;
+  init_world(W, n, channels, slots, op, slice_bytes);
+  uint64_t steps = 0;
+  uint64_t rng = schedule_seed * 6364136223846793005ull + 1442695040888963407ull;
+  for (int call = 0; call < calls; ++call) {
+    const int c = coll[call];
+    if (c < kCollAllReduce || c > kCollScatter || (c != kCollAllReduce && sched[call] != 0 && sched[call] != 2)) return -2;
+    int rc;
+    if (c == kCollAllToAllV) {
+      if (!vcounts || !vsdispls || !vrdispls) return -2;
       const size_t m = (size_t)call * n * n;
       rc = run_var_call(W, sched[call], esz, vcounts + m, vsdispls + m, vrdispls + m,
                         (const char* const*)(send + (size_t)call * n), (char* const*)(recv + (size_t)call * n), slice_bytes,

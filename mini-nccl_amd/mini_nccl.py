@@ -89,6 +89,8 @@ SIGNATURES = {
     "ncclAllToAll": (_I, [_VP, _VP, _SZ, _I, _VP, _VP]),
     "ncclAllToAllv": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ),
                            _I, _VP, _VP]),
+    "ncclGather": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
+    "ncclScatter": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclSend": (_I, [_VP, _SZ, _I, _I, _VP, _VP]),
     "ncclRecv": (_I, [_VP, _SZ, _I, _I, _VP, _VP]),
     "ncclGroupStart": (_I, []),
@@ -213,6 +215,18 @@ class Comm:
         arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
         return load().ncclAllToAllv(send_ptr, arrays[0], arrays[1], recv_ptr, arrays[2], arrays[3], dtype, self.handle,
                                     stream)
+
+    def gather(self, send_ptr, recv_ptr, sendcount, dtype=ncclFloat, root=0, stream=0):
+        """ncclGather: the root's recv holds nranks * sendcount elements, rank q's send at
+        [q * sendcount, (q + 1) * sendcount) (recv is written on the root only: elsewhere it may be
+        0 / None and is never touched).  Returns the ncclResult_t."""
+        return load().ncclGather(send_ptr, recv_ptr, sendcount, dtype, root, self.handle, stream)
+
+    def scatter(self, send_ptr, recv_ptr, recvcount, dtype=ncclFloat, root=0, stream=0):
+        """ncclScatter: the root's send holds nranks * recvcount elements, this rank's recv gets block
+        `rank` of it (send is read on the root only: elsewhere it may be 0 / None).  Returns the
+        ncclResult_t."""
+        return load().ncclScatter(send_ptr, recv_ptr, recvcount, dtype, root, self.handle, stream)
 
     def send(self, send_ptr, count, dtype=ncclFloat, peer=0, stream=0):
         """ncclSend: `count` elements to rank `peer`; inside a group (group_start / group) it is only

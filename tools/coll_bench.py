@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Times ncclReduceScatter, ncclAllGather, ncclBroadcast, ncclReduce, ncclAllToAll, ncclAllToAllv and
-grouped ncclSend / ncclRecv beside ncclAllReduce on one communicator.
+"""Times ncclReduceScatter, ncclAllGather, ncclBroadcast, ncclReduce, ncclAllToAll, ncclAllToAllv,
+ncclGather, ncclScatter and grouped ncclSend / ncclRecv beside ncclAllReduce on one communicator.
 
     python tools/coll_bench.py --gpus 4 [--same-device] [--bytes N] [--rounds R] [--calls K] [--warmup W]
                                [--kinds all_reduce,reduce_scatter,...] [--dtype f32|bf16]
@@ -36,6 +36,15 @@ persistent form (mncclAlgoRead), fp32 Sum, stream-ordered (MINI_NCCL_BLOCKING=0)
                     the all-to-all without its own block, through the peers' scratch
                     (both p2p rows also as p2p_sent_GBps: the bytes a rank sends over the time; no
                     threshold is set on them -- ratios p2p_all_pairs_over_all_to_all[_ring] beside)
+    gather          1 chunk from every rank -> root 0's n chunks; scatter: root 0's n chunks -> 1 chunk
+                    on every rank.  One chunk per link into or out of the root, n chunks through the
+                    root's HBM (derived from the schedule).  Beside each, the group a caller had to
+                    write before the two existed, on the scratch protocol:
+    gather_p2p      root 0: one group of n - 1 recvs (chunk q from rank q); every other rank: one send
+    scatter_p2p     root 0: one group of n - 1 sends (chunk q to rank q); every other rank: one recv
+                    (neither moves the root's own chunk: a caller adds a device copy for it).  Ratios
+                    gather_over_gather_p2p, scatter_over_scatter_p2p, *_over_all_gather, with the
+                    spreads of the groups' and the all-gather's own rounds as the yardsticks
 
 (broadcast: every rank loads one chunk of the root's send and stores it into all n recvs; reduce:
 every rank loads its chunk from all n sends and stores it into the root's recv -- on the one-GPU
@@ -67,7 +76,8 @@ for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "mini-nccl_amd")):
         sys.path.insert(0, p)
 
 KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "all_gather", "broadcast", "reduce",
-         "all_to_all", "all_to_all_v", "all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs")
+         "all_to_all", "all_to_all_v", "all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
+         "gather", "gather_p2p", "scatter", "scatter_p2p")
 # the kinds --dtype bf16 can time (the others' helpers are written for fp32 elements)
 BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce")
 
@@ -146,6 +156,12 @@ def rank_main(a):
                                            (False, big_b.ptr, n * chunk, (a.rank - 1) % n)], st.handle),
         "p2p_all_pairs": p2p_call(M, comm, [(True, big_a.ptr + 4 * chunk * q, chunk, q) for q in range(n) if q != a.rank] +
                                   [(False, big_b.ptr + 4 * chunk * q, chunk, q) for q in range(n) if q != a.rank], st.handle),
+        "gather": lambda: comm.gather(small.ptr, big_b.ptr if a.rank == 0 else None, chunk, M.ncclFloat, 0, st.handle),
+        "scatter": lambda: comm.scatter(big_a.ptr if a.rank == 0 else None, small.ptr, chunk, M.ncclFloat, 0, st.handle),
+        "gather_p2p": p2p_call(M, comm, [(False, big_b.ptr + 4 * chunk * q, chunk, q) for q in range(1, n)] if a.rank == 0
+                               else [(True, small.ptr, chunk, 0)], st.handle),
+        "scatter_p2p": p2p_call(M, comm, [(True, big_a.ptr + 4 * chunk * q, chunk, q) for q in range(1, n)] if a.rank == 0
+                                else [(False, small.ptr, chunk, 0)], st.handle),
     }
     kinds = tuple(a.kinds.split(","))
     e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
@@ -246,11 +262,13 @@ def main():
         "ms": {k: round(v, 4) for k, v in med.items()},
         "rounds_ms": {k: [round(x, 4) for x in v] for k, v in rounds.items()},
         "hbm_bytes": {k: (2 * n if k in ("all_reduce", "all_reduce_premul", "all_to_all", "all_to_all_v") else n + 1) * chunk_bytes
-                      for k in kinds if k not in ("all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs")},
+                      for k in kinds if k not in ("all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
+                                                  "gather", "gather_p2p", "scatter", "scatter_p2p")},
         "ratio": dict([(f"{k}_over_all_reduce", round(med[k] / med["all_reduce"], 4)) for k in kinds if k != "all_reduce"] +
                       [(f"{k}_over_{y}", round(med[k] / med[y], 4))
                        for k, y in (("reduce", "reduce_scatter"), ("broadcast", "all_gather"), ("all_to_all", "all_gather"),
-                                    ("reduce_scatter_premul", "reduce_scatter"))
+                                    ("reduce_scatter_premul", "reduce_scatter"), ("gather", "gather_p2p"),
+                                    ("scatter", "scatter_p2p"), ("gather", "all_gather"), ("scatter", "all_gather"))
                        if k in med and y in med] +
                       [("hbm_bytes", round((n + 1) / (2 * n), 4))] +
                       ([("all_to_all_hbm_bytes_over_all_gather", round(2 * n / (n + 1), 4))] if "all_to_all" in med else [])),
@@ -275,6 +293,9 @@ def main():
     for y in ("all_to_all", "all_to_all_ring"):
         if "p2p_all_pairs" in med and y in med:
             res["ratio"][f"p2p_all_pairs_over_{y}"] = round(med["p2p_all_pairs"] / med[y], 4)
+    for k in ("gather", "gather_p2p", "scatter", "scatter_p2p"):
+        if k in rounds:
+            res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
     if "all_gather" in rounds:
         res["all_gather_spread"] = round((max(rounds["all_gather"]) - min(rounds["all_gather"])) / med["all_gather"], 4)
     print(json.dumps(res))
