@@ -88,7 +88,9 @@ extern "C" {
    ncclAllToAllv was added the same way (detected by symbol); still 600: ncclSend, ncclRecv,
    ncclGroupStart and ncclGroupEnd were added the same way; still 600: ncclRedOpCreatePreMulSum and
    ncclRedOpDestroy were added the same way; still 600: ncclGather and ncclScatter were added the
-   same way (detected by symbol) */
+   same way (detected by symbol); still 600: ncclSend / ncclRecv push straight into a recvbuff that
+   lies in a registered window (no new symbol; mncclCommInfo_t grew, same prefix: p2p_direct_recvs,
+   p2p_direct_sends -- mncclCommGetInfoV writes them to a caller whose struct has room) */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -203,6 +205,15 @@ typedef struct {
                                             that the waves of every rank sharing a GPU stay resident
                                             together (CUs x 4 SIMDs x 2 waves / ranks on the most
                                             crowded GPU) */
+  /* still 600: point to point on registered windows (ncclSend / ncclRecv, Transport) */
+  unsigned long long p2p_direct_recvs;   /* ncclRecv operations this rank posted as direct (recvbuff in
+                                            a registered window with a table slot): counted on the
+                                            host when the launch is issued, so exact at once */
+  unsigned long long p2p_direct_sends;   /* messages this rank's kernels pushed straight into a peer's
+                                            recvbuff: counted on the device and mirrored into a
+                                            host-mapped page by the kernel, so exact once every call
+                                            issued so far has completed (after a blocking call
+                                            returned, or the stream was synchronized) */
 } mncclCommInfo_t;
 
 /* The all-reduce's two halves, NCCL's signatures.  ncclReduceScatter: sendbuff holds nranks *
@@ -428,8 +439,37 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
  * stores slices of at most slot_bytes into its region of the receiver's scratch and raises READY, the
  * receiver copies them out and returns a CREDIT -- so mncclCommInfo_t.last_algo reports mncclAlgoRing.
  * A message's slices and pipelines are a function of its byte count and the communicator's
- * rank-uniform configuration only.  A zero-copy form that pushes straight into the peer's recvbuff
- * needs a pairwise rendezvous and is not part of this interface yet. */
+ * rank-uniform configuration only.
+ *
+ * Zero copy into registered windows.  On a communicator with AT LEAST ONE registered window
+ * (mncclCommRegister) when ncclGroupEnd -- or the ungrouped call -- is made, the whole group runs a
+ * second kernel with one more hand-off per message, made from the device: the receiver posts where
+ * the bytes go, and the sender pushes them there.  An ncclRecv whose recvbuff range lies inside a
+ * registered window is posted "direct" -- window, byte offset, byte count -- and the sender, which
+ * has every window mapped since the collective registration, stores the message straight into
+ * recvbuff: one pass over the bytes, no scratch, no host rendezvous, so idle ranks stay idle,
+ * nothing blocks on the host and a captured group replays.  Any other recv (outside every window,
+ * pinned host memory, or a window beyond the table's capacity: the point-to-point table holds the
+ * first 16 live windows, slots assigned lowest-free-first on every rank alike) is posted "scratch"
+ * and moves exactly as described above.  sendbuff may be anywhere.  Direct and scratch messages and
+ * collectives follow each other on one pair in any order; the pushed bytes are visible to the
+ * receiver's stream work after its call, plain loads included, as the read schedule's pushes are.
+ * last_algo still reports mncclAlgoRing; mncclCommInfo_t.p2p_direct_recvs / p2p_direct_sends count
+ * the direct operations.
+ *   The switch is rank-uniform because registration is collective and ordered.  THE CALLER'S
+ * OBLIGATION: a send and its matching recv are issued under the same set of registered windows --
+ * they do not straddle an mncclCommRegister / mncclCommDeregister (and a captured group is replayed
+ * under the windows it was captured with).  A pair that straddles one ends at the watchdog.
+ *   With windows, the sender checks the receiver's record before it stores anything: the posted byte
+ * count must equal its own (on the scratch path too), the window must be live on the sender and the
+ * range must lie inside it.  A count disagreement between a send and its recv therefore FAILS FAST
+ * -- ncclInvalidUsage on both ranks, sticky, nothing written outside the protocol words, as for a
+ * broken window promise of ncclAllReduce -- instead of ending at the watchdog.  With windows a send,
+ * direct or not, starts only once its recv has been issued and has posted: the deadlock rule above
+ * then holds at every size (no short send completes early).  A group replayed from a HIP graph
+ * advances p2p_direct_sends per replay and p2p_direct_recvs not at all (it is counted when the
+ * group is issued).  With no window registered nothing changes: the first kernel runs exactly as
+ * before. */
 ncclResult_t ncclSend(const void* sendbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
                       hipStream_t stream);
 ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,

@@ -534,6 +534,8 @@ ncclResult_t mncclCommGetInfoV(ncclComm_t comm, void* out, size_t size) {
   info->budget_refusals = mnccl::ipc::budget_refusals();
   info->window_fast = c->window_fast() ? 1 : 0;
   info->run_pipelines = c->run_pipes();
+  info->p2p_direct_recvs = c->p2p_direct_recvs();
+  info->p2p_direct_sends = c->p2p_direct_sends();
   memcpy(out, &full, size < sizeof full ? size : sizeof full);
   return ncclSuccess;
 }
@@ -576,7 +578,14 @@ ncclResult_t mncclCommRegister(ncclComm_t comm, void* buff, size_t size, void** 
 
 ncclResult_t mncclCommDeregister(ncclComm_t comm, void* handle) {
   if (!comm || !handle) return ncclInvalidArgument;
-  return reinterpret_cast<Comm*>(comm)->deregister_window(handle);
+  try {
+    return reinterpret_cast<Comm*>(comm)->deregister_window(handle);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] CommDeregister Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
 }
 
 int mncclVersion(void) { return MNCCL_VERSION; }

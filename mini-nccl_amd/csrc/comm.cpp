@@ -106,6 +106,9 @@ struct PeerInfo {
   int32_t window_rendezvous, cus;  // MINI_NCCL_WINDOW_RENDEZVOUS as configured; the GPU's CUs
 };
 constexpr uint32_t kInfoMagic = 0x4d4e4934u;  // 'MNI4' (4.0's record: a 3.x rank fails the check)
+// 32-bit word of the host-mapped control page where the 16 per-peer direct-send counters start
+// (64-bit each; words 0-2 are status / abort / started, 4-11 the kernels' diagnostic)
+constexpr int kCtlDirectSends = 64;
 
 }  // namespace
 
@@ -162,6 +165,9 @@ void Comm::setup_device_resources() {
     hipError_t e = hipMemsetAsync(scratch_, 0, scratch_bytes_, st);
     if (e == hipSuccess) e = hipMemsetAsync(mbox_, 0, mbox_bytes_, st);
     if (e == hipSuccess) e = hipMemsetAsync(pair_seq_, 0, seq_bytes + 256, st);
+    // the point-to-point window table (p2p.h P2pWinTable): empty until a window is registered
+    hip_check(hipMalloc((void**)&win_table_, sizeof(P2pWinTable)), "alloc window table");
+    if (e == hipSuccess) e = hipMemsetAsync(win_table_, 0, sizeof(P2pWinTable), st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     hipStreamDestroy(st);
     hip_check(e, "zero scratch / mailbox / counters");
@@ -435,6 +441,8 @@ void Comm::release() {
     ipc::pool_release(mbox_);
   }
   if (pair_seq_) hipFree(pair_seq_);
+  if (win_table_) hipFree(win_table_);
+  win_table_ = nullptr;
   if (h_ctl_) hipHostFree(h_ctl_);
   if (stage_) hipFree(stage_);
   stage_ = nullptr;
@@ -464,7 +472,8 @@ ncclResult_t Comm::check_status() {
     sticky_ = mismatch ? ncclInvalidUsage
               : (st & kStatusRemoteAbort) && !(st & kStatusTimeout) ? ncclRemoteError : ncclInternalError;
     fprintf(stderr, "[Mini-NCCL] rank %d: all-reduce %s (status 0x%x); communicator is no longer usable\n", rank_,
-            mismatch ? "on registered windows: the ranks passed different windows / offsets / count / datatype / op"
+            mismatch ? "on registered windows: the ranks passed different windows / offsets / count / datatype / op (or a "
+                       "send and its recv on a communicator with windows disagreed on the byte count or the window)"
             : (st & kStatusTimeout) ? "timed out (watchdog)" : (st & kStatusHostAbort) ? "aborted by host" : "aborted by a peer",
             st);
     if ((st & kStatusRemoteAbort) && !(st & (kStatusTimeout | kStatusHostAbort))) {
@@ -484,9 +493,11 @@ ncclResult_t Comm::check_status() {
       const uint64_t word = diag[0], line = word / kFlagStride;
       const int P = wave_channels(), n = nranks_;
       const bool ready = line < (uint64_t)n * P;
-      const uint64_t idx = ready ? line : line - (uint64_t)n * P;
+      // (behind ABORT: a point-to-point DEST record's tag line, two lines per (peer, pipeline))
+      const bool dest = line > (uint64_t)2 * n * P;
+      const uint64_t idx = ready ? line : dest ? (line - (uint64_t)2 * n * P - 1) / 2 : line - (uint64_t)n * P;
       fprintf(stderr, "[Mini-NCCL] rank %d: stuck on %s word of peer %llu, pipeline %llu: waiting for >= %llu, saw %llu\n",
-              rank_, ready ? "READY" : "CREDIT", (unsigned long long)(idx / P), (unsigned long long)(idx % P),
+              rank_, ready ? "READY" : dest ? "DEST" : "CREDIT", (unsigned long long)(idx / P), (unsigned long long)(idx % P),
               (unsigned long long)diag[1], (unsigned long long)diag[2]);
     }
   }
@@ -1321,12 +1332,37 @@ ncclResult_t Comm::p2p_group(const P2pGroup& g, hipStream_t stream) {
     return ncclInvalidUsage;
   }
   if (p2p_launch_waves(a) == 0) return ncclSuccess;
+  // The rank-uniform switch: with a window registered, the window kernel runs the whole group.
+  // Per recv, direct or scratch: its range lies in a window that has a table slot, and the buffer
+  // is device memory (kaddr is the caller's pointer; a pinned host buffer's differs or lies in no window)
+  const bool windowed = nranks_ > 1 && !windows_.empty() && a.npairs > 0;
+  P2pWinArgs wa;
+  if (windowed) {
+    uint8_t op_slot[kMaxGroupOps];
+    uint64_t op_off[kMaxGroupOps];
+    unsigned direct = 0;
+    for (int j = 0; j < g.nops; ++j) {
+      const P2pOp& o = g.ops[j];
+      op_slot[j] = (uint8_t)kP2pNoSlot;
+      op_off[j] = 0;
+      if (o.send || o.peer == rank_) continue;
+      const Window* w = find_window((const void*)(uintptr_t)o.addr, (size_t)o.bytes);
+      if (!w || !p2p_win_direct(true, w->slot, o.kaddr == o.addr)) continue;
+      op_slot[j] = (uint8_t)w->slot;
+      op_off[j] = o.addr - (uint64_t)(uintptr_t)w->base;
+      ++direct;
+    }
+    p2p_win_build(g, rank_, p2p_pipes_, wave_slice(), op_slot, op_off, &wa);  // (p2p_build passed above)
+    wa.table = win_table_;
+    wa.host_sends = reinterpret_cast<uint64_t*>(d_ctl_ + kCtlDirectSends);
+    p2p_direct_recvs_ += direct;
+  }
   const CallScope scope = begin_call(stream);
   uint32_t seq = ++call_seq_;
   if (seq == 0) seq = ++call_seq_;
   int A = 0;
   const CollParams p = make_params(0, nullptr, nullptr, 0, seq, nullptr, nullptr, 0, 0, kCollAllReduce, 0, 0, &A);
-  hip_check(launch_p2p(p, a, stream), "kernel launch");
+  hip_check(windowed ? launch_p2p_window(p, wa, stream) : launch_p2p(p, a, stream), "kernel launch");
   last_algo_ = 0;  // the ring's scratch protocol
   return end_call(scope, stream, seq);
 }
@@ -1336,6 +1372,41 @@ const Comm::Window* Comm::find_window(const void* p, size_t bytes) const {
   for (const Window& w : windows_)
     if (c >= w.base && (size_t)(c - w.base) <= w.bytes && bytes <= w.bytes - (size_t)(c - w.base)) return &w;
   return nullptr;
+}
+
+// The messages this rank's kernels pushed direct: the device's per-peer counts, mirrored into the
+// host-mapped control page by the wave that advanced them
+unsigned long long Comm::p2p_direct_sends() const {
+  if (!h_ctl_) return 0;
+  unsigned long long sum = 0;
+  const uint64_t* c = reinterpret_cast<const uint64_t*>(h_ctl_ + kCtlDirectSends);
+  for (int q = 0; q < kMaxRanks; ++q) sum += __atomic_load_n(c + q, __ATOMIC_ACQUIRE);
+  return sum;
+}
+
+// The point-to-point window table follows the registrations: rebuilt on the host and copied to the
+// device once this communicator's previous call has completed (its kernel may still read the table),
+// on a private stream (the null stream would wait for other communicators' persistent kernels)
+void Comm::upload_win_table() {
+  if (!win_table_) return;
+  memset(win_host_.base, 0, sizeof win_host_.base);
+  memset(win_host_.bytes, 0, sizeof win_host_.bytes);
+  for (const Window& w : windows_) {
+    if (w.slot < 0) continue;
+    for (int q = 0; q < nranks_; ++q) win_host_.base[w.slot][q] = (uint64_t)(uintptr_t)w.peer[q];
+    win_host_.bytes[w.slot] = w.bytes;
+  }
+  int cur_dev = device_;
+  if (hipGetDevice(&cur_dev) != hipSuccess) (void)hipGetLastError();
+  if (cur_dev != device_) hip_check(hipSetDevice(device_), "hipSetDevice");
+  wait_previous_call();
+  hipStream_t st = nullptr;
+  hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "table stream");
+  hipError_t e = hipMemcpyAsync(win_table_, &win_host_, offsetof(P2pWinTable, direct_sends), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  hipStreamDestroy(st);
+  if (cur_dev != device_) hipSetDevice(cur_dev);
+  hip_check(e, "upload the window table");
 }
 
 // Collective: every rank registers its buffer of the window (same size) in the same order.  One
@@ -1358,6 +1429,7 @@ ncclResult_t Comm::register_window(void* buf, size_t bytes, void** handle) {
     w.id = next_window_++;
     w.peer[0] = w.base;
     w.aligned = (uintptr_t)buf % 4 == 0;
+    w.slot = -1;  // one rank: no peer, no table
     windows_.push_back(w);
     *handle = (void*)(uintptr_t)w.id;
     if (cur_dev != device_) hipSetDevice(cur_dev);
@@ -1405,7 +1477,9 @@ ncclResult_t Comm::register_window(void* buf, size_t bytes, void** handle) {
   w.id = next_window_++;
   for (int q = 0; q < nranks_; ++q) w.peer[q] = psend[q];
   w.aligned = vec_all;
+  w.slot = p2p_win_take(win_slots_, w.id);  // the lowest free slot, on every rank alike; -1: the table is full
   windows_.push_back(w);
+  upload_win_table();
   *handle = (void*)(uintptr_t)w.id;
   return ncclSuccess;
 }
@@ -1415,6 +1489,7 @@ ncclResult_t Comm::deregister_window(void* handle) {
   for (size_t i = 0; i < windows_.size(); ++i)
     if (windows_[i].id == id) {
       windows_.erase(windows_.begin() + (long)i);
+      if (p2p_win_drop(win_slots_, id) >= 0) upload_win_table();
       return ncclSuccess;
     }
   return ncclInvalidArgument;

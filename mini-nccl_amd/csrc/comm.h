@@ -116,10 +116,18 @@ class Comm {
   // the ring's scratch protocol, with no host rendezvous, between begin_call and end_call as any
   // collective; a self send or recv left unpaired, or paired with another size, is ncclInvalidUsage
   // with nothing launched.  last_algo reports the ring.
+  // With at least one registered window (and more than one rank) the launch is kernels.hip
+  // p2p_window_group instead: every recv whose range lies in a window with a table slot (p2p.h
+  // p2p_win_direct) is posted direct and its sender pushes straight into it; the switch is
+  // rank-uniform because registration is collective.  p2p_direct_recvs counts those recvs on the host;
+  // p2p_direct_sends is the device's count of the messages this rank pushed direct, read from the
+  // host-mapped control page (exact once the calls issued so far have completed).
   ncclResult_t p2p_validate(P2pGroup& g, bool grouped, bool send, int peer, const void* buf, size_t count, int dtype);
   ncclResult_t p2p_group(const P2pGroup& g, hipStream_t stream);
   // pipelines one point-to-point message may use (schedule.h p2p_pipes; the same on every rank)
   int p2p_pipes() const { return p2p_pipes_; }
+  unsigned long long p2p_direct_recvs() const { return p2p_direct_recvs_; }
+  unsigned long long p2p_direct_sends() const;
 
   int rank() const { return rank_; }
   int nranks() const { return nranks_; }
@@ -216,7 +224,9 @@ class Comm {
     size_t bytes;
     const char* peer[kMaxRanks];    // every rank's buffer of this window, mapped here
     bool aligned;                   // every rank's base is dword-aligned
+    int slot;                       // its slot of the point-to-point window table (p2p.h), -1: none
   };
+  void upload_win_table();          // win_host_ -> win_table_, after wait_previous_call
   const Window* find_window(const void* p, size_t bytes) const;
   void wait_previous_call();
   ncclResult_t check_status();
@@ -240,6 +250,10 @@ class Comm {
   int run_pipes_ = 0;                       // 0 until exchange_and_map: run_pipes()
   int ranks_on_device_ = 1;
   int p2p_pipes_ = 1;                       // schedule.h p2p_pipes (exchange_and_map)
+  P2pWinSlots win_slots_;                   // which window holds which slot of the table below
+  P2pWinTable win_host_;                    // the host's copy of base / bytes (upload_win_table)
+  P2pWinTable* win_table_ = nullptr;        // device: the table p2p_window_group reads (nranks > 1)
+  unsigned long long p2p_direct_recvs_ = 0; // recv operations posted direct
   bool topo_read_ = true;        // auto may run the read schedule (every pair: same GPU or 1 xGMI hop)
   std::string topo_why_ = "read: one rank";
   int peer_link_[kMaxRanks] = {}, peer_hops_[kMaxRanks] = {};

@@ -130,6 +130,13 @@ hipError_t launch_varblock(int dtype, int channels, int threads, const CollParam
 // of them, wave b serving pair b / a.pipes on pipeline b % a.pipes.  Refuses an empty launch, more
 // pairs or pipelines than the layout holds, and pairs on a communicator of one rank.
 hipError_t launch_p2p(const CollParams& p, const P2pArgs& a, hipStream_t stream);
+// The same group on a communicator with registered windows (kernels.hip p2p_window_group): every
+// receiver posts a DEST record per message from the device, and the sender pushes straight into the
+// recv buffer when that lies in a window, else through the scratch as above.  wa (p2p.h P2pWinArgs):
+// the argument above plus, per recv entry, the window slot and offset it posts, the communicator's
+// window table and the host-mapped mirror of its direct-send counters.  Refuses what launch_p2p
+// refuses, a missing table and a slot outside it.
+hipError_t launch_p2p_window(const CollParams& p, const P2pWinArgs& wa, hipStream_t stream);
 // the read schedule's push form for large calls as three launches (start, grid fold, done):
 // schedule.h read_grid_fits(p.chunk_bytes, p.n, kReadGridFloor) (2 <= n <= 8, whole 16-byte vectors), p.go set
 // vectors: 0 = schedule.h read_grid_vectors; 1 / 2 / 4 (MINI_NCCL_GRID_VECTORS) for fp32 Sum only

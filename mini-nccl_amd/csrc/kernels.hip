@@ -35,6 +35,9 @@
 //                 half of one ring hop to an arbitrary peer, a recv the receiver's half, on the
 //                 ring's scratch, flags and counters; every directed pair of the group on waves of
 //                 its own, one per pipeline, so no wave ever waits for two peers.
+//  p2p_window_group   the same groups on a communicator with registered windows: the receiver posts a
+//                 destination per message from the device, and the sender pushes straight into a recv
+//                 that lies in a window (one pass over the bytes), else through the scratch.
 //  read_start / read_grid / read_done   the read schedule's push form as three launches (the
 //                 runtime form mncclAlgoReadGrid, for large calls): a grid of one-batch workgroups
 //                 between a one-wave START and a one-wave DONE.
@@ -1693,6 +1696,183 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) p2p_kernel(Coll
   if (lane == 0) *ctr = seq;
 }
 
+// ---------------------------------------------------------------- point to point on registered windows
+// p2p_window_group: the launch of a group on a communicator with at least one registered window
+// (Comm::p2p_group; with none, p2p_kernel above runs as it always did).  The mapping is p2p_kernel's:
+// every directed pair on waves of its own, one per pipeline, a pair's operations in call order, the
+// self pairs copied by their own waves.  What is new is one hand-off per message, from the device:
+//
+//  * Receiver, at the start of message m on pipeline w: lane 0 writes a DEST record into the SENDER's
+//    mailbox (schedule.h mbox_dest_info / mbox_dest_tag, p2p.h P2pDest) -- three info words (st_sys),
+//    drained, then the tag, the pair's message counter + 1 (publish).  The record says "direct:
+//    window slot, byte offset, byte count" when the host found recvbuff inside a window with a table
+//    slot, else "scratch: byte count".  The counters are monotone across calls, schedules and graph
+//    replays, so a stale tag is always below the one a sender waits for.
+//  * Sender: waits for the tag (wait_ge_spin: bounded, abort-aware), reads the record, and checks it
+//    BEFORE it stores anything: the byte count equals its own (both paths), the slot is live in its
+//    table, offset + bytes lies inside the window (p2p_dest_check).  A failure is the windows'
+//    mismatch: kStatusMismatch claimed, the peer's ABORT raised with that cause, nothing written.
+//  * Direct: pipeline w pushes slices w, w + A, ... of the message into dest + s * slot_bytes, all in
+//    one push_pairs_vec run (the slices are its pairs: the next slice's loads leave before this one's
+//    stores) -- 16-byte non-temporal loads of the own send, sc0 sc1 stores to the peer -- when source
+//    and destination are both dword-aligned, which only the device knows: a wave-uniform branch;
+//    else, and for each slice's last len % 16 bytes, 2-byte elements.  No CREDIT wait: no slot is
+//    used.  The wave drains and raises READY ONCE, to seq + p2p_pipe_msgs: the sequence numbers the
+//    scratch form of the same message would consume, so direct and scratch messages and collectives
+//    follow each other on one pair in any order.  The receiver's wave waits for that READY and
+//    returns CREDIT at the same value; it moves no data.  The pushed bytes are visible to the
+//    receiver's stream work after its call as the read schedule's pushes are (file header).
+//  * Scratch: p2p_kernel's per-slice protocol, unchanged.
+__device__ __forceinline__ void p2p_give_up(const CollParams& p, const Ctl& c, int C, int peer, int lane, uint32_t seen) {
+  if (lane != 0) return;
+  if (seen && claim_first(c)) st_sys32(c.status, seen);
+  st_sys(p.peer_mbox[peer] + mbox_abort(p.n, C), abort_word(p, seen));
+}
+
+// slices w, w + A, ... (`mine` of them) of a message of `bytes` from src into dst
+__device__ __forceinline__ void p2p_push_direct(const char* src, char* dst, u64 bytes, u64 slot, int A, int w, int mine,
+                                                int lane) {
+  auto at = [&](int k) { return ((u64)w + (u64)k * (u64)A) * slot; };
+  auto len_of = [&](int k) { return k < mine ? (uint32_t)slice_len(bytes, slot, (u64)w + (u64)k * (u64)A) : 0u; };
+  const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | slot) & 3u) == 0;
+  if (vec) {
+    auto src_of = [&](int k) { return make_rsrc(src + (k < mine ? at(k) : 0), len_of(k) & ~15u); };
+    auto dst_of = [&](int k) { return make_rsrc(dst + (k < mine ? at(k) : 0), len_of(k) & ~15u); };
+    // (a full slice's vectors: a shorter last slice ends inside its resource, which drops the rest)
+    const uint32_t nvec = (uint32_t)((bytes < slot ? bytes : slot) >> 4);
+    if (nvec) push_pairs_vec<kDealV>(mine, src_of, dst_of, nvec, lane);
+  }
+  for (int k = 0; k < mine; ++k) {
+    const uint32_t len = len_of(k), done = vec ? len & ~15u : 0u;
+    if (done == len) continue;
+    const rsrc_t s = make_rsrc(src + at(k), len), d = make_rsrc(dst + at(k), len);
+    for (uint32_t i = done / 2 + (uint32_t)lane; i < len / 2; i += 64) Scal<2>::st(d, i * 2, Scal<2>::ld(s, i * 2));
+  }
+}
+
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) p2p_window_group(CollParams p, P2pWinArgs wa) {
+  signal_start(p);
+  const P2pArgs& a = wa.a;
+  const int lane = threadIdx.x & 63;
+  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+  const int nwaves = a.npairs * a.pipes;
+  if (b >= nwaves) {
+    p2p_self_copies(a, b - nwaves, lane);
+    return;
+  }
+  const int pair = b / a.pipes, w = b % a.pipes, C = p.pipes;
+  const int n = p.n, r = p.rank, K = p.nslots;
+  const int peer = a.pair_peer[pair], first = a.pair_first[pair], count = a.pair_count[pair];
+  const bool sends = a.pair_send[pair] != 0;
+  const Ctl ctl{p.status, p.host_abort, p.mbox + mbox_abort(n, C), p.timeout_ticks, p.mbox, p.claim};
+  u64* ctr = (sends ? p.tx_seq : p.rx_seq) + (u64)peer * C + w;
+  u64 seq = uniform64(*ctr);
+  const u64* wait_word = p.mbox + (sends ? mbox_credit(n, C, peer, w) : mbox_ready(C, peer, w));
+  u64* raise_word = p.peer_mbox[peer] + (sends ? mbox_ready(C, r, w) : mbox_credit(n, C, r, w));
+  // the DEST record of this (pair, pipeline): a receiver writes the sender's copy, a sender reads its own
+  u64* dest_info = (sends ? p.mbox + mbox_dest_info(n, C, peer, w) : p.peer_mbox[peer] + mbox_dest_info(n, C, r, w));
+  u64* dest_tag = dest_info + kFlagStride;
+  const u64 slot = p.slot_bytes;
+  u64 pushed = 0;  // messages this wave's pair pushed direct (counted on pipeline 0, which every message uses)
+  for (int i = first; i < first + count; ++i) {
+    const u64 bytes = a.bytes[i], nsl = p2p_nslices(bytes, slot);
+    const int A = p2p_msg_pipes(bytes, slot, a.p2p_pipes);
+    if (w >= A) continue;  // this message uses fewer pipelines: the pair's counters on w stay
+    const u64 mine = p2p_pipe_msgs(bytes, slot, a.p2p_pipes, w);
+    char* local = reinterpret_cast<char*>(a.ptr[i]);
+    bool direct;
+    char* dest = nullptr;
+    if (!sends) {
+      P2pDest d;
+      d.tag = p2p_dest_tag(seq);
+      d.direct = wa.wslot[i] != kP2pNoSlot ? 1u : 0u;
+      d.slot = d.direct ? wa.wslot[i] : 0u;
+      d.off = d.direct ? wa.woff[i] : 0;
+      d.bytes = bytes;
+      direct = d.direct != 0;
+      if (lane == 0) {
+        u64 info[kDestInfoWords];
+        p2p_dest_encode(d, info);
+#pragma unroll
+        for (int k = 0; k < kDestInfoWords; ++k) st_sys(dest_info + k, info[k]);
+        publish(dest_tag, d.tag, p.sys_fence);  // (drains the info words first)
+      }
+    } else {
+      if (!wave_wait_ge(dest_tag, p2p_dest_tag(seq), ctl, lane)) {
+        p2p_give_up(p, ctl, C, peer, lane, 0);
+        return;
+      }
+      acquire_sys(p.sys_fence);  // (the record is read with system-scope loads of uncached memory)
+      u64 info[kDestInfoWords];
+#pragma unroll
+      for (int k = 0; k < kDestInfoWords; ++k) info[k] = uniform64(ld_sys(dest_info + k));
+      const P2pDest d = p2p_dest_decode(info, uniform64(ld_sys(dest_tag)));
+      const bool slot_ok = d.direct && d.slot < (uint32_t)kP2pWinSlots;
+      const u64 wbase = slot_ok ? uniform64(wa.table->base[d.slot][peer]) : 0;
+      const u64 wbytes = slot_ok ? uniform64(wa.table->bytes[d.slot]) : 0;
+      if (d.tag != p2p_dest_tag(seq) || p2p_dest_check(d, bytes, wbase, wbytes) != kDestOk) {
+        p2p_give_up(p, ctl, C, peer, lane, kStatusMismatch);
+        return;
+      }
+      direct = d.direct != 0;
+      dest = reinterpret_cast<char*>(wbase + d.off);
+    }
+    if (direct) {
+      if (sends) {
+        p2p_push_direct(local, dest, bytes, slot, A, w, (int)mine, lane);
+        drain_stores();
+        seq += mine;
+        if (lane == 0) publish(raise_word, seq, p.sys_fence);
+        if (w == 0) ++pushed;
+      } else {
+        if (!wave_wait_ge(wait_word, seq + mine, ctl, lane)) {
+          p2p_give_up(p, ctl, C, peer, lane, 0);
+          return;
+        }
+        acquire_sys(p.sys_fence);
+        seq += mine;
+        if (lane == 0) st_sys(raise_word, seq);
+      }
+      continue;
+    }
+    const bool vec = a.vec[i] != 0;
+    for (u64 s = (u64)w; s < nsl; s += (u64)A) {  // p2p_kernel's slice loop
+      const uint32_t len = (uint32_t)slice_len(bytes, slot, s);
+      const bool ok = sends ? (seq + 1 <= (u64)K || wave_wait_ge(wait_word, seq + 1 - K, ctl, lane))
+                            : wave_wait_ge(wait_word, seq + 1, ctl, lane);
+      if (!ok) {
+        p2p_give_up(p, ctl, C, peer, lane, 0);
+        return;
+      }
+      char* at = local + s * slot;
+      if (sends) {
+        const rsrc_t out = make_rsrc(msg_slot(p, C, r, peer, w, seq), len);
+        if (vec) move<P2pElem, kSum, true, kSend>(at, at, out, out, len, lane);
+        else move<P2pElem, kSum, false, kSend>(at, at, out, out, len, lane);
+      } else {
+        acquire_sys(p.sys_fence);
+        const rsrc_t in = make_rsrc(msg_slot(p, C, peer, r, w, seq), len);
+        if (vec) move<P2pElem, kSum, true, kCopy>(at, at, in, in, len, lane);
+        else move<P2pElem, kSum, false, kCopy>(at, at, in, in, len, lane);
+      }
+      drain_stores();
+      ++seq;
+      if (lane == 0) {
+        if (sends) publish(raise_word, seq, p.sys_fence);
+        else st_sys(raise_word, seq);
+      }
+    }
+  }
+  if (lane == 0) {
+    *ctr = seq;
+    if (pushed) {  // this pair's only writer: the launches of one communicator run one after another
+      const u64 total = wa.table->direct_sends[peer] + pushed;
+      wa.table->direct_sends[peer] = total;
+      st_sys(wa.host_sends + peer, total);
+    }
+  }
+}
+
 // ---------------------------------------------------------------- read schedule, grid form
 // mncclAlgoReadGrid / MINI_NCCL_ALGO=read_grid, and auto's large read calls since 5.1
 // (schedule.h read_grid_form): the push form of a large call (read_grid_fits) as three launches on
@@ -2150,25 +2330,39 @@ hipError_t launch_varblock(int dtype, int C, int nt, const CollParams& p, const 
   });
 }
 
-hipError_t launch_p2p(const CollParams& p, const P2pArgs& a, hipStream_t st) {
+// the shapes both point-to-point kernels assume, checked before anything is launched: every index
+// they form from the argument stays inside the argument's arrays and the communicator's layout
+static bool p2p_shapes_ok(const CollParams& p, const P2pArgs& a) {
   const int waves = p2p_launch_waves(a);
-  // the shapes the kernel assumes, checked before anything is launched: every index it forms from
-  // the argument stays inside the argument's arrays and the communicator's layout
   if (waves < 1 || a.npairs < 0 || a.npairs > kP2pMaxPairs || a.nself < 0 || a.self_waves < 0 ||
       a.self_waves > kP2pMaxSelfWaves || (a.nself == 0) != (a.self_waves == 0) || a.self_first < 0 ||
       a.self_first + 2 * a.nself > kMaxGroupOps)
-    return hipErrorInvalidValue;
+    return false;
   if (a.npairs > 0) {
     if (p.n < 2 || p.n > kMaxRanks || p.nslots < 1 || !p.mbox || !p.tx_seq || !p.rx_seq || a.pipes < 1 ||
         a.pipes > a.p2p_pipes || a.p2p_pipes > p.pipes || p.slot_bytes == 0 || p.slot_bytes > kMaxSlice)
-      return hipErrorInvalidValue;
+      return false;
     for (int i = 0; i < a.npairs; ++i)
       if (a.pair_peer[i] >= p.n || a.pair_peer[i] == p.rank || a.pair_count[i] < 1 ||
           a.pair_first[i] + a.pair_count[i] > a.self_first || !p.peer_mbox[a.pair_peer[i]] ||
           !p.peer_scratch[a.pair_peer[i]])
-        return hipErrorInvalidValue;
+        return false;
   }
-  hipLaunchKernelGGL(p2p_kernel, dim3((unsigned)waves), dim3(64), 0, st, p, a);
+  return true;
+}
+
+hipError_t launch_p2p(const CollParams& p, const P2pArgs& a, hipStream_t st) {
+  if (!p2p_shapes_ok(p, a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(p2p_kernel, dim3((unsigned)p2p_launch_waves(a)), dim3(64), 0, st, p, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_p2p_window(const CollParams& p, const P2pWinArgs& wa, hipStream_t st) {
+  if (!p2p_shapes_ok(p, wa.a) || !wa.table || !wa.host_sends) return hipErrorInvalidValue;
+  // a direct recv names a slot of the table (the sender checks the rest of the record on the device)
+  for (int i = 0; i < wa.a.self_first; ++i)
+    if (wa.wslot[i] != kP2pNoSlot && wa.wslot[i] >= kP2pWinSlots) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(p2p_window_group, dim3((unsigned)p2p_launch_waves(wa.a)), dim3(64), 0, st, p, wa);
   return hipGetLastError();
 }
 

@@ -3,7 +3,9 @@
 // Comm::p2p_group builds the kernel's second argument from it (kernels.hip p2p_kernel), and the
 // simulator (sim.cpp mnccl_sim_p2p) runs the same builder, so the wave-per-(pair, pipeline) mapping
 // the CPU suite checks is the one the GPU executes.  Compiles into a stand-alone program
-// (tests/native/p2p_selftest.cpp).
+// (tests/native/p2p_selftest.cpp).  The second half of the file is the zero-copy form on registered
+// windows (kernels.hip p2p_window_group, sim.cpp mnccl_sim_p2p_win): the window table's slots, the
+// per-recv direct / scratch decision, and the DEST record with the sender's check of it.
 //
 // A group is a list of operations in call order.  A directed pair is (direction, peer): the sends
 // to one peer, or the recvs from one peer.  The operations of a pair run in call order on that
@@ -157,5 +159,130 @@ inline int p2p_build(const P2pGroup& g, int rank, int pipes_per_msg, uint64_t sl
 
 // waves of the launch (0: nothing to launch)
 inline int p2p_launch_waves(const P2pArgs& a) { return a.npairs * a.pipes + a.self_waves; }
+
+// ---- the zero-copy form on registered windows (kernels.hip p2p_window_group) ----
+// On a communicator with at least one registered window the receiver of every message tells its
+// sender, from the device, where the bytes go: straight into the recv buffer when that lies in a
+// window (the sender has every window mapped since the collective registration), else into the
+// scratch as before.  Everything the two kernels and the simulator share is here.
+
+// The communicator's window table: slot s holds one registered window -- this rank's mapping of
+// every rank's buffer of it and the window's byte size (the same on every rank).  Slots are assigned
+// identically on every rank (registration is collective and ordered): the lowest free one.  A window
+// registered while the table is full has no slot, and recvs into it are posted "scratch".
+constexpr int kP2pWinSlots = 16;
+constexpr int kP2pNoSlot = 0xff;  // P2pWinArgs::wslot of an entry that is posted "scratch"
+
+struct P2pWinSlots {
+  uint64_t id[kP2pWinSlots] = {};  // the window's registration number, 0: free
+};
+// the lowest free slot for window `id` (!= 0), or -1 when the table is full
+inline int p2p_win_take(P2pWinSlots& t, uint64_t id) {
+  for (int s = 0; s < kP2pWinSlots; ++s)
+    if (t.id[s] == 0) {
+      t.id[s] = id;
+      return s;
+    }
+  return -1;
+}
+inline int p2p_win_find(const P2pWinSlots& t, uint64_t id) {
+  for (int s = 0; s < kP2pWinSlots; ++s)
+    if (id != 0 && t.id[s] == id) return s;
+  return -1;
+}
+// frees the slot of window `id`; -1 when it had none
+inline int p2p_win_drop(P2pWinSlots& t, uint64_t id) {
+  const int s = p2p_win_find(t, id);
+  if (s >= 0) t.id[s] = 0;
+  return s;
+}
+
+// The table as the kernel reads it (device memory of the communicator; the host uploads base and
+// bytes after every registration and deregistration, once the previous call has completed).
+struct P2pWinTable {
+  uint64_t base[kP2pWinSlots][16];  // [slot][rank]: rank's buffer of the window, mapped here (0: free slot)
+  uint64_t bytes[kP2pWinSlots];     // the window's size
+  uint64_t direct_sends[16];        // per peer: messages this rank's kernels pushed direct (device-owned)
+};
+
+// Whether a recv is posted direct: its range lies in a window (Comm::find_window) that has a table
+// slot, and the buffer is device memory (a pinned host buffer goes through the scratch).
+inline bool p2p_win_direct(bool in_window, int slot, bool device_memory) {
+  return in_window && device_memory && slot >= 0 && slot < kP2pWinSlots;
+}
+
+// The DEST record a receiver posts per message (schedule.h mbox_dest_info / mbox_dest_tag).
+struct P2pDest {
+  uint64_t tag;     // the pair's message counter on this pipeline at the message's start + 1: full width
+  uint32_t direct;  // 1: push into window `slot` at byte `off`; 0: into the scratch
+  uint32_t slot;
+  uint64_t off;
+  uint64_t bytes;   // the receiver's byte count of the message, on both paths
+};
+MNCCL_HD uint64_t p2p_dest_tag(uint64_t seq) { return seq + 1; }
+// info[kDestInfoWords]: kind and slot, offset, bytes
+MNCCL_HD void p2p_dest_encode(const P2pDest& d, uint64_t* info) {
+  info[0] = (uint64_t)(d.direct ? 1u : 0u) | ((uint64_t)d.slot << 8);
+  info[1] = d.off;
+  info[2] = d.bytes;
+}
+MNCCL_HD P2pDest p2p_dest_decode(const uint64_t* info, uint64_t tag) {
+  P2pDest d;
+  d.tag = tag;
+  d.direct = (uint32_t)(info[0] & 1u);
+  d.slot = (uint32_t)(info[0] >> 8);
+  d.off = info[1];
+  d.bytes = info[2];
+  return d;
+}
+// The sender's check of a record before it stores anything.  win_base / win_bytes: the sender's
+// table entry for (d.slot, the receiver), read only when d.slot < kP2pWinSlots.
+enum P2pDestVerdict : int {
+  kDestOk = 0,
+  kDestBytes = 1,  // the posted byte count differs from the sender's (both paths)
+  kDestSlot = 2,   // the window slot is out of range or free on this rank
+  kDestRange = 3   // offset + bytes does not lie inside the window
+};
+MNCCL_HD int p2p_dest_check(const P2pDest& d, uint64_t my_bytes, uint64_t win_base, uint64_t win_bytes) {
+  if (d.bytes != my_bytes) return kDestBytes;
+  if (!d.direct) return kDestOk;
+  if (d.slot >= (uint32_t)kP2pWinSlots || win_base == 0) return kDestSlot;
+  if (d.off > win_bytes || d.bytes > win_bytes - d.off) return kDestRange;
+  return kDestOk;
+}
+
+// The window kernel's second argument: the old one, and per entry of a.ptr what a recv posts.
+struct P2pWinArgs {
+  P2pArgs a;
+  uint64_t woff[kMaxGroupOps];   // a direct recv's byte offset in its window
+  uint8_t wslot[kMaxGroupOps];   // its window's table slot, kP2pNoSlot: the recv is posted "scratch"
+  P2pWinTable* table;            // the communicator's table (device)
+  uint64_t* host_sends;          // host-mapped mirror of table->direct_sends (16 words)
+};
+
+// Builds it: p2p_build, then op_slot[j] / op_off[j] of group operation j (a recv the caller decided
+// to post direct: p2p_win_direct; anything else kP2pNoSlot) moved to the operation's entry.  Entry
+// pair_first[p] + k is the k-th operation of pair p in call order.
+inline int p2p_win_build(const P2pGroup& g, int rank, int pipes_per_msg, uint64_t slot_bytes, const uint8_t* op_slot,
+                         const uint64_t* op_off, P2pWinArgs* out) {
+  memset(out, 0, sizeof *out);
+  const int v = p2p_build(g, rank, pipes_per_msg, slot_bytes, &out->a);
+  memset(out->wslot, kP2pNoSlot, sizeof out->wslot);
+  if (v != kP2pOk) return v;
+  const P2pArgs& a = out->a;
+  for (int p = 0; p < a.npairs; ++p) {
+    int at = a.pair_first[p];
+    for (int j = 0; j < g.nops; ++j) {
+      const P2pOp& o = g.ops[j];
+      if (o.peer == rank || o.peer != a.pair_peer[p] || o.send != a.pair_send[p]) continue;
+      if (!o.send && op_slot[j] < kP2pWinSlots) {
+        out->wslot[at] = op_slot[j];
+        out->woff[at] = op_off[j];
+      }
+      ++at;
+    }
+  }
+  return kP2pOk;
+}
 
 }  // namespace mnccl

@@ -442,7 +442,18 @@ constexpr int kFlagStride = 16;  // uint64 words per flag line
 MNCCL_HD uint64_t mbox_ready(int C, int src, int w) { return ((uint64_t)src * C + w) * kFlagStride; }
 MNCCL_HD uint64_t mbox_credit(int n, int C, int dst, int w) { return ((uint64_t)n * C + (uint64_t)dst * C + w) * kFlagStride; }
 MNCCL_HD uint64_t mbox_abort(int n, int C) { return (uint64_t)2 * n * C * kFlagStride; }
-MNCCL_HD uint64_t mbox_words(int n, int C) { return mbox_abort(n, C) + kFlagStride; }
+//   DEST(dst, w)   : behind ABORT, two lines per (receiving rank, pipeline): written by rank dst at
+//                    the start of each point-to-point message it receives from this rank on a
+//                    communicator with registered windows (kernels.hip p2p_window_group, p2p.h
+//                    P2pDest) -- the record's three info words on the first line, then its tag, the
+//                    pair's message counter + 1, on the second.  READY / CREDIT / ABORT keep their
+//                    offsets.
+constexpr int kDestInfoWords = 3;
+MNCCL_HD uint64_t mbox_dest_info(int n, int C, int dst, int w) {
+  return mbox_abort(n, C) + kFlagStride + ((uint64_t)dst * C + w) * 2 * kFlagStride;
+}
+MNCCL_HD uint64_t mbox_dest_tag(int n, int C, int dst, int w) { return mbox_dest_info(n, C, dst, w) + kFlagStride; }
+MNCCL_HD uint64_t mbox_words(int n, int C) { return mbox_dest_info(n, C, n, 0); }
 
 // Where message `seq` from rank `src` to rank `dst` (pipeline w) lives: in the receiver's
 // scratch, region src -- the sender's stores cross the link.

@@ -584,23 +584,34 @@ int run_var_call(World& W, int code, int esz, const uint64_t* counts, const uint
   return 0;
 }
 
-// ---- point to point (kernels.hip p2p_kernel) ----
+// ---- point to point (kernels.hip p2p_kernel, and p2p_window_group on registered windows) ----
 // One wave of a launch: pair `pair` of the launch's argument on pipeline w, at operation i, slice s.
 struct P2pWave {
   int pair, w, i;
   uint64_t s, seq;
   bool done = false;
+  // the window kernel: whether the current message's hand-off happened, and what it said
+  bool handed = false, direct = false;
+  char* dest = nullptr;
+};
+
+// the simulated windows: window k is win_base[k * n + q] on rank q, win_bytes[k] bytes; its table slot is k
+struct SimWindows {
+  int nwin = 0;
+  void* const* base = nullptr;
+  const uint64_t* bytes = nullptr;
 };
 
 struct P2pLaunch {
-  P2pArgs a;
+  P2pWinArgs wa;     // (wa.a alone for p2p_kernel)
+  bool win = false;  // the window kernel's protocol: a DEST record per message
   std::vector<P2pWave> waves;
 };
 
 // the launch's waves as the kernel maps them (wave b: pair b / pipes, pipeline b % pipes); the self
 // copies happen at once (their waves wait for nobody)
 void p2p_start(World& W, int r, P2pLaunch& L) {
-  const P2pArgs& a = L.a;
+  const P2pArgs& a = L.wa.a;
   for (int c = 0; c < a.nself; ++c) {
     const int i = a.self_first + 2 * c;
     memcpy((void*)(uintptr_t)a.ptr[i + 1], (const void*)(uintptr_t)a.ptr[i], (size_t)a.bytes[i]);
@@ -618,44 +629,90 @@ void p2p_start(World& W, int r, P2pLaunch& L) {
   }
 }
 
-// One slice of one wave (or its end: the counter written back); false if its wait is unsatisfied.
-bool p2p_step(World& W, int r, const P2pArgs& a, P2pWave& v) {
-  const int peer = a.pair_peer[v.pair], w = v.w, K = W.K;
+// One step of one wave -- a slice, a direct message's hand-off and push, or its end (the counter
+// written back): 1, 0 if its wait is unsatisfied, -4 when a sender refuses the receiver's record.
+// direct[0] / direct[1]: rank r's recvs posted direct / messages pushed direct.
+int p2p_step(World& W, int r, const P2pLaunch& L, P2pWave& v, const SimWindows& T, uint64_t* direct) {
+  const P2pArgs& a = L.wa.a;
+  const int peer = a.pair_peer[v.pair], w = v.w, K = W.K, n = W.n;
   const bool sends = a.pair_send[v.pair] != 0;
   const int last = a.pair_first[v.pair] + a.pair_count[v.pair];
   for (;;) {
     if (v.i >= last) {
       (sends ? W.tx_seq : W.rx_seq)[r][(size_t)peer * W.C + w] = v.seq;
       v.done = true;
-      return true;
+      return 1;
     }
     const uint64_t bytes = a.bytes[v.i], nsl = p2p_nslices(bytes, W.slot_bytes);
     const int A = p2p_msg_pipes(bytes, W.slot_bytes, a.p2p_pipes);
     if (w >= A || v.s >= nsl) {  // the next operation of the pair
       ++v.i;
       v.s = (uint64_t)w;
+      v.handed = false;
       continue;
+    }
+    const uint64_t mine = p2p_pipe_msgs(bytes, W.slot_bytes, a.p2p_pipes, w);
+    if (L.win && !v.handed) {  // kernels.hip p2p_window_group: the message's DEST record
+      if (!sends) {
+        P2pDest d;
+        d.tag = p2p_dest_tag(v.seq);
+        d.direct = L.wa.wslot[v.i] != kP2pNoSlot ? 1u : 0u;
+        d.slot = d.direct ? L.wa.wslot[v.i] : 0u;
+        d.off = d.direct ? L.wa.woff[v.i] : 0;
+        d.bytes = bytes;
+        uint64_t* info = &W.mbox[peer][mbox_dest_info(n, W.C, r, w)];
+        p2p_dest_encode(d, info);
+        W.mbox[peer][mbox_dest_tag(n, W.C, r, w)] = d.tag;
+        v.direct = d.direct != 0;
+        if (v.direct && w == 0) ++direct[0];
+      } else {
+        const uint64_t tag = W.mbox[r][mbox_dest_tag(n, W.C, peer, w)];
+        if (tag < p2p_dest_tag(v.seq)) return 0;
+        const P2pDest d = p2p_dest_decode(&W.mbox[r][mbox_dest_info(n, W.C, peer, w)], tag);
+        const bool slot_ok = d.direct && d.slot < (uint32_t)T.nwin;
+        const uint64_t wbase = slot_ok ? (uint64_t)(uintptr_t)T.base[(size_t)d.slot * n + peer] : 0;
+        const uint64_t wbytes = slot_ok ? T.bytes[d.slot] : 0;
+        if (d.tag != p2p_dest_tag(v.seq) || p2p_dest_check(d, bytes, wbase, wbytes) != kDestOk) return -4;
+        v.direct = d.direct != 0;
+        v.dest = (char*)(uintptr_t)(wbase + d.off);
+      }
+      v.handed = true;
+      if (!sends) return 1;  // (posting is a step of its own: the sender may run in between)
+    }
+    if (L.win && v.direct) {
+      if (sends) {  // slices w, w + A, ... straight into the peer's recv; READY once
+        for (uint64_t s = (uint64_t)w; s < nsl; s += (uint64_t)A)
+          memcpy(v.dest + s * W.slot_bytes, (const char*)(uintptr_t)a.ptr[v.i] + s * W.slot_bytes,
+                 (size_t)slice_len(bytes, W.slot_bytes, s));
+        W.ready(peer, r, w) = v.seq += mine;
+        if (w == 0) ++direct[1];
+      } else {
+        if (W.ready(r, peer, w) < v.seq + mine) return 0;
+        W.credit(peer, r, w) = v.seq += mine;
+      }
+      v.s = nsl;
+      return 1;
     }
     const uint64_t len = slice_len(bytes, W.slot_bytes, v.s);
     char* at = (char*)(uintptr_t)a.ptr[v.i] + v.s * W.slot_bytes;
     if (sends) {
-      if (v.seq + 1 > (uint64_t)K && W.credit(r, peer, w) < v.seq + 1 - K) return false;
+      if (v.seq + 1 > (uint64_t)K && W.credit(r, peer, w) < v.seq + 1 - K) return 0;
       memcpy(W.slot(r, peer, w, v.seq), at, (size_t)len);
       W.ready(peer, r, w) = ++v.seq;
     } else {
-      if (W.ready(r, peer, w) < v.seq + 1) return false;
+      if (W.ready(r, peer, w) < v.seq + 1) return 0;
       memcpy(at, W.slot(peer, r, w, v.seq), (size_t)len);
       W.credit(peer, r, w) = ++v.seq;
     }
     v.s += (uint64_t)A;
-    return true;
+    return 1;
   }
 }
 
 // One point-to-point phase: rank r runs launches[r] one after another (stream order), the ranks
 // independently of each other.  0, -1 on no progress.
 int run_p2p_phase(World& W, std::vector<std::vector<P2pLaunch>>& launches, uint64_t schedule_seed, uint64_t& rng,
-                  uint64_t& steps) {
+                  uint64_t& steps, const SimWindows& T, uint64_t* direct) {
   const int n = W.n;
   std::vector<size_t> cur((size_t)n, 0);
   for (int r = 0; r < n; ++r)
@@ -680,7 +737,9 @@ int run_p2p_phase(World& W, std::vector<std::vector<P2pLaunch>>& launches, uint6
           burst = 1 + (int)((rng >> 40) % 4);
         }
         for (int b = 0; b < burst && !v.done; ++b) {
-          if (!p2p_step(W, r, L.a, v)) break;
+          const int rc = p2p_step(W, r, L, v, T, direct + 2 * r);
+          if (rc < 0) return rc;
+          if (!rc) break;
           any = true;
           ++steps;
         }
@@ -695,6 +754,81 @@ int run_p2p_phase(World& W, std::vector<std::vector<P2pLaunch>>& launches, uint6
     if (all_done) return 0;
     if (!any) return -1;
   }
+}
+
+// The run behind mnccl_sim_p2p and mnccl_sim_p2p_win (below).  op_window == nullptr: p2p_kernel's
+// protocol; else the window kernel's, operation k's recv posted direct into window op_window[k] (its
+// table slot) or, with -1, through the scratch.
+int sim_p2p_run(int n, int channels, int slots, uint64_t slot_bytes, int pipes, int nphases, const int* phase_coll,
+                const int* phase_sched, const uint64_t* phase_count, const float* const* csend, float* const* crecv,
+                int op, int nops, const int* op_phase, const int* op_rank, const int* op_launch, const int* op_send,
+                const int* op_peer, void* const* op_ptr, const uint64_t* op_bytes, const int* op_window,
+                const SimWindows& T, uint64_t schedule_seed, uint64_t* counters_out, uint64_t* direct_out,
+                uint64_t* steps_out) {
+  if (n < 1 || n > 16 || channels < 1 || slots < 1 || slot_bytes < 4 || slot_bytes % 4 || nphases < 0 || nops < 0 ||
+      pipes < 1 || pipes > channels)
+    return -2;
+  if (op_window && (T.nwin < 0 || T.nwin > kP2pWinSlots)) return -2;
+  World W;
+  init_world(W, n, channels, slots, op, slot_bytes);
+  std::vector<uint64_t> direct((size_t)2 * n, 0);
+  uint64_t steps = 0;
+  uint64_t rng = schedule_seed * 6364136223846793005ull + 1442695040888963407ull;
+  int k = 0;
+  for (int ph = 0; ph < nphases; ++ph) {
+    if (phase_coll[ph] >= 0) {
+      const int c = phase_coll[ph];
+      if (c > kCollAllToAll || phase_count[ph] == 0) return -2;
+      const int rc = run_call(W, phase_sched[ph], c, phase_count[ph], csend + (size_t)ph * n, crecv + (size_t)ph * n,
+                              slot_bytes, 0, schedule_seed, rng, steps);
+      if (rc != 0) return rc;
+      continue;
+    }
+    std::vector<std::vector<P2pLaunch>> launches((size_t)n);
+    while (k < nops && op_phase[k] == ph) {
+      const int r = op_rank[k], l = op_launch[k];
+      if (r < 0 || r >= n) return -2;
+      P2pGroup g;
+      uint8_t g_slot[kMaxGroupOps];
+      uint64_t g_off[kMaxGroupOps];
+      for (; k < nops && op_phase[k] == ph && op_rank[k] == r && op_launch[k] == l; ++k) {
+        if (op_bytes[k] == 0) continue;  // count == 0: nothing recorded
+        uint64_t bytes = 0;
+        if (p2p_check_op(g, n, op_send[k] != 0, op_peer[k], op_ptr[k], (size_t)op_bytes[k], 1, &bytes) != kP2pOk) return -3;
+        if (p2p_append(g, op_send[k] != 0, op_peer[k], op_ptr[k], (uint64_t)(uintptr_t)op_ptr[k], bytes) != kP2pOk) return -3;
+        // Comm::p2p_group's decision per recv: the range lies in the window the caller names
+        const int j = g.nops - 1, win = op_window ? op_window[k] : -1;
+        g_slot[j] = (uint8_t)kP2pNoSlot;
+        g_off[j] = 0;
+        if (win < 0 || op_send[k] != 0 || op_peer[k] == r) continue;
+        if (win >= T.nwin) return -2;
+        const char* base = (const char*)T.base[(size_t)win * n + r];
+        const char* at = (const char*)op_ptr[k];
+        if (at < base || (uint64_t)(at - base) > T.bytes[win] || bytes > T.bytes[win] - (uint64_t)(at - base)) return -2;
+        if (!p2p_win_direct(true, win, true)) continue;
+        g_slot[j] = (uint8_t)win;
+        g_off[j] = (uint64_t)(at - base);
+      }
+      P2pLaunch L;
+      L.win = op_window != nullptr;
+      if (p2p_win_build(g, r, pipes, slot_bytes, g_slot, g_off, &L.wa) != kP2pOk) return -3;
+      if (p2p_launch_waves(L.wa.a) > 0) launches[(size_t)r].push_back(L);
+    }
+    const int rc = run_p2p_phase(W, launches, schedule_seed, rng, steps, T, direct.data());
+    if (rc != 0) return rc;
+  }
+  if (k != nops) return -2;
+  if (counters_out) {
+    const size_t per = (size_t)n * channels;
+    for (int r = 0; r < n; ++r)
+      for (size_t j = 0; j < per; ++j) {
+        counters_out[(size_t)r * per + j] = W.tx_seq[r][j];
+        counters_out[(size_t)n * per + (size_t)r * per + j] = W.rx_seq[r][j];
+      }
+  }
+  if (direct_out) memcpy(direct_out, direct.data(), direct.size() * sizeof(uint64_t));
+  if (steps_out) *steps_out = steps;
+  return 0;
 }
 
 }  // namespace
@@ -729,52 +863,77 @@ int mnccl_sim_p2p(int n, int channels, int slots, uint64_t slot_bytes, int pipes
                   int op, int nops, const int* op_phase, const int* op_rank, const int* op_launch, const int* op_send,
                   const int* op_peer, void* const* op_ptr, const uint64_t* op_bytes, uint64_t schedule_seed,
                   uint64_t* counters_out, uint64_t* steps_out) {
-  if (n < 1 || n > 16 || channels < 1 || slots < 1 || slot_bytes < 4 || slot_bytes % 4 || nphases < 0 || nops < 0 ||
-      pipes < 1 || pipes > channels)
-    return -2;
-  World W;
-  init_world(W, n, channels, slots, op, slot_bytes);
-  uint64_t steps = 0;
-  uint64_t rng = schedule_seed * 6364136223846793005ull + 1442695040888963407ull;
-  int k = 0;
-  for (int ph = 0; ph < nphases; ++ph) {
-    if (phase_coll[ph] >= 0) {
-      const int c = phase_coll[ph];
-      if (c > kCollAllToAll || phase_count[ph] == 0) return -2;
-      const int rc = run_call(W, phase_sched[ph], c, phase_count[ph], csend + (size_t)ph * n, crecv + (size_t)ph * n,
-                              slot_bytes, 0, schedule_seed, rng, steps);
-      if (rc != 0) return rc;
-      continue;
-    }
-    std::vector<std::vector<P2pLaunch>> launches((size_t)n);
-    while (k < nops && op_phase[k] == ph) {
-      const int r = op_rank[k], l = op_launch[k];
-      if (r < 0 || r >= n) return -2;
-      P2pGroup g;
-      for (; k < nops && op_phase[k] == ph && op_rank[k] == r && op_launch[k] == l; ++k) {
-        if (op_bytes[k] == 0) continue;  // count == 0: nothing recorded
-        uint64_t bytes = 0;
-        if (p2p_check_op(g, n, op_send[k] != 0, op_peer[k], op_ptr[k], (size_t)op_bytes[k], 1, &bytes) != kP2pOk) return -3;
-        if (p2p_append(g, op_send[k] != 0, op_peer[k], op_ptr[k], (uint64_t)(uintptr_t)op_ptr[k], bytes) != kP2pOk) return -3;
-      }
-      P2pLaunch L;
-      if (p2p_build(g, r, pipes, slot_bytes, &L.a) != kP2pOk) return -3;
-      if (p2p_launch_waves(L.a) > 0) launches[(size_t)r].push_back(L);
-    }
-    const int rc = run_p2p_phase(W, launches, schedule_seed, rng, steps);
-    if (rc != 0) return rc;
-  }
-  if (k != nops) return -2;
-  if (counters_out) {
-    const size_t per = (size_t)n * channels;
-    for (int r = 0; r < n; ++r)
-      for (size_t j = 0; j < per; ++j) {
-        counters_out[(size_t)r * per + j] = W.tx_seq[r][j];
-        counters_out[(size_t)n * per + (size_t)r * per + j] = W.rx_seq[r][j];
-      }
-  }
-  if (steps_out) *steps_out = steps;
-  return 0;
+  return sim_p2p_run(n, channels, slots, slot_bytes, pipes, nphases, phase_coll, phase_sched, phase_count, csend, crecv, op,
+                     nops, op_phase, op_rank, op_launch, op_send, op_peer, op_ptr, op_bytes, nullptr, SimWindows(),
+                     schedule_seed, counters_out, nullptr, steps_out);
+}
+
+// The same run on a communicator with registered windows (kernels.hip p2p_window_group): every
+// launch runs the window kernel's protocol on the real word layout -- per message a DEST record in
+// the sender's mailbox (schedule.h mbox_dest_info / mbox_dest_tag, p2p.h P2pDest), checked by the
+// sender (p2p_dest_check) before it moves anything.  There are nwin <= kP2pWinSlots windows, window k
+// being win_base[k * n + q] on rank q and win_bytes[k] bytes, in table slot k.  op_window[k] is the
+// per-operation "in window" flag: -1 posts a recv "scratch" (and is what every send carries), a
+// window's index posts it "direct" into that window, in which its range must lie (-2 if not).
+// direct_out (2 * n words): per rank, the recvs it posted direct and the messages it pushed direct.
+// Returns what mnccl_sim_p2p returns, and -4 when a sender refuses a record (the byte counts of a
+// send and its recv differ).
+int mnccl_sim_p2p_win(int n, int channels, int slots, uint64_t slot_bytes, int pipes, int nphases, const int* phase_coll,
+                      const int* phase_sched, const uint64_t* phase_count, const float* const* csend,
+                      float* const* crecv, int op, int nops, const int* op_phase, const int* op_rank,
+                      const int* op_launch, const int* op_send, const int* op_peer, void* const* op_ptr,
+                      const uint64_t* op_bytes, const int* op_window, int nwin, void* const* win_base,
+                      const uint64_t* win_bytes, uint64_t schedule_seed, uint64_t* counters_out, uint64_t* direct_out,
+                      uint64_t* steps_out) {
+  if (!op_window && nops > 0) return -2;
+  SimWindows T;
+  T.nwin = nwin;
+  T.base = win_base;
+  T.bytes = win_bytes;
+  static const int none = -1;
+  return sim_p2p_run(n, channels, slots, slot_bytes, pipes, nphases, phase_coll, phase_sched, phase_count, csend, crecv, op,
+                     nops, op_phase, op_rank, op_launch, op_send, op_peer, op_ptr, op_bytes, op_window ? op_window : &none, T,
+                     schedule_seed, counters_out, direct_out, steps_out);
+}
+
+// the pure functions of p2p.h's window form, exported for the host-logic tests
+int mnccl_p2p_win_slots(void) { return kP2pWinSlots; }
+// ops[i] > 0: register window id ops[i]; < 0: deregister window -ops[i].  slots_out[i]: the slot taken or freed, -1: none
+void mnccl_p2p_win_assign(int nops, const int64_t* ops, int* slots_out) {
+  P2pWinSlots t;
+  for (int i = 0; i < nops; ++i)
+    slots_out[i] = ops[i] > 0 ? p2p_win_take(t, (uint64_t)ops[i]) : p2p_win_drop(t, (uint64_t)-ops[i]);
+}
+int mnccl_p2p_win_direct(int in_window, int slot, int device_memory) {
+  return p2p_win_direct(in_window != 0, slot, device_memory != 0) ? 1 : 0;
+}
+// rec: tag, direct, slot, off, bytes -> words_out: info[0..2], tag -> back_out: the same five decoded
+void mnccl_p2p_dest_roundtrip(const uint64_t* rec, uint64_t* words_out, uint64_t* back_out) {
+  P2pDest d;
+  d.tag = rec[0];
+  d.direct = (uint32_t)rec[1];
+  d.slot = (uint32_t)rec[2];
+  d.off = rec[3];
+  d.bytes = rec[4];
+  p2p_dest_encode(d, words_out);
+  words_out[kDestInfoWords] = d.tag;
+  const P2pDest b = p2p_dest_decode(words_out, words_out[kDestInfoWords]);
+  back_out[0] = b.tag; back_out[1] = b.direct; back_out[2] = b.slot; back_out[3] = b.off; back_out[4] = b.bytes;
+}
+uint64_t mnccl_p2p_dest_tag(uint64_t seq) { return p2p_dest_tag(seq); }
+int mnccl_p2p_dest_check(int direct, uint32_t slot, uint64_t off, uint64_t bytes, uint64_t my_bytes, uint64_t win_base,
+                         uint64_t win_bytes) {
+  P2pDest d;
+  d.tag = 1;
+  d.direct = (uint32_t)direct;
+  d.slot = slot;
+  d.off = off;
+  d.bytes = bytes;
+  return p2p_dest_check(d, my_bytes, win_base, win_bytes);
+}
+uint64_t mnccl_mbox_word(int which, int n, int C, int q, int w) {
+  return which == 0 ? mbox_ready(C, q, w) : which == 1 ? mbox_credit(n, C, q, w) : which == 2 ? mbox_abort(n, C)
+         : which == 3 ? mbox_dest_info(n, C, q, w) : which == 4 ? mbox_dest_tag(n, C, q, w) : mbox_words(n, C);
 }
 
 // csrc/schedule.h one-shot geometry, exported for the host-logic tests

@@ -70,6 +70,8 @@ class CommInfo(ctypes.Structure):
         ("retired_bytes", ctypes.c_ulonglong), ("retired_budget", ctypes.c_ulonglong),
         ("budget_refusals", ctypes.c_ulonglong), ("window_fast", ctypes.c_int),
         ("run_pipelines", ctypes.c_int),
+        # still 600: point to point on registered windows
+        ("p2p_direct_recvs", ctypes.c_ulonglong), ("p2p_direct_sends", ctypes.c_ulonglong),
     ]
 
 

@@ -36,6 +36,11 @@ persistent form (mncclAlgoRead), fp32 Sum, stream-ordered (MINI_NCCL_BLOCKING=0)
                     the all-to-all without its own block, through the peers' scratch
                     (both p2p rows also as p2p_sent_GBps: the bytes a rank sends over the time; no
                     threshold is set on them -- ratios p2p_all_pairs_over_all_to_all[_ring] beside)
+    p2p_neighbor_win / p2p_all_pairs_win   the same two groups, on the same buffers, while the recv
+                    buffer is a registered window (mncclCommRegister around the kind's calls, outside
+                    the timed region): the zero-copy form, one pass over the bytes instead of two.
+                    Ratios p2p_*_win_over_p2p_* beside p2p_*_spread, the spread of the scratch form's
+                    own rounds in this run; p2p_direct counts rank 0's direct recvs / sends per kind
     gather          1 chunk from every rank -> root 0's n chunks; scatter: root 0's n chunks -> 1 chunk
                     on every rank.  One chunk per link into or out of the root, n chunks through the
                     root's HBM (derived from the schedule).  Beside each, the group a caller had to
@@ -77,8 +82,10 @@ for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "mini-nccl_amd")):
 
 KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "all_gather", "broadcast", "reduce",
          "all_to_all", "all_to_all_v", "all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
-         "gather", "gather_p2p", "scatter", "scatter_p2p")
+         "p2p_neighbor_win", "p2p_all_pairs_win", "gather", "gather_p2p", "scatter", "scatter_p2p")
 # the kinds --dtype bf16 can time (the others' helpers are written for fp32 elements)
+# the kinds that run while big_b is a registered window, and the scratch form each is measured against
+WIN_KINDS = {"p2p_neighbor_win": "p2p_neighbor", "p2p_all_pairs_win": "p2p_all_pairs"}
 BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce")
 
 
@@ -163,20 +170,43 @@ def rank_main(a):
         "scatter_p2p": p2p_call(M, comm, [(True, big_a.ptr + 4 * chunk * q, chunk, q) for q in range(1, n)] if a.rank == 0
                                 else [(False, small.ptr, chunk, 0)], st.handle),
     }
+    for k, base in WIN_KINDS.items():
+        calls[k] = calls[base]
     kinds = tuple(a.kinds.split(","))
+    window = [None]
+
+    def set_window(k, on):
+        """Collective, outside the timed region: big_b is a registered window exactly while a *_win kind runs."""
+        if k not in WIN_KINDS:
+            return
+        st.sync()
+        if on:
+            window[0] = comm.register(big_b.ptr, n * chunk * esz)
+        else:
+            comm.deregister(window[0])
+
+    def direct_counts():
+        ci = comm.info()
+        return [ci["p2p_direct_recvs"], ci["p2p_direct_sends"]]
+
     e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
     hip_rt.check(H.hipEventCreate(ctypes.byref(e0)), "hipEventCreate")
     hip_rt.check(H.hipEventCreate(ctypes.byref(e1)), "hipEventCreate")
     sh = ctypes.c_void_p(st.handle)
     algos = {}
     for k in kinds:
+        set_window(k, True)
         for _ in range(a.warmup):
             M.check(calls[k](), k)
         st.sync()
         algos[k] = comm.info()["last_algo"]
+        set_window(k, False)
     ms = {k: [] for k in kinds}
+    direct = {k: [0, 0] for k in kinds if k.startswith("p2p_")}
     for _ in range(a.rounds):
         for k in kinds:
+            set_window(k, True)
+            d0 = direct_counts()
             hip_rt.check(H.hipEventRecord(e0, sh), "hipEventRecord")
             for _ in range(a.calls):
                 M.check(calls[k](), k)
@@ -185,6 +215,9 @@ def rank_main(a):
             t = ctypes.c_float()
             hip_rt.check(H.hipEventElapsedTime(ctypes.byref(t), e0, e1), "hipEventElapsedTime")
             ms[k].append(t.value / a.calls)
+            if k in direct:
+                direct[k] = [x + y - z for x, y, z in zip(direct[k], direct_counts(), d0)]
+            set_window(k, False)
     info = comm.info()
     err = comm.async_error()
     H.hipEventDestroy(e0)
@@ -193,7 +226,7 @@ def rank_main(a):
         b.free()
     st.destroy()
     comm.destroy()
-    print("COLL_BENCH_RANK " + json.dumps({"rank": a.rank, "device": dev, "ms": ms, "algos": algos, "async": err,
+    print("COLL_BENCH_RANK " + json.dumps({"rank": a.rank, "device": dev, "ms": ms, "algos": algos, "async": err, "direct": direct,
                                            "ranks_on_device": info["ranks_on_device"]}), flush=True)
 
 
@@ -263,7 +296,7 @@ def main():
         "rounds_ms": {k: [round(x, 4) for x in v] for k, v in rounds.items()},
         "hbm_bytes": {k: (2 * n if k in ("all_reduce", "all_reduce_premul", "all_to_all", "all_to_all_v") else n + 1) * chunk_bytes
                       for k in kinds if k not in ("all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
-                                                  "gather", "gather_p2p", "scatter", "scatter_p2p")},
+                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") and k not in WIN_KINDS},
         "ratio": dict([(f"{k}_over_all_reduce", round(med[k] / med["all_reduce"], 4)) for k in kinds if k != "all_reduce"] +
                       [(f"{k}_over_{y}", round(med[k] / med[y], 4))
                        for k, y in (("reduce", "reduce_scatter"), ("broadcast", "all_gather"), ("all_to_all", "all_gather"),
@@ -287,13 +320,21 @@ def main():
     # the point-to-point rows: the bytes one rank sends over the time, and the all-pairs group beside
     # the all-to-all on both schedules (one-GPU proxy numbers when co-located; no threshold)
     sent = {"p2p_neighbor": n * chunk_bytes, "p2p_all_pairs": (n - 1) * chunk_bytes}
+    sent.update({k: sent[base] for k, base in WIN_KINDS.items()})
     p2p = {k: round(sent[k] / (med[k] * 1e-3) / 1e9, 2) for k in sent if k in med}
     if p2p:
         res["p2p_sent_GBps"] = p2p
     for y in ("all_to_all", "all_to_all_ring"):
         if "p2p_all_pairs" in med and y in med:
             res["ratio"][f"p2p_all_pairs_over_{y}"] = round(med["p2p_all_pairs"] / med[y], 4)
-    for k in ("gather", "gather_p2p", "scatter", "scatter_p2p"):
+    # the zero-copy form beside the scratch form of the same group in the same run, the scratch
+    # form's own round-to-round spread as the yardstick, and the direct operations rank 0 counted
+    for k, base in WIN_KINDS.items():
+        if k in med and base in med:
+            res["ratio"][f"{k}_over_{base}"] = round(med[k] / med[base], 4)
+    if any(k.startswith("p2p_") for k in kinds):
+        res["p2p_direct"] = {k: v for k, v in min(ranks, key=lambda r: r["rank"])["direct"].items()}
+    for k in ("gather", "gather_p2p", "scatter", "scatter_p2p", "p2p_neighbor", "p2p_all_pairs"):
         if k in rounds:
             res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
     if "all_gather" in rounds:
