@@ -532,6 +532,46 @@ ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataTyp
                                       ncclScalarResidence_t residence, ncclComm_t comm);
 ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm);
 
+/* fp8 (NCCL's and RCCL's ncclFloat8e4m3 = 10 / ncclFloat8e5m2 = 11; detected by the symbol
+ * mncclDataTypeSize and its answer for the two values, MNCCL_VERSION stays 600).  Every call accepts
+ * the two types wherever it accepts ncclBfloat16, with the same checks in the same order: the calls
+ * that fold (ncclAllReduce, ncclReduceScatter, ncclReduce with ncclSum / ncclProd / ncclMax / ncclMin
+ * and ncclRedOpCreatePreMulSum ops; mncclLocalReduce with the four built-in ops), the calls that only
+ * move bytes, with element size 1 (ncclAllGather, ncclBroadcast, ncclAllToAll, ncclAllToAllv,
+ * ncclGather, ncclScatter, ncclSend, ncclRecv), and ncclRedOpCreatePreMulSum, whose scalar is one fp8
+ * byte.  ncclAvg stays ncclInternalError.  Every schedule and form the 16-bit types have works: ring,
+ * read, one-shot, grid form, registered windows, HIP-graph capture, one rank, host buffers.
+ *
+ * Encodings: both OCP (not MI300's fnuz).  E4M3 is e4m3fn: bias 7, no infinities, NaN 0x7f / 0xff,
+ * largest finite value 448.  E5M2: bias 15, IEEE-like, 0x7c / 0xfc are +-inf, 0x7d..0x7f / 0xfd..0xff
+ * NaN, largest finite value 57344.
+ *
+ * Result, bit for bit (ncclBfloat16's rule: widen exactly, operate in float, round once).  ncclSum,
+ * ncclProd: r = float(a) op float(b), one IEEE single-precision operation (the product of two fp8
+ * values is exact), then encode(r).  ncclMax, ncclMin: the decoded values are compared and an
+ * operand's byte is returned unchanged -- (fa > fb) ? a : b and (fa < fb) ? a : b, with a the local
+ * element and b the incoming one (op(x_q, acc)); what happens to NaN and +-0 follows from that
+ * expression.  encode(r): NaN gives a NaN of the type (which one is unspecified); +-inf gives +-inf
+ * for E5M2 (it cannot arise for E4M3); a finite r is rounded to nearest even onto the type's finite
+ * grid, subnormals included; a finite r that rounds beyond the largest finite value SATURATES to
+ * +-448 / +-57344 and never becomes inf or NaN; the sign of zero is r's.  A pre-multiplied sum:
+ * y = encode(float(s) * float(x)), one product and one rounding, and the y are summed as ncclSum sums
+ * them -- two roundings, no fusion, ncclAllReduce's tail unscaled, as for every datatype.  The
+ * association across ranks is unchanged -- chunk c: acc = x_c, then acc = op(x_q, acc) for
+ * q = c+1 ... c-1 -- re-encoded to fp8 after every step, so every schedule gives the same bits.
+ *
+ * 16-byte vectors.  The vector path's rule is unchanged: pointers dword-aligned and chunk bytes a
+ * multiple of 4.  A one-byte type misses it for three chunk lengths out of four and then runs the
+ * element path (same bits, one element per access): callers who care keep counts per rank a
+ * multiple of 4.
+ *
+ * mncclDataTypeSize writes the element size of a supported datatype to *size and returns ncclSuccess;
+ * an unsupported datatype is ncclInvalidArgument with *size untouched, a NULL size
+ * ncclInvalidArgument. */
+#define ncclFloat8e4m3 ((ncclDataType_t)10)
+#define ncclFloat8e5m2 ((ncclDataType_t)11)
+ncclResult_t mncclDataTypeSize(ncclDataType_t datatype, size_t* size);
+
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream);
 

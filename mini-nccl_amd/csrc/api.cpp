@@ -29,8 +29,10 @@ namespace {
 
 // reference api.cpp:101-128: Float/Int32/Double x Sum/Prod/Max/Min; this build adds
 // Float16/Bfloat16 (build-defined parity).  Anything else -> error.
+// ncclFloat8e4m3 / ncclFloat8e5m2 (mini_nccl_ext.h): the OCP fp8 types, wherever ncclBfloat16 is accepted.
 bool dtype_ok(ncclDataType_t t) {
-  return t == ncclFloat || t == ncclDouble || t == ncclInt32 || t == ncclFloat16 || t == ncclBfloat16;
+  return t == ncclFloat || t == ncclDouble || t == ncclInt32 || t == ncclFloat16 || t == ncclBfloat16 ||
+         t == ncclFloat8e4m3 || t == ncclFloat8e5m2;
 }
 bool op_ok(ncclRedOp_t op) { return op == ncclSum || op == ncclProd || op == ncclMax || op == ncclMin; }
 
@@ -586,6 +588,12 @@ ncclResult_t mncclCommDeregister(ncclComm_t comm, void* handle) {
   } catch (...) {
     return ncclSystemError;
   }
+}
+
+ncclResult_t mncclDataTypeSize(ncclDataType_t datatype, size_t* size) {
+  if (!size || !dtype_ok(datatype)) return ncclInvalidArgument;
+  *size = (size_t)mnccl::dtype_size((int)datatype);
+  return ncclSuccess;
 }
 
 int mncclVersion(void) { return MNCCL_VERSION; }

@@ -929,6 +929,9 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
     // 16-byte vector path whenever every message's local base is dword-aligned (vectors may
     // straddle 16-byte boundaries on the local side; each message's last len % 16 bytes go
     // element by element); element-wise path otherwise (2-byte types with odd chunks)
+    // (the one-byte fp8 types miss the rule for three chunk lengths out of four -- chunk bytes 1, 2 or
+    // 3 mod 4 -- and then run the element path: same bits, one byte per access; the rule itself is
+    // the same for every datatype)
     bool vec = (((uintptr_t)ksend | (uintptr_t)krecv) % 4 == 0) && (chunk_bytes % 4 == 0);
     int algo = oneshot ? 3 : 0;  // else the ring unless every rank can share its buffers
     const char* psend[kMaxRanks] = {};

@@ -8,7 +8,9 @@
 namespace mnccl {
 
 // Element types the kernels are instantiated for (subset of ncclDataType_t values).
-enum DType : int { kI32 = 2, kF16 = 6, kF32 = 7, kF64 = 8, kBF16 = 9 };
+enum DType : int { kI32 = 2, kF16 = 6, kF32 = 7, kF64 = 8, kBF16 = 9,
+                   // OCP fp8 (ncclFloat8e4m3 = e4m3fn, ncclFloat8e5m2): NCCL's and RCCL's values
+                   kF8E4M3 = 10, kF8E5M2 = 11 };
 enum RedOp : int { kSum = 0, kProd = 1, kMax = 2, kMin = 3,
                    // a handle of ncclRedOpCreatePreMulSum, resolved: the sum of inputs scaled by
                    // CollParams::scale where they enter a fold (kernels.hip Scale); the communicator
@@ -120,7 +122,7 @@ struct VarBlockArgs {
   uint32_t pad;
 };
 // p: the all-to-all's geometry for chunk_bytes = the largest block of the whole matrix (the same on
-// every rank), p.peer_recv every rank's recv.  By element size (2 / 4 / 8 from dtype): no arithmetic.
+// every rank), p.peer_recv every rank's recv.  By element size (1 / 2 / 4 / 8 from dtype): no arithmetic.
 hipError_t launch_varblock(int dtype, int channels, int threads, const CollParams& p, const VarBlockArgs& v,
                            hipStream_t stream);
 // ncclSend / ncclRecv (kernels.hip p2p_kernel): one launch for a whole group.  p: the communicator's

@@ -45,6 +45,9 @@
 //                 rank stores its pieces into every peer's scratch and folds the result itself,
 //                 same association order.
 //  local_reduce   the element-wise op alone: out = op(local, incoming), 16 B per lane.
+//  fp8_* / byte_*  the same bodies for the one-byte datatypes (ncclFloat8e4m3 / ncclFloat8e5m2, OCP): the
+//                 kernels that fold under fp8_* names (element ops over gfx950's packed fp8 conversions,
+//                 saturating), the kernels that only copy under byte_* names (element size 1).
 //
 // Memory-ordering protocol (cross-process, cross-device over xGMI):
 //  * everything another rank writes in the ring lives in THIS rank's scratch / mailbox,
@@ -123,6 +126,85 @@ template <> struct Op<bf16_t, kProd> { __device__ static bf16_t f(bf16_t a, bf16
 template <> struct Op<bf16_t, kMax> { __device__ static bf16_t f(bf16_t a, bf16_t b) { return (bf2f(a) > bf2f(b)) ? a : b; } };
 template <> struct Op<bf16_t, kMin> { __device__ static bf16_t f(bf16_t a, bf16_t b) { return (bf2f(a) < bf2f(b)) ? a : b; } };
 
+// fp8, OCP encodings (ncclFloat8e4m3 = e4m3fn: bias 7, no infinities, NaN 0x7f / 0xff, largest finite
+// 448; ncclFloat8e5m2: bias 15, IEEE-like, largest finite 57344) -- bf16's rule one format down: widen
+// (exact), ONE f32 operation (the product of two fp8 values is exact in f32), round once to nearest
+// even onto the type's finite grid, subnormals included, with gfx950's packed conversions, two elements
+// per instruction each way (v_cvt_pk_f32_fp8 / v_cvt_pk_fp8_f32 and the bf8 pair; the word of the dword
+// they read or write is an op_sel bit).  A finite result beyond the largest finite value saturates to
+// it and never becomes inf or NaN: fp8_sat clamps every value whose f32 exponent is not all ones ahead
+// of the conversion (amd_hip_fp8.h's saturating cast does the same), so the conversion itself never
+// sees a finite value out of range; NaN stays a NaN of the type, +-inf stays +-inf for e5m2 (e4m3 has
+// no operand that could produce one), the sign of zero is the f32 result's.  Max and Min compare the
+// decoded values and return an operand's byte unchanged, with bf16's expression.
+struct e4m3_t { uint8_t v; };
+struct e5m2_t { uint8_t v; };
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+template <typename T> struct IsFp8 : std::false_type {};
+template <> struct IsFp8<e4m3_t> : std::true_type {};
+template <> struct IsFp8<e5m2_t> : std::true_type {};
+
+// dec2<HI>(w): bytes 2 HI, 2 HI + 1 of w as two floats; enc2<HI>(a, b, old): old with those bytes replaced
+template <typename T> struct Fp8;
+template <> struct Fp8<e4m3_t> {
+  static constexpr float kMax = 448.0f;
+  template <bool HI> __device__ static v2f dec2(uint32_t w) { return __builtin_amdgcn_cvt_pk_f32_fp8((int)w, HI); }
+  template <bool HI> __device__ static uint32_t enc2(float a, float b, uint32_t old) {
+    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, (int)old, HI);
+  }
+};
+template <> struct Fp8<e5m2_t> {
+  static constexpr float kMax = 57344.0f;
+  template <bool HI> __device__ static v2f dec2(uint32_t w) { return __builtin_amdgcn_cvt_pk_f32_bf8((int)w, HI); }
+  template <bool HI> __device__ static uint32_t enc2(float a, float b, uint32_t old) {
+    return (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(a, b, (int)old, HI);
+  }
+};
+
+template <typename T>
+__device__ __forceinline__ float fp8_sat(float r) {
+  return (__float_as_uint(r) & 0x7f800000u) != 0x7f800000u ? __builtin_amdgcn_fmed3f(r, Fp8<T>::kMax, -Fp8<T>::kMax) : r;
+}
+
+// op(a, b) on the two elements in word HI of a and b, written into that word of old
+template <typename T, int OPC, bool HI>
+__device__ __forceinline__ uint32_t fp8_fold2(uint32_t a, uint32_t b, uint32_t old) {
+  const v2f fa = Fp8<T>::template dec2<HI>(a), fb = Fp8<T>::template dec2<HI>(b);
+  if constexpr (OPC == kMax || OPC == kMin) {
+    const bool t0 = OPC == kMax ? fa.x > fb.x : fa.x < fb.x, t1 = OPC == kMax ? fa.y > fb.y : fa.y < fb.y;
+    constexpr uint32_t word = HI ? 0xffff0000u : 0x0000ffffu;
+    const uint32_t m = ((t0 ? 0x00ff00ffu : 0u) | (t1 ? 0xff00ff00u : 0u)) & word;  // bytes taken from a
+    return (old & ~word) | (a & m) | (b & ~m & word);
+  } else {
+    const v2f r = OPC == kProd ? fa * fb : fa + fb;
+    return Fp8<T>::template enc2<HI>(fp8_sat<T>(r.x), fp8_sat<T>(r.y), old);
+  }
+}
+template <typename T, int OPC>
+__device__ __forceinline__ uint32_t fp8_fold4(uint32_t a, uint32_t b) {
+  return fp8_fold2<T, OPC, true>(a, b, fp8_fold2<T, OPC, false>(a, b, 0u));
+}
+// s * x on the two elements in word HI of x (s: one fp8 value in the low byte), one rounding
+template <typename T, bool HI>
+__device__ __forceinline__ uint32_t fp8_scale2(uint32_t s, uint32_t x, uint32_t old) {
+  const float fs = Fp8<T>::template dec2<false>(s & 0xffu).x;
+  const v2f r = Fp8<T>::template dec2<HI>(x) * fs;
+  return Fp8<T>::template enc2<HI>(fp8_sat<T>(r.x), fp8_sat<T>(r.y), old);
+}
+
+#define MNCCL_FP8_OP(T, OPC)                                          \
+  template <> struct Op<T, OPC> {                                     \
+    __device__ static T f(T a, T b) {                                 \
+      T r;                                                            \
+      r.v = (uint8_t)fp8_fold2<T, OPC, false>(a.v, b.v, 0u);          \
+      return r;                                                       \
+    }                                                                 \
+  };
+MNCCL_FP8_OP(e4m3_t, kSum) MNCCL_FP8_OP(e4m3_t, kProd) MNCCL_FP8_OP(e4m3_t, kMax) MNCCL_FP8_OP(e4m3_t, kMin)
+MNCCL_FP8_OP(e5m2_t, kSum) MNCCL_FP8_OP(e5m2_t, kProd) MNCCL_FP8_OP(e5m2_t, kMax) MNCCL_FP8_OP(e5m2_t, kMin)
+#undef MNCCL_FP8_OP
+
 
 // kPreMulSum (ncclRedOpCreatePreMulSum): the sum of inputs that were scaled on their way in.  Every
 // rank's input element becomes y = round_T(s * x) where it enters a fold (prescale below) -- ONE
@@ -166,6 +248,22 @@ template <> struct Scale<int32_t> {
   __device__ static int32_t f(u64 s, int32_t x) { return (int32_t)((uint32_t)s * (uint32_t)x); }
 };
 
+// fp8: the scalar is one fp8 byte; y = encode(float(s) * float(x)), the product exact in f32
+template <> struct Scale<e4m3_t> {
+  __device__ static e4m3_t f(u64 s, e4m3_t x) {
+    e4m3_t r;
+    r.v = (uint8_t)fp8_scale2<e4m3_t, false>((uint32_t)s, x.v, 0u);
+    return r;
+  }
+};
+template <> struct Scale<e5m2_t> {
+  __device__ static e5m2_t f(u64 s, e5m2_t x) {
+    e5m2_t r;
+    r.v = (uint8_t)fp8_scale2<e5m2_t, false>((uint32_t)s, x.v, 0u);
+    return r;
+  }
+};
+
 template <typename T> struct alignas(16) Pack16 { T x[16 / sizeof(T)]; };
 
 // an input on its way into a fold: scaled for kPreMulSum, untouched (and no code) for every other op
@@ -176,7 +274,13 @@ __device__ __forceinline__ T prescale(T x, u64 s) {
 }
 template <typename T, int OPC>
 __device__ __forceinline__ v4u prescale16(v4u a, u64 s) {
-  if constexpr (OPC == kPreMulSum) {
+  if constexpr (OPC == kPreMulSum && IsFp8<T>::value) {
+    // (fp8: dword by dword, so that two elements share each conversion)
+    v4u r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = fp8_scale2<T, true>((uint32_t)s, a[i], fp8_scale2<T, false>((uint32_t)s, a[i], 0u));
+    return r;
+  } else if constexpr (OPC == kPreMulSum) {
     Pack16<T> pa = __builtin_bit_cast(Pack16<T>, a);
 #pragma unroll
     for (int i = 0; i < (int)(16 / sizeof(T)); ++i) pa.x[i] = Scale<T>::f(s, pa.x[i]);
@@ -188,11 +292,19 @@ __device__ __forceinline__ v4u prescale16(v4u a, u64 s) {
 
 template <typename T, int OPC>
 __device__ __forceinline__ v4u reduce16(v4u a, v4u b) {
-  Pack16<T> pa = __builtin_bit_cast(Pack16<T>, a);
-  const Pack16<T> pb = __builtin_bit_cast(Pack16<T>, b);
+  if constexpr (IsFp8<T>::value) {
+    // 16 elements, dword by dword: two elements per conversion each way (8 + 8 in, 8 out)
+    v4u r;
 #pragma unroll
-  for (int i = 0; i < (int)(16 / sizeof(T)); ++i) pa.x[i] = Op<T, OPC>::f(pa.x[i], pb.x[i]);
-  return __builtin_bit_cast(v4u, pa);
+    for (int i = 0; i < 4; ++i) r[i] = fp8_fold4<T, OPC == kPreMulSum ? kSum : OPC>(a[i], b[i]);
+    return r;
+  } else {
+    Pack16<T> pa = __builtin_bit_cast(Pack16<T>, a);
+    const Pack16<T> pb = __builtin_bit_cast(Pack16<T>, b);
+#pragma unroll
+    for (int i = 0; i < (int)(16 / sizeof(T)); ++i) pa.x[i] = Op<T, OPC>::f(pa.x[i], pb.x[i]);
+    return __builtin_bit_cast(v4u, pa);
+  }
 }
 
 // ---------------------------------------------------------------- memory primitives
@@ -235,6 +347,11 @@ __device__ __forceinline__ void st_g16(char* p, v4u v) { __builtin_nontemporal_s
 
 // scalar (unaligned-count) path: one element per access
 template <int SZ> struct Scal;
+template <> struct Scal<1> {
+  typedef uint8_t U;
+  __device__ static U ld(rsrc_t r, uint32_t o) { return __builtin_amdgcn_raw_buffer_load_b8(r, o, 0, kAuxSys); }
+  __device__ static void st(rsrc_t r, uint32_t o, U v) { __builtin_amdgcn_raw_buffer_store_b8(v, r, o, 0, kAuxSys); }
+};
 template <> struct Scal<2> {
   typedef uint16_t U;
   __device__ static U ld(rsrc_t r, uint32_t o) { return __builtin_amdgcn_raw_buffer_load_b16(r, o, 0, kAuxSys); }
@@ -665,6 +782,13 @@ template <typename T, bool VEC>
 __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scaled_ring(CollParams p) {
   ring_body<T, kPreMulSum, VEC>(p);
 }
+// The fp8 types' entry points (the `fp8_*` family: the built-in kernels' instantiation sets are
+// pinned by name and count, so the one-byte types get names of their own over the same bodies, as
+// kPreMulSum got scaled_*); OPC: the four built-in ops and kPreMulSum.
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) fp8_ring(CollParams p) {
+  ring_body<T, OPC, VEC>(p);
+}
 
 constexpr int kMaxWaves = kMaxThreads / 64;
 
@@ -995,6 +1119,10 @@ template <typename T, bool VEC>
 __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scaled_read(CollParams p) {
   read_body<T, kPreMulSum, VEC>(p);
 }
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) fp8_read(CollParams p) {
+  read_body<T, OPC, VEC>(p);
+}
 
 // ---------------------------------------------------------------- the read schedule's two halves
 // ncclReduceScatter (scatter_fold) and ncclAllGather (gather_push) on device buffers every rank
@@ -1075,6 +1203,11 @@ template <typename T, bool VEC>
 __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scaled_scatter(CollParams p) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, kPreMulSum, VEC, false>(p, coff, len, lane); });
+}
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) fp8_scatter(CollParams p) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, OPC, VEC, false>(p, coff, len, lane); });
 }
 
 // ---------------------------------------------------------------- copy and push
@@ -1177,12 +1310,22 @@ __device__ __forceinline__ void copy_push_slice(const CollParams& p, const char*
 // and goes to all n - 1 peers; in place, this rank's chunk already is in its recv.  No arithmetic,
 // so by element size only.  Only rank q ever writes chunk q of any recv, and nobody reads a recv
 // inside the call.  Each GPU's HBM moves n + 1 chunks per call (one read, n writes landing in it).
+// (The kernels that only copy have their code in a *_body function too: the entry point named for
+// the element sizes 2 / 4 / 8, and a `byte_*` one for element size 1 -- the fp8 types -- beside it.)
 template <int ESZ, bool VEC>
-__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) gather_push(CollParams p) {
+__device__ __forceinline__ void gather_body(const CollParams& p) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) {
     copy_push_slice<ESZ, VEC, true>(p, p.send, p.send != p.recv, p.n - 1, 0, coff, len, lane);
   });
+}
+template <int ESZ, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) gather_push(CollParams p) {
+  gather_body<ESZ, VEC>(p);
+}
+template <bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) byte_gather(CollParams p) {
+  gather_body<1, VEC>(p);
 }
 
 // ---------------------------------------------------------------- the rooted collectives
@@ -1215,6 +1358,12 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scaled_root(Col
   read_half<true>(p, s_tx, s_rx,
                   [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, kPreMulSum, VEC, false>(p, coff, len, lane); });
 }
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) fp8_root(CollParams p) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half<true>(p, s_tx, s_rx,
+                  [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, OPC, VEC, false>(p, coff, len, lane); });
+}
 
 // Broadcast: rank r copies its slices of chunk r from the root's send -- sc0 sc1 loads over the
 // link, as the fold loads its peers; the root reads its own send non-temporal, as gather_push does
@@ -1230,7 +1379,7 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scaled_root(Col
 // No arithmetic, so by element size only.  Only rank c ever writes chunk c of any recv, nobody
 // reads a recv inside the call, and the root's send is only read (in place: see above).
 template <int ESZ, bool VEC>
-__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) root_relay(CollParams p) {
+__device__ __forceinline__ void relay_body(const CollParams& p) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   // one slice, by role: its source, whether this rank's recv takes it, and the D destinations
   auto slice = [&p](auto is_root, u64 coff, uint32_t len, int lane) {
@@ -1246,6 +1395,14 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) root_relay(Coll
     read_half<true>(p, s_tx, s_rx, [&](u64 coff, uint32_t len, int lane) { slice(std::true_type{}, coff, len, lane); });
   else
     read_half<true>(p, s_tx, s_rx, [&](u64 coff, uint32_t len, int lane) { slice(std::false_type{}, coff, len, lane); });
+}
+template <int ESZ, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) root_relay(CollParams p) {
+  relay_body<ESZ, VEC>(p);
+}
+template <bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) byte_relay(CollParams p) {
+  relay_body<1, VEC>(p);
 }
 
 // ---------------------------------------------------------------- the all-to-all
@@ -1342,11 +1499,19 @@ __device__ __forceinline__ void exchange_slice(const CollParams& p, uint64_t sof
 // No arithmetic, so by element size only.  read_half hands the slice's offset in chunk `rank`; the
 // slice's offset within a block is what every block shares.
 template <int ESZ, bool VEC>
-__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) exchange_push(CollParams p) {
+__device__ __forceinline__ void exchange_body(const CollParams& p) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) {
     exchange_slice<ESZ, VEC>(p, coff - (u64)p.rank * p.chunk_bytes, len, lane);
   });
+}
+template <int ESZ, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) exchange_push(CollParams p) {
+  exchange_body<ESZ, VEC>(p);
+}
+template <bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) byte_exchange(CollParams p) {
+  exchange_body<1, VEC>(p);
 }
 
 // ---------------------------------------------------------------- gather and scatter
@@ -1467,19 +1632,35 @@ __device__ __forceinline__ void deal_slice(const CollParams& p, uint64_t soff, u
 
 // No arithmetic, so by element size only.  launch_persistent refuses a root outside [0, n).
 template <int ESZ, bool VEC>
-__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) collect_push(CollParams p) {
+__device__ __forceinline__ void collect_body(const CollParams& p) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { collect_slice<ESZ, VEC>(p, coff, len, lane); });
+}
+template <int ESZ, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) collect_push(CollParams p) {
+  collect_body<ESZ, VEC>(p);
+}
+template <bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) byte_collect(CollParams p) {
+  collect_body<1, VEC>(p);
 }
 
 // read_half hands the slice's offset in chunk `rank`; the slice's offset within a block is what
 // every block shares.
 template <int ESZ, bool VEC>
-__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) deal_push(CollParams p) {
+__device__ __forceinline__ void deal_body(const CollParams& p) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   read_half(p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) {
     if (p.rank == p.root) deal_slice<ESZ, VEC>(p, coff - (u64)p.rank * p.chunk_bytes, len, lane);
   });
+}
+template <int ESZ, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) deal_push(CollParams p) {
+  deal_body<ESZ, VEC>(p);
+}
+template <bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) byte_deal(CollParams p) {
+  deal_body<1, VEC>(p);
 }
 
 // ---------------------------------------------------------------- the variable all-to-all
@@ -1583,11 +1764,18 @@ __device__ __forceinline__ void varblock_slice(const CollParams& p, const VarBlo
 // read_half hands the slice's offset in chunk `rank` of the largest-block geometry; the slice's
 // offset within a block is what every block shares.
 template <int ESZ>
-__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) varblock_push(CollParams p, VarBlockArgs v) {
+__device__ __forceinline__ void varblock_body(const CollParams& p, const VarBlockArgs& v) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   read_half(p, s_tx, s_rx, [&p, &v](u64 coff, uint32_t, int lane) {
     varblock_slice<ESZ>(p, v, coff - (u64)p.rank * p.chunk_bytes, lane);
   });
+}
+template <int ESZ>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) varblock_push(CollParams p, VarBlockArgs v) {
+  varblock_body<ESZ>(p, v);
+}
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) byte_varblock(CollParams p, VarBlockArgs v) {
+  varblock_body<1>(p, v);
 }
 
 // ---------------------------------------------------------------- point to point
@@ -1621,6 +1809,14 @@ typedef _Float16 P2pElem;  // the element path's 2-byte unit (moved, never used 
 __device__ __forceinline__ u64 uniform64(u64 v) {
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
   return ((u64)hi << 32) | lo;
+}
+
+// The element path moves 2-byte units; a message of a one-byte datatype (the fp8 types) may end on an
+// odd byte, which only a message's last slice can hold: lane 0 moves it, into the slot or out of it.
+__device__ __forceinline__ void p2p_last_byte(bool sends, char* at, rsrc_t slot, uint32_t len, int lane) {
+  if (!(len & 1u) || lane != 0) return;
+  if (sends) Scal<1>::st(slot, len - 1, (uint8_t)at[len - 1]);
+  else at[len - 1] = (char)Scal<1>::ld(slot, len - 1);
 }
 
 // the self copies, spread over the launch's self waves: wave k of K takes batches k, k + K, ...
@@ -1679,11 +1875,13 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) p2p_kernel(Coll
         const rsrc_t out = make_rsrc(msg_slot(p, C, r, peer, w, seq), len);
         if (vec) move<P2pElem, kSum, true, kSend>(at, at, out, out, len, lane);
         else move<P2pElem, kSum, false, kSend>(at, at, out, out, len, lane);
+        p2p_last_byte(true, at, out, len, lane);
       } else {
         acquire_sys(p.sys_fence);
         const rsrc_t in = make_rsrc(msg_slot(p, C, peer, r, w, seq), len);
         if (vec) move<P2pElem, kSum, true, kCopy>(at, at, in, in, len, lane);
         else move<P2pElem, kSum, false, kCopy>(at, at, in, in, len, lane);
+        p2p_last_byte(false, at, in, len, lane);
       }
       drain_stores();  // every load of the slot has returned and every store has landed
       ++seq;
@@ -1747,6 +1945,7 @@ __device__ __forceinline__ void p2p_push_direct(const char* src, char* dst, u64 
     if (done == len) continue;
     const rsrc_t s = make_rsrc(src + at(k), len), d = make_rsrc(dst + at(k), len);
     for (uint32_t i = done / 2 + (uint32_t)lane; i < len / 2; i += 64) Scal<2>::st(d, i * 2, Scal<2>::ld(s, i * 2));
+    if ((len & 1u) && lane == 0) Scal<1>::st(d, len - 1, Scal<1>::ld(s, len - 1));  // (a one-byte datatype's odd count)
   }
 }
 
@@ -1849,11 +2048,13 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) p2p_window_grou
         const rsrc_t out = make_rsrc(msg_slot(p, C, r, peer, w, seq), len);
         if (vec) move<P2pElem, kSum, true, kSend>(at, at, out, out, len, lane);
         else move<P2pElem, kSum, false, kSend>(at, at, out, out, len, lane);
+        p2p_last_byte(true, at, out, len, lane);
       } else {
         acquire_sys(p.sys_fence);
         const rsrc_t in = make_rsrc(msg_slot(p, C, peer, r, w, seq), len);
         if (vec) move<P2pElem, kSum, true, kCopy>(at, at, in, in, len, lane);
         else move<P2pElem, kSum, false, kCopy>(at, at, in, in, len, lane);
+        p2p_last_byte(false, at, in, len, lane);
       }
       drain_stores();
       ++seq;
@@ -1914,7 +2115,7 @@ __global__ void __launch_bounds__(64) read_start_kernel(CollParams p) {
 // slots, as read_fold_all), folded in ring order, stored into my recv and pushed into every
 // peer's recv (the push order rotated by workgroup so the workgroups' stores spread over the links)
 template <typename T, int OPC, int G, int V>
-__global__ void __launch_bounds__(64) read_grid_kernel(CollParams p) {
+__device__ __forceinline__ void grid_body(const CollParams& p) {
   if (*p.go != p.call_seq) return;  // START failed: the peers' buffers are not ours to touch
   constexpr uint32_t B = 64u * 16u * V;
   const uint32_t batch = blockIdx.x;
@@ -1954,6 +2155,14 @@ __global__ void __launch_bounds__(64) read_grid_kernel(CollParams p) {
     }
   drain_stores();  // every push acknowledged by the peer's memory before this wave ends
 }
+template <typename T, int OPC, int G, int V>
+__global__ void __launch_bounds__(64) read_grid_kernel(CollParams p) {
+  grid_body<T, OPC, G, V>(p);
+}
+template <typename T, int OPC, int G, int V>
+__global__ void __launch_bounds__(64) fp8_grid(CollParams p) {
+  grid_body<T, OPC, G, V>(p);
+}
 
 __global__ void __launch_bounds__(64) read_done_kernel(CollParams p) {
   if (*p.go != p.call_seq) return;  // START failed and already raised the peers' ABORT words
@@ -1989,7 +2198,7 @@ __global__ void __launch_bounds__(64) read_done_kernel(CollParams p) {
 // pipelines of a slice run side by side: a 4 KiB call at 8 ranks is 8 waves, each one piece
 // out, one flag round, one fold.  Costs (n-1) x the call's bytes out per rank: small calls only.
 template <typename T, int OPC, bool VEC>
-__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) oneshot_kernel(CollParams p) {
+__device__ __forceinline__ void oneshot_body(const CollParams& p) {
   signal_start(p);
   const WaveId id = wave_id();
   const int lane = id.lane, w = id.w, C = p.pipes, wv = id.wv;
@@ -2082,6 +2291,14 @@ aborted:
   if (lane == 0)
     for (int k = 1; k < n; ++k) st_sys(p.peer_mbox[direct_peer(n, r, k)] + mbox_abort(n, C), abort_word(p));
 }
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) oneshot_kernel(CollParams p) {
+  oneshot_body<T, OPC, VEC>(p);
+}
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) fp8_oneshot(CollParams p) {
+  oneshot_body<T, OPC, VEC>(p);
+}
 
 // ---------------------------------------------------------------- local reduce
 // One 16-byte vector per lane, one wave per workgroup, one workgroup per 1 KiB of output,
@@ -2090,44 +2307,55 @@ aborted:
 // the 8 TB/s spec, vs 5.84 TB/s for a 4096-block grid-stride loop with 4 vectors per lane
 // and 5.27 TB/s with plain (temporal) loads/stores.  Short-lived single-wave workgroups
 // let the dispatcher keep every CU's memory pipeline full without a tail.
-template <typename T, int OPC>
-__global__ void __launch_bounds__(64) local_reduce_vec(char* __restrict__ out, const char* __restrict__ a,
-                                                       const char* __restrict__ b, u64 nvec) {
-  const u64 i = (u64)blockIdx.x * 64 + threadIdx.x;
-  if (i < nvec) {
-    const v4u x = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(a) + i);
-    const v4u y = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(b) + i);
-    __builtin_nontemporal_store(reduce16<T, OPC>(x, y), reinterpret_cast<v4u*>(out) + i);
+// The three kernels are stamped twice, under the names they always had for the five wider datatypes
+// and under fp8_local_* for the fp8 types (instantiation sets are pinned by name; as whole kernels,
+// not over a shared body function: inlined from one, the grid-stride forms read blockDim another way
+// and the flagship kernel must compile to what it was).
+//   VECK: one vector per lane; GSK: grid-stride form for buffers beyond 2^32 threads of the exact grid
+//   (> 64 GiB); ELEMK: element by element (the last bytes % 16, and buffers that are not dword-aligned)
+#define MNCCL_LOCAL_KERNELS(VECK, GSK, ELEMK)                                                                          \
+  template <typename T, int OPC>                                                                                       \
+  __global__ void __launch_bounds__(64) VECK(char* __restrict__ out, const char* __restrict__ a,                       \
+                                             const char* __restrict__ b, u64 nvec) {                                   \
+    const u64 i = (u64)blockIdx.x * 64 + threadIdx.x;                                                                  \
+    if (i < nvec) {                                                                                                    \
+      const v4u x = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(a) + i);                                   \
+      const v4u y = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(b) + i);                                   \
+      __builtin_nontemporal_store(reduce16<T, OPC>(x, y), reinterpret_cast<v4u*>(out) + i);                            \
+    }                                                                                                                  \
+  }                                                                                                                    \
+  template <typename T, int OPC>                                                                                       \
+  __global__ void __launch_bounds__(256) GSK(char* __restrict__ out, const char* __restrict__ a,                       \
+                                             const char* __restrict__ b, u64 nvec) {                                   \
+    const u64 stride = (u64)gridDim.x * blockDim.x;                                                                    \
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {                                  \
+      const v4u x = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(a) + i);                                   \
+      const v4u y = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(b) + i);                                   \
+      __builtin_nontemporal_store(reduce16<T, OPC>(x, y), reinterpret_cast<v4u*>(out) + i);                            \
+    }                                                                                                                  \
+  }                                                                                                                    \
+  template <typename T, int OPC>                                                                                       \
+  __global__ void __launch_bounds__(256) ELEMK(T* __restrict__ out, const T* __restrict__ a, const T* __restrict__ b,  \
+                                               u64 n) {                                                                \
+    const u64 stride = (u64)gridDim.x * blockDim.x;                                                                    \
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = Op<T, OPC>::f(a[i], b[i]);   \
   }
-}
-
-// grid-stride form for buffers beyond 2^32 threads of the exact grid (> 64 GiB)
-template <typename T, int OPC>
-__global__ void __launch_bounds__(256) local_reduce_vec_gs(char* __restrict__ out, const char* __restrict__ a,
-                                                           const char* __restrict__ b, u64 nvec) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-    const v4u x = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(a) + i);
-    const v4u y = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(b) + i);
-    __builtin_nontemporal_store(reduce16<T, OPC>(x, y), reinterpret_cast<v4u*>(out) + i);
-  }
-}
-
-template <typename T, int OPC>
-__global__ void __launch_bounds__(256) local_reduce_scalar(T* __restrict__ out, const T* __restrict__ a,
-                                                           const T* __restrict__ b, u64 n) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = Op<T, OPC>::f(a[i], b[i]);
-}
+MNCCL_LOCAL_KERNELS(local_reduce_vec, local_reduce_vec_gs, local_reduce_scalar)
+MNCCL_LOCAL_KERNELS(fp8_local_vec, fp8_local_gs, fp8_local_elem)
+#undef MNCCL_LOCAL_KERNELS
 
 // kPreMulSum on a communicator of one rank: the call is no copy but out[i] = round_T(s * in[i]), the
 // same single rounding the folds apply (Scale).  out may be in (in place): an element is read and
-// written by one thread.
-template <typename T>
-__global__ void __launch_bounds__(256) scale_kernel(T* out, const T* in, u64 n, u64 s) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = Scale<T>::f(s, in[i]);
-}
+// written by one thread.  (Stamped twice, as the local-reduce kernels are.)
+#define MNCCL_SCALE_KERNEL(NAME)                                                                                  \
+  template <typename T>                                                                                           \
+  __global__ void __launch_bounds__(256) NAME(T* out, const T* in, u64 n, u64 s) {                                \
+    const u64 stride = (u64)gridDim.x * blockDim.x;                                                               \
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = Scale<T>::f(s, in[i]);  \
+  }
+MNCCL_SCALE_KERNEL(scale_kernel)
+MNCCL_SCALE_KERNEL(fp8_scale)
+#undef MNCCL_SCALE_KERNEL
 
 // ---------------------------------------------------------------- link probe
 struct ProbeArgs {
@@ -2217,6 +2445,19 @@ static hipError_t for_dtype(int dtype, F&& f) {
   }
 }
 
+// the fp8 types: dispatched apart, to entry points of their own (the fp8_* / byte_* kernels), so
+// that for_dtype and for_elem_size keep instantiating exactly the kernels they always did
+static bool is_fp8(int dtype) { return dtype == kF8E4M3 || dtype == kF8E5M2; }
+
+template <typename F>
+static hipError_t for_fp8(int dtype, F&& f) {
+  switch (dtype) {
+    case kF8E4M3: return f(TypeTag<e4m3_t>{});
+    case kF8E5M2: return f(TypeTag<e5m2_t>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
 template <typename F>
 static hipError_t for_op(int op, F&& f) {
   switch (op) {
@@ -2228,6 +2469,13 @@ static hipError_t for_op(int op, F&& f) {
   }
 }
 
+// the fp8 family's ops: the four built-ins and kPreMulSum (one template parameter, no second entry point)
+template <typename F>
+static hipError_t for_fp8_op(int op, F&& f) {
+  return op == kPreMulSum ? f(IntTag<kPreMulSum>{}) : for_op(op, f);
+}
+
+// (element size 1 is not here: the callers send it to the byte_* kernels)
 template <typename F>
 static hipError_t for_elem_size(int dtype, F&& f) {
   switch (dtype_size(dtype)) {
@@ -2265,15 +2513,20 @@ static hipError_t local_for(void* out, const void* a, const void* b, u64 count, 
   const u64 nvec = vec ? count * sizeof(T) / 16 : 0;
   const u64 done = nvec * 16 / sizeof(T);
   const u64 kMaxExactBlocks = (1ull << 31) / 64;  // keep the exact grid under 2^31 threads
-  if (nvec && (nvec + 63) / 64 <= kMaxExactBlocks)
-    hipLaunchKernelGGL((local_reduce_vec<T, OPC>), dim3((unsigned)((nvec + 63) / 64)), dim3(64), 0, st, (char*)out,
-                       (const char*)a, (const char*)b, nvec);
-  else if (nvec)
-    hipLaunchKernelGGL((local_reduce_vec_gs<T, OPC>), dim3(16384), dim3(256), 0, st, (char*)out, (const char*)a,
-                       (const char*)b, nvec);
-  if (count > done)
-    hipLaunchKernelGGL((local_reduce_scalar<T, OPC>), dim3((unsigned)std::min<u64>((count - done + 255) / 256, 16384)),
-                       dim3(256), 0, st, (T*)out + done, (const T*)a + done, (const T*)b + done, count - done);
+  // (the fp8 types: the same three kernels under their fp8_local_* names)
+  constexpr bool f8 = IsFp8<T>::value;
+  const dim3 exact((unsigned)((nvec + 63) / 64)), rest((unsigned)std::min<u64>((count - done + 255) / 256, 16384));
+  if (nvec && (nvec + 63) / 64 <= kMaxExactBlocks) {
+    if constexpr (f8) hipLaunchKernelGGL((fp8_local_vec<T, OPC>), exact, dim3(64), 0, st, (char*)out, (const char*)a, (const char*)b, nvec);
+    else hipLaunchKernelGGL((local_reduce_vec<T, OPC>), exact, dim3(64), 0, st, (char*)out, (const char*)a, (const char*)b, nvec);
+  } else if (nvec) {
+    if constexpr (f8) hipLaunchKernelGGL((fp8_local_gs<T, OPC>), dim3(16384), dim3(256), 0, st, (char*)out, (const char*)a, (const char*)b, nvec);
+    else hipLaunchKernelGGL((local_reduce_vec_gs<T, OPC>), dim3(16384), dim3(256), 0, st, (char*)out, (const char*)a, (const char*)b, nvec);
+  }
+  if (count > done) {
+    if constexpr (f8) hipLaunchKernelGGL((fp8_local_elem<T, OPC>), rest, dim3(256), 0, st, (T*)out + done, (const T*)a + done, (const T*)b + done, count - done);
+    else hipLaunchKernelGGL((local_reduce_scalar<T, OPC>), rest, dim3(256), 0, st, (T*)out + done, (const T*)a + done, (const T*)b + done, count - done);
+  }
   return hipGetLastError();
 }
 
@@ -2292,38 +2545,64 @@ static hipError_t launch_on(K kernel, int C, int nt, const CollParams& p, hipStr
 hipError_t launch_persistent(int kernel, int dtype, int op, bool vec, int C, int nt, const CollParams& p,
                              hipStream_t st) {
   const bool root_ok = p.root >= 0 && p.root < p.n;
-  // K: the kernel of the four built-in ops; S: its entry point for kPreMulSum (no op parameter)
-#define FOLDS(K, S)                                                                                           \
-  (op == kPreMulSum ? for_dtype(dtype, [&](auto t) {                                                          \
+  // K: the kernel of the four built-in ops; S: its entry point for kPreMulSum (no op parameter);
+  // F: the fp8 types' entry point (all five ops).  B: a copy kernel's entry point for element size 1
+#define FP8_FOLDS(F)                                                                                          \
+  for_fp8(dtype, [&](auto t) {                                                                                \
+    return for_fp8_op(op, [&](auto o) {                                                                       \
+      return for_vec(vec, [&](auto v) {                                                                       \
+        return launch_on(F<typename decltype(t)::type, decltype(o)::value, decltype(v)::value>, C, nt, p, st); \
+      });                                                                                                     \
+    });                                                                                                       \
+  })
+#define FOLDS(K, S, F)                                                                                        \
+  (is_fp8(dtype) ? FP8_FOLDS(F) : op == kPreMulSum ? for_dtype(dtype, [&](auto t) {                                                          \
     return for_vec(vec, [&](auto v) { return launch_on(S<typename decltype(t)::type, decltype(v)::value>, C, nt, p, st); }); \
   }) : for_type_op_vec(dtype, op, vec, [&](auto t, auto o, auto v) {                                          \
     return launch_on(K<typename decltype(t)::type, decltype(o)::value, decltype(v)::value>, C, nt, p, st);   \
   }))
-#define COPIES(K) \
-  for_size_vec(dtype, vec, [&](auto e, auto v) { return launch_on(K<decltype(e)::value, decltype(v)::value>, C, nt, p, st); })
+#define COPIES(K, B)                                                                                     \
+  (dtype_size(dtype) == 1 ? for_vec(vec, [&](auto v) { return launch_on(B<decltype(v)::value>, C, nt, p, st); }) \
+                          : for_size_vec(dtype, vec, [&](auto e, auto v) {                                 \
+                              return launch_on(K<decltype(e)::value, decltype(v)::value>, C, nt, p, st);   \
+                            }))
   switch (kernel) {
-    case kKernelRing: return FOLDS(ring_kernel, scaled_ring);
-    case kKernelRead: return FOLDS(read_kernel, scaled_read);
+    case kKernelRing: return FOLDS(ring_kernel, scaled_ring, fp8_ring);
+    case kKernelRead: return FOLDS(read_kernel, scaled_read, fp8_read);
         // (no one-shot form of kPreMulSum: Comm::collective routes such a call to the read schedule or the ring)
     case kKernelOneshot:
-      return op == kPreMulSum ? hipErrorInvalidValue : for_type_op_vec(dtype, op, vec, [&](auto t, auto o, auto v) {
+      if (op == kPreMulSum) return hipErrorInvalidValue;
+      if (is_fp8(dtype))
+        return for_fp8(dtype, [&](auto t) {
+          return for_op(op, [&](auto o) {
+            return for_vec(vec, [&](auto v) {
+              return launch_on(fp8_oneshot<typename decltype(t)::type, decltype(o)::value, decltype(v)::value>, C, nt, p, st);
+            });
+          });
+        });
+      return for_type_op_vec(dtype, op, vec, [&](auto t, auto o, auto v) {
         return launch_on(oneshot_kernel<typename decltype(t)::type, decltype(o)::value, decltype(v)::value>, C, nt, p, st);
       });
-    case kKernelScatterFold: return p.coll == kCollReduceScatter ? FOLDS(scatter_fold, scaled_scatter) : hipErrorInvalidValue;
-    case kKernelGatherPush: return p.coll == kCollAllGather ? COPIES(gather_push) : hipErrorInvalidValue;
-    case kKernelRootFold: return p.coll == kCollReduce && root_ok ? FOLDS(root_fold, scaled_root) : hipErrorInvalidValue;
-    case kKernelRootRelay: return p.coll == kCollBroadcast && root_ok ? COPIES(root_relay) : hipErrorInvalidValue;
-    case kKernelExchangePush: return p.coll == kCollAllToAll && p.n >= 2 ? COPIES(exchange_push) : hipErrorInvalidValue;
-    case kKernelCollectPush: return p.coll == kCollGather && root_ok && p.n >= 2 ? COPIES(collect_push) : hipErrorInvalidValue;
-    case kKernelDealPush: return p.coll == kCollScatter && root_ok && p.n >= 2 ? COPIES(deal_push) : hipErrorInvalidValue;
+    case kKernelScatterFold: return p.coll == kCollReduceScatter ? FOLDS(scatter_fold, scaled_scatter, fp8_scatter) : hipErrorInvalidValue;
+    case kKernelGatherPush: return p.coll == kCollAllGather ? COPIES(gather_push, byte_gather) : hipErrorInvalidValue;
+    case kKernelRootFold: return p.coll == kCollReduce && root_ok ? FOLDS(root_fold, scaled_root, fp8_root) : hipErrorInvalidValue;
+    case kKernelRootRelay: return p.coll == kCollBroadcast && root_ok ? COPIES(root_relay, byte_relay) : hipErrorInvalidValue;
+    case kKernelExchangePush: return p.coll == kCollAllToAll && p.n >= 2 ? COPIES(exchange_push, byte_exchange) : hipErrorInvalidValue;
+    case kKernelCollectPush: return p.coll == kCollGather && root_ok && p.n >= 2 ? COPIES(collect_push, byte_collect) : hipErrorInvalidValue;
+    case kKernelDealPush: return p.coll == kCollScatter && root_ok && p.n >= 2 ? COPIES(deal_push, byte_deal) : hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
 #undef COPIES
 #undef FOLDS
+#undef FP8_FOLDS
 }
 
 hipError_t launch_varblock(int dtype, int C, int nt, const CollParams& p, const VarBlockArgs& v, hipStream_t st) {
   if (p.coll != kCollAllToAllV || p.n < 2) return hipErrorInvalidValue;
+  if (dtype_size(dtype) == 1) {
+    hipLaunchKernelGGL(byte_varblock, dim3(C), dim3(nt), 0, st, p, v);
+    return hipGetLastError();
+  }
   return for_elem_size(dtype, [&](auto e) {
     hipLaunchKernelGGL(varblock_push<decltype(e)::value>, dim3(C), dim3(nt), 0, st, p, v);
     return hipGetLastError();
@@ -2375,7 +2654,8 @@ static hipError_t read_grid_launch(const CollParams& p, hipStream_t st) {
     // V 16-byte vectors per lane per workgroup: V KiB of the chunk each
     const uint64_t per_block = 1024ull * (uint64_t)V;
     const unsigned blocks = (unsigned)((p.chunk_bytes + per_block - 1) / per_block);
-    hipLaunchKernelGGL((read_grid_kernel<T, OPC, G, V>), dim3(blocks), dim3(64), 0, st, p);
+    if constexpr (IsFp8<T>::value) hipLaunchKernelGGL((fp8_grid<T, OPC, G, V>), dim3(blocks), dim3(64), 0, st, p);
+    else hipLaunchKernelGGL((read_grid_kernel<T, OPC, G, V>), dim3(blocks), dim3(64), 0, st, p);
     return hipGetLastError();
   } else {
     return hipErrorInvalidValue;
@@ -2412,11 +2692,12 @@ hipError_t launch_read_grid(int dtype, int op, const CollParams& p, hipStream_t 
   hipLaunchKernelGGL(read_start_kernel, dim3(1), dim3(64), 0, st, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  e = for_dtype(dtype, [&](auto t) {
+  auto grid = [&](auto t) {
     using T = typename decltype(t)::type;
     if (op == kPreMulSum) return read_grid_for<T, kPreMulSum>(p, st, vectors);
     return for_op(op, [&](auto o) { return read_grid_for<T, decltype(o)::value>(p, st, vectors); });
-  });
+  };
+  e = is_fp8(dtype) ? for_fp8(dtype, grid) : for_dtype(dtype, grid);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(read_done_kernel, dim3(1), dim3(64), 0, st, p);
   return hipGetLastError();
@@ -2425,21 +2706,24 @@ hipError_t launch_read_grid(int dtype, int op, const CollParams& p, hipStream_t 
 hipError_t launch_local_reduce(int dtype, int op, void* out, const void* local, const void* incoming, uint64_t count,
                                hipStream_t st) {
   if (count == 0) return hipSuccess;
-  return for_dtype(dtype, [&](auto t) {
+  auto run = [&](auto t) {
     return for_op(op, [&](auto o) {
       return local_for<typename decltype(t)::type, decltype(o)::value>(out, local, incoming, count, st);
     });
-  });
+  };
+  return is_fp8(dtype) ? for_fp8(dtype, run) : for_dtype(dtype, run);
 }
 
 hipError_t launch_scale(int dtype, void* out, const void* in, uint64_t count, uint64_t scale, hipStream_t st) {
   if (count == 0) return hipSuccess;
-  return for_dtype(dtype, [&](auto t) {
+  auto run = [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(scale_kernel<T>, dim3((unsigned)std::min<u64>((count + 255) / 256, 16384)), dim3(256), 0, st, (T*)out,
-                       (const T*)in, (u64)count, (u64)scale);
+    const dim3 grid((unsigned)std::min<u64>((count + 255) / 256, 16384));
+    if constexpr (IsFp8<T>::value) hipLaunchKernelGGL(fp8_scale<T>, grid, dim3(256), 0, st, (T*)out, (const T*)in, (u64)count, (u64)scale);
+    else hipLaunchKernelGGL(scale_kernel<T>, grid, dim3(256), 0, st, (T*)out, (const T*)in, (u64)count, (u64)scale);
     return hipGetLastError();
-  });
+  };
+  return is_fp8(dtype) ? for_fp8(dtype, run) : for_dtype(dtype, run);
 }
 
 bool dtype_supported(int dtype) { return dtype_size(dtype) != 0; }
@@ -2449,6 +2733,7 @@ int dtype_size(int dtype) {
     case kF32: case kI32: return 4;
     case kF64: return 8;
     case kF16: case kBF16: return 2;
+    case kF8E4M3: case kF8E5M2: return 1;
     default: return 0;
   }
 }

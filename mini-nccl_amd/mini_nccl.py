@@ -31,6 +31,8 @@ ncclInProgress = 7
 # ncclDataType_t (reference :29-40)
 ncclInt8, ncclUint8, ncclInt32, ncclUint32, ncclInt64, ncclUint64 = 0, 1, 2, 3, 4, 5
 ncclFloat16, ncclFloat, ncclDouble, ncclBfloat16 = 6, 7, 8, 9
+# the OCP fp8 types (include/mini_nccl_ext.h; NCCL's and RCCL's values)
+ncclFloat8e4m3, ncclFloat8e5m2 = 10, 11
 
 # ncclRedOp_t (reference :43-49)
 ncclSum, ncclProd, ncclMax, ncclMin, ncclAvg = 0, 1, 2, 3, 4
@@ -42,7 +44,8 @@ MNCCL_FIRST_USER_OP = 5
 # mncclAlgo_t (mncclAlgoDirect = 1 was removed in mncclVersion 400)
 ALGO_AUTO, ALGO_RING, ALGO_READ, ALGO_ONESHOT, ALGO_READ_GRID = -1, 0, 2, 3, 4
 
-DTYPE_SIZE = {ncclInt32: 4, ncclFloat16: 2, ncclFloat: 4, ncclDouble: 8, ncclBfloat16: 2}
+DTYPE_SIZE = {ncclInt32: 4, ncclFloat16: 2, ncclFloat: 4, ncclDouble: 8, ncclBfloat16: 2,
+              ncclFloat8e4m3: 1, ncclFloat8e5m2: 1}
 
 
 class CommInfo(ctypes.Structure):
@@ -100,6 +103,7 @@ SIGNATURES = {
     "ncclRedOpCreatePreMulSum": (_I, [ctypes.POINTER(_I), _VP, _I, _I, _VP]),
     "ncclRedOpDestroy": (_I, [_I, _VP]),
     "mncclLocalReduce": (_I, [_VP, _VP, _VP, _SZ, _I, _I, _VP]),
+    "mncclDataTypeSize": (_I, [_I, ctypes.POINTER(_SZ)]),
     "mncclCommGetAsyncError": (_I, [_VP, ctypes.POINTER(_I)]),
     "mncclCommGetInfo": (_I, [_VP, ctypes.POINTER(CommInfo)]),
     "mncclCommGetInfoV": (_I, [_VP, _VP, _SZ]),
@@ -145,11 +149,46 @@ def check(code, what="mini-nccl"):
     return code
 
 
+def _fp8_encode(value, ebits, mbits, bias, has_inf):
+    """One float as an OCP fp8 byte by the library's rule (mini_nccl_ext.h): nearest even onto the
+    finite grid, subnormals included; a finite value beyond the largest finite one saturates to it;
+    NaN stays NaN, +-inf stays +-inf where the format has it (e5m2) and is NaN where it has not."""
+    import math
+    from fractions import Fraction
+    sign = 0x80 if math.copysign(1.0, value) < 0 else 0
+    nan = 0x7F  # (a NaN of either format)
+    if math.isnan(value):
+        return sign | nan
+    top = (1 << ebits) - 1                      # the largest exponent field
+    max_e = top - 1 if has_inf else top         # ... that holds finite values
+    max_m = (1 << mbits) - 1 if has_inf else (1 << mbits) - 2  # e4m3fn: the all-ones code is NaN
+    max_code = (max_e << mbits) | max_m
+    if math.isinf(value):
+        return sign | ((top << mbits) if has_inf else nan)
+    a = Fraction(abs(value))
+    if a == 0:
+        return sign
+    # the grid's step at a: 2^(e - bias - mbits) with e the biased exponent, at least 1 (subnormals)
+    e = max(1, min(max_e, (a.numerator.bit_length() - a.denominator.bit_length()) + bias + 1))
+    while e > 1 and a < Fraction(2) ** (e - bias):
+        e -= 1
+    while e < max_e and a >= Fraction(2) ** (e + 1 - bias):
+        e += 1
+    q = a / Fraction(2) ** (e - bias - mbits)    # in units of the step: [2^mbits, 2^(mbits+1)) if normal
+    k = q.numerator // q.denominator
+    r = q - k
+    if r > Fraction(1, 2) or (r == Fraction(1, 2) and k & 1):
+        k += 1
+    code = ((e - 1) << mbits) + k                # (a carry out of the mantissa moves into the exponent)
+    return sign | min(code, max_code)
+
+
 def scalar_bytes(scalar, dtype):
     """One value of `dtype` as a ctypes buffer (what ncclRedOpCreatePreMulSum reads through its
     `scalar` pointer).  A number is converted to the datatype, rounded to nearest even.  For
-    ncclBfloat16 alone an integer (a Python int or a numpy integer such as numpy.uint16) is taken as
-    the 16 bits themselves, since numpy has no bfloat16 scalar to pass."""
+    ncclBfloat16 and the fp8 types an integer (a Python int or a numpy integer such as numpy.uint16)
+    is taken as the 16 / 8 bits themselves, since numpy has no such scalar to pass; an fp8 float is
+    rounded by the library's own rule (saturating)."""
     import numbers
     import struct
     if dtype == ncclFloat:
@@ -166,6 +205,13 @@ def scalar_bytes(scalar, dtype):
         else:
             u = struct.unpack("<I", struct.pack("<f", float(scalar)))[0]
             raw = struct.pack("<H", ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) & 0xFFFF)
+    elif dtype in (ncclFloat8e4m3, ncclFloat8e5m2):
+        if isinstance(scalar, numbers.Integral):
+            raw = struct.pack("<B", int(scalar) & 0xFF)
+        elif dtype == ncclFloat8e4m3:
+            raw = struct.pack("<B", _fp8_encode(float(scalar), 4, 3, 7, False))
+        else:
+            raw = struct.pack("<B", _fp8_encode(float(scalar), 5, 2, 15, True))
     else:
         raw = bytes(8)  # an unsupported datatype: the library refuses it before it reads the scalar
     return ctypes.create_string_buffer(raw, 8)
@@ -356,3 +402,10 @@ class group:
 def local_reduce(out_ptr, local_ptr, incoming_ptr, count, dtype=ncclFloat, op=ncclSum, stream=0):
     """out[i] = op(local[i], incoming[i]) on the GPU (the scatter-reduce element-wise kernel)."""
     return load().mncclLocalReduce(out_ptr, local_ptr, incoming_ptr, count, dtype, op, stream)
+
+
+def data_type_size(dtype):
+    """mncclDataTypeSize: (ncclResult_t, element size in bytes or None)."""
+    n = ctypes.c_size_t(0)
+    rc = load().mncclDataTypeSize(int(dtype), ctypes.byref(n))
+    return rc, (n.value if rc == ncclSuccess else None)
