@@ -572,6 +572,58 @@ ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm);
 #define ncclFloat8e5m2 ((ncclDataType_t)11)
 ncclResult_t mncclDataTypeSize(ncclDataType_t datatype, size_t* size);
 
+/* Sub-communicators (NCCL's ncclCommSplit: name, argument order and meaning; detected by the symbol,
+ * MNCCL_VERSION stays 600 and mncclCommInfo_t does not grow).  COLLECTIVE over every rank of `comm`.
+ * Ranks passing the same color >= 0 form one new communicator; within it the ranks are ordered by
+ * `key`, ascending -- keys may be negative or equal, and ties are broken by the rank in `comm`.  A
+ * rank passing NCCL_SPLIT_NOCOLOR takes part in the exchange and gets *newcomm = NULL with
+ * ncclSuccess.  A group of one is a valid one-rank communicator, and a child may be split again.  So
+ * tensor- / data- / pipeline-parallel groups come from one ncclCommInitRank: no second port, no
+ * MINI_NCCL_PORT changed between two calls, no rank numbering worked out by the caller.
+ *
+ * Checks, in this order (no exception crosses the boundary):
+ *  1. a NULL comm or a NULL newcomm: ncclInvalidArgument;
+ *  2. a group is open on this thread: ncclInvalidUsage, the group stays open and clean;
+ *  3. a non-NULL config: ncclInvalidUsage (ncclConfig_t is opaque here: the child takes its parent's
+ *     configuration);
+ *  4. color < 0 other than NCCL_SPLIT_NOCOLOR: ncclInvalidArgument;
+ *  5. with the communicator: its sticky error is returned;
+ *  6. the exchange: any failure -- a peer gone, the bootstrap timeout
+ *     MINI_NCCL_BOOTSTRAP_TIMEOUT_MS, a child that cannot be built -- is ncclSystemError on every rank
+ *     that sees it.
+ * Checks 1 - 4 happen before the communicator is read or any peer is contacted and leave *newcomm
+ * untouched; as in NCCL their arguments are the caller's to keep valid on EVERY rank (a rank refused
+ * there does not join the exchange the others wait in).  In 5 and 6 *newcomm is NULL on return and
+ * the parent stays usable.
+ *
+ * The call first waits on the host for the parent's previous call, as mncclCommRegister does: no
+ * collective of the parent is in flight while sockets are exchanged.  The exchange is two rounds
+ * over the parent's bootstrap connections -- every rank's (color, key), then the ephemeral loopback
+ * port each group's new rank 0 already listens on -- so no well-known port is used.
+ *
+ * A child is a full, independent communicator: its own scratch and mailbox, counters, control page,
+ * read-schedule board, registered windows, user-created ops, sticky error, last_algo and bootstrap
+ * connections (led by its new rank 0).  From the parent it takes the configuration BY COPY -- the
+ * environment is not read again, and its schedule starts at the configured MINI_NCCL_ALGO, not at a
+ * later mncclCommSetAlgo of the parent -- and the parent's GPU (the call makes that device current
+ * while it builds the child and restores the caller's).  It does NOT inherit registered windows or
+ * ncclRedOpCreatePreMulSum handles: a parent's handle used on the child is an unknown handle,
+ * ncclInternalError.  Every collective, ncclSend / ncclRecv, windows and ops work on a child as on
+ * any communicator.  Parent and children may be destroyed in any order (each ncclCommDestroy is
+ * collective over that communicator's own ranks); a child keeps working after its parent is gone.
+ *
+ * Residency: sibling groups run their kernels on the same GPUs at the same time, so a child's
+ * mncclCommInfo_t.run_pipelines is capped for the whole family -- by the ranks its parent (and,
+ * through it, the first ancestor) counted on the most crowded GPU -- and never exceeds its
+ * parent's; ranks_on_device stays the child's own count.
+ *
+ * Concurrency is NCCL's rule: calls on two communicators of one process -- a parent and a child, or
+ * two children -- may overlap only if EVERY rank issues them in the same order.  Overlapping calls on
+ * a parent and its child are also not covered by the residency cap above. */
+#define NCCL_SPLIT_NOCOLOR (-1)
+typedef struct ncclConfig ncclConfig_t; /* opaque; only NULL is accepted */
+ncclResult_t ncclCommSplit(ncclComm_t comm, int color, int key, ncclComm_t* newcomm, ncclConfig_t* config);
+
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream);
 

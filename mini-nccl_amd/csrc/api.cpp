@@ -454,6 +454,24 @@ ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm) {
   return reinterpret_cast<Comm*>(comm)->redop_destroy((int)op);
 }
 
+// Sub-communicators (mini_nccl_ext.h): the checks in the header's order.  The first four read neither
+// the communicator nor the network and leave *newcomm as it was; a refusal inside an open group does
+// not poison the group.
+ncclResult_t ncclCommSplit(ncclComm_t comm, int color, int key, ncclComm_t* newcomm, ncclConfig_t* config) {
+  if (!comm || !newcomm) return ncclInvalidArgument;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
+  if (config) {
+    fprintf(stderr, "[Mini-NCCL] ncclCommSplit: only a NULL config is supported (the child takes its parent's)\n");
+    return ncclInvalidUsage;
+  }
+  if (color < 0 && color != NCCL_SPLIT_NOCOLOR) return ncclInvalidArgument;
+  RoctxRange range("mini_ncclCommSplit");
+  Comm* child = nullptr;
+  const ncclResult_t rc = reinterpret_cast<Comm*>(comm)->split(color, key, &child);  // never throws
+  *newcomm = reinterpret_cast<ncclComm_t>(child);
+  return rc;
+}
+
 ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming, size_t count,
                               ncclDataType_t datatype, ncclRedOp_t op, hipStream_t stream) {
   if (!out || !local || !incoming) return ncclInvalidArgument;

@@ -114,6 +114,7 @@ constexpr int kCtlDirectSends = 64;
 
 Comm::Comm(int nranks, int rank, const std::string& ip) : rank_(rank), nranks_(nranks) {
   cfg_ = Config::from_env();
+  board_port_ = cfg_.port;
   // auto: the read schedule (same bits; no scratch; each call falls back to the ring when some
   // rank's buffers cannot be shared)
   set_algo(cfg_.algo);
@@ -128,6 +129,22 @@ Comm::Comm(int nranks, int rank, const std::string& ip) : rank_(rank), nranks_(n
   try {
     setup_device_resources();
     boot_.connect(rank, nranks, ip, cfg_.port, cfg_.bootstrap_timeout_ms / 1000.0);
+    exchange_and_map();
+  } catch (...) {
+    release();
+    throw;
+  }
+}
+
+Comm::Comm(Bootstrap&& boot, const Config& cfg, int board_port, const Family& fam)
+    : rank_(boot.rank()), nranks_(boot.nranks()), cfg_(cfg), fam_(fam), board_port_(board_port), boot_(std::move(boot)) {
+  // the configured schedule, not a later mncclCommSetAlgo of the parent
+  set_algo(cfg_.algo);
+  geo_ = pipeline_geometry(nranks_, cfg_.channels, cfg_.threads, cfg_.window_size, cfg_.signal_batch, cfg_.slots,
+                           cfg_.slice_size, cfg_.scratch_cap);
+  hip_check(hipGetDevice(&device_), "hipGetDevice");
+  try {
+    setup_device_resources();
     exchange_and_map();
   } catch (...) {
     release();
@@ -177,7 +194,13 @@ void Comm::setup_device_resources() {
 void Comm::exchange_and_map() {
   peer_scratch_.assign((size_t)nranks_, nullptr);
   peer_mbox_.assign((size_t)nranks_, nullptr);
-  if (nranks_ == 1) return;
+  if (nranks_ == 1) {
+    // a child of one rank launches no persistent kernel; it still hands the family's values on
+    most_ = fam_.most;
+    budget_div_ = fam_.on_device;
+    if (fam_.run_pipes > 0) run_pipes_ = std::min(wave_channels(), fam_.run_pipes);
+    return;
+  }
   PeerInfo me;
   memset(&me, 0, sizeof me);
   me.magic = kInfoMagic;
@@ -246,9 +269,15 @@ void Comm::exchange_and_map() {
       for (int p = 0; p < nranks_; ++p) same += all[(size_t)p].pci == all[(size_t)q].pci;
       most = std::max(most, same);
     }
+    // A child (split): its sibling groups' kernels share these GPUs with its own, so it counts the
+    // ranks its parent counted -- and through the parent the root ancestor's -- and never launches
+    // more pipelines than its parent (fam_ came over the parent's star: the same on every rank)
+    most = std::max(most, fam_.most);
+    most_ = most;
     run_pipes_ = resident_pipes(wave_channels(), geo_.waves, cus, most, kMinWavesPerSimd);
+    if (fam_.run_pipes > 0) run_pipes_ = std::min(run_pipes_, fam_.run_pipes);
     p2p_pipes_ = mnccl::p2p_pipes(nranks_, wave_channels(), cus, most, kMinWavesPerSimd);
-    if (run_pipes_ < wave_channels() && rank_ == 0)
+    if (run_pipes_ < wave_channels() && rank_ == 0 && fam_.run_pipes == 0)
       fprintf(stderr, "[Mini-NCCL] %d rank(s) share a GPU of %d CUs: calls launch at most %d of the communicator's %d "
               "pipelines, so every rank's waves stay resident together\n", most, cus, run_pipes_, wave_channels());
   }
@@ -279,7 +308,8 @@ void Comm::exchange_and_map() {
       if (all[(size_t)q].pci == me.pci) first_here = false;
     // 8 x 4 queues time-sliced every hand-off (profiles/r2_coloc8_*); 2 x 4 did as soon as each
     // process made one more stream (profiles/r5_bench_size_order.txt), 2 per process never did
-    if (procs.size() > 1 && queues > 2 && first_here)
+    // (a child's parent has said it already)
+    if (procs.size() > 1 && queues > 2 && first_here && fam_.run_pipes == 0)
       fprintf(stderr,
               "[Mini-NCCL] warning: %zu rank processes share GPU %d with up to %d hardware queues each; the "
               "all-reduce needs every rank's kernel resident at once -- with more than 2 queues per process "
@@ -290,7 +320,9 @@ void Comm::exchange_and_map() {
   // the bytes of freed same-GPU peer allocations this process may keep mapped (ipcreg.h
   // close_import): MINI_NCCL_RETIRED_MB, by default 1/8 of this GPU's memory shared by the ranks on
   // it (36 GB on MI355X between them: each co-located process pins memory of the same GPU)
-  if (ranks_on_device_ > 1) {
+  // (a child divides by its family's count: its siblings' processes pin memory of this GPU too)
+  budget_div_ = std::max(ranks_on_device_, fam_.on_device);
+  if (budget_div_ > 1) {
     uint64_t budget = (uint64_t)cfg_.retired_mb << 20;
     if (cfg_.retired_mb < 0) {
       size_t fr = 0, total = 0;
@@ -298,7 +330,7 @@ void Comm::exchange_and_map() {
         (void)hipGetLastError();
         total = (size_t)288 << 30;
       }
-      budget = (uint64_t)total / 8 / (uint64_t)ranks_on_device_;
+      budget = (uint64_t)total / 8 / (uint64_t)budget_div_;
     }
     ipc::set_retired_budget(budget);
   }
@@ -339,7 +371,7 @@ void Comm::exchange_and_map() {
   // memory is)
   std::vector<uint64_t> nonces((size_t)nranks_);
   for (int q = 0; q < nranks_; ++q) nonces[(size_t)q] = all[(size_t)q].nonce;
-  pbuf_.init(boot_, rank_, nranks_, nonces, cfg_.port);
+  pbuf_.init(boot_, rank_, nranks_, nonces, board_port_);
   // the peers in other processes, for the import lifecycle (ipcreg.h comm_opened / comm_closed)
   for (int q = 0; q < nranks_; ++q)
     if (all[(size_t)q].nonce != me.nonce &&
@@ -1496,6 +1528,41 @@ ncclResult_t Comm::deregister_window(void* handle) {
       return ncclSuccess;
     }
   return ncclInvalidArgument;
+}
+
+ncclResult_t Comm::split(int color, int key, Comm** child) {
+  *child = nullptr;
+  if (sticky_ != ncclSuccess) return sticky_;
+  if (h_ctl_ && check_status() != ncclSuccess) return sticky_;
+  int cur_dev = -1;
+  if (hipGetDevice(&cur_dev) != hipSuccess) {
+    (void)hipGetLastError();
+    cur_dev = -1;
+  }
+  ncclResult_t rc = ncclSuccess;
+  try {
+    if (cur_dev != device_) hip_check(hipSetDevice(device_), "hipSetDevice");
+    wait_previous_call();  // no collective of this communicator is in flight while sockets are exchanged
+    Bootstrap star;
+    int port = 0;
+    const SplitSlot slot =
+        split_bootstrap(boot_, color, key, cfg_.bootstrap_timeout_ms / 1000.0, &star, &port);
+    if (slot.size > 0) {
+      Family fam;
+      fam.most = most_;
+      fam.on_device = budget_div_;
+      fam.run_pipes = run_pipes();
+      *child = new Comm(std::move(star), cfg_, port, fam);
+    }
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: ncclCommSplit failed: %s\n", rank_, e.what());
+    rc = ncclSystemError;
+  } catch (...) {
+    rc = ncclSystemError;
+  }
+  if (cur_dev >= 0 && cur_dev != device_) (void)hipSetDevice(cur_dev);
+  (void)hipGetLastError();
+  return rc;
 }
 
 void Comm::abort_peers() {

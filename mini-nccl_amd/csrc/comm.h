@@ -23,6 +23,19 @@ class Comm {
  public:
   // Throws on failure; the API layer maps exceptions to ncclSystemError (api.cpp:62-65).
   Comm(int nranks, int rank, const std::string& ip);
+  // What a communicator made by split() takes from its parent besides the Config: its sibling groups
+  // run their persistent kernels on the same GPUs at the same time, so the residency cap
+  // (exchange_and_map) is the family's, not the child's alone.  most: ranks on the most crowded GPU;
+  // on_device: the divisor of the retired-import budget; run_pipes: the parent's run_pipes(), which
+  // the child's never exceeds (0: no parent).  A child hands its own values on, so the root
+  // ancestor's reach every descendant.
+  struct Family {
+    int most = 1, on_device = 1, run_pipes = 0;
+  };
+  // A child (ncclCommSplit): `boot` is its connected star (bootstrap.h split_bootstrap), `cfg` the
+  // parent's Config by copy -- the environment is not read again -- and `board_port` its leader's
+  // ephemeral port, which names the read schedule's board (peerbuf.cpp).  On the current device.
+  Comm(Bootstrap&& boot, const Config& cfg, int board_port, const Family& fam);
   ~Comm();
   Comm(const Comm&) = delete;
   Comm& operator=(const Comm&) = delete;
@@ -74,6 +87,15 @@ class Comm {
   ncclResult_t redop_destroy(int op);
   bool redop_find(int op, int* dtype, uint64_t* scalar) const;
   ncclResult_t sticky_error() const { return sticky_; }
+
+  // ncclCommSplit (mini_nccl_ext.h), after api.cpp's argument checks; collective over this
+  // communicator's ranks.  Waits for the previous call, then two rounds over the bootstrap star
+  // (split_bootstrap) and the child's construction on this communicator's device (the caller's is
+  // restored).  *child: the new communicator, or nullptr for kSplitNoColor (ncclSuccess) and on any
+  // failure: this communicator's sticky error, else ncclSystemError; this communicator stays usable.
+  // The child is independent: own scratch, mailbox, counters, board, windows, user ops and star; it
+  // may outlive this communicator.  Never throws.
+  ncclResult_t split(int color, int key, Comm** child);
 
   // The all-to-all (RCCL's ncclAllToAll; `count` elements per block, n blocks in both buffers):
   // block q of this rank's send becomes block `rank` of rank q's recv, byte for byte.  The schedule
@@ -237,6 +259,9 @@ class Comm {
 
   int rank_, nranks_, device_ = 0;
   Config cfg_;
+  Family fam_;                   // a child's inheritance (split); a root communicator's defaults
+  int most_ = 1, budget_div_ = 1;  // what this communicator's own children inherit (exchange_and_map)
+  int board_port_ = 0;           // names the read schedule's board: MINI_NCCL_PORT, a child's leader's port
   Geometry geo_;
   int algo_ = 0;                 // 0 ring, 2 read (its calls fall back to the ring when some rank's
                                  // buffers cannot be shared), 3 one-shot (larger calls: as auto)

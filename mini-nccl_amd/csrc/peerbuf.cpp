@@ -128,7 +128,11 @@ void PeerBuffers::init(Bootstrap& boot, int rank, int nranks, const std::vector<
   memset(name, 0, sizeof name);
   int fd = -1;
   if (rank == 0) {
-    snprintf(name, sizeof name, "/mnccl-%d-%d-%016llx", (int)getpid(), port, (unsigned long long)nonces[0]);
+    // (one process may lead several live communicators -- ncclCommSplit's children, whose `port` is
+    // their leader's ephemeral one, which the system may hand out again -- so a serial number too)
+    static std::atomic<unsigned> serial{0};
+    snprintf(name, sizeof name, "/mnccl-%d-%d-%016llx-%u", (int)getpid(), port, (unsigned long long)nonces[0],
+             serial.fetch_add(1));
     fd = shm_open(name, O_CREAT | O_EXCL | O_RDWR, 0600);
     if (fd >= 0 && ftruncate(fd, (off_t)board_bytes_) != 0) {
       close(fd);

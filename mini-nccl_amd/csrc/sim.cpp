@@ -1233,6 +1233,7 @@ int mnccl_sim_signed_read(const float* const* send, float* const* recv, int n, u
 
 #include <stdexcept>
 #include <string>
+#include <thread>
 
 #include <unistd.h>
 
@@ -1240,6 +1241,7 @@ int mnccl_sim_signed_read(const float* const* send, float* const* recv, int n, u
 #include "config.h"
 #include "kernels.h"
 #include "peerbuf.h"
+#include "split.h"
 
 extern "C" {
 
@@ -1370,6 +1372,82 @@ int mnccl_config_describe(char* buf, int len) {
     snprintf(buf, (size_t)len, "%s", e.what());
     return -1;
   }
+}
+
+// ncclCommSplit's plan (csrc/split.h split_plan): out[3 * r] = {group size, new rank, leader's parent
+// rank} of rank r, {0, -1, -1} for a rank in no group.
+void mnccl_split_plan(int n, const int* colors, const int* keys, int* out) {
+  std::vector<mnccl::SplitSlot> plan((size_t)(n > 0 ? n : 0));
+  mnccl::split_plan(n, colors, keys, plan.data());
+  for (int r = 0; r < n; ++r) {
+    out[3 * r] = plan[(size_t)r].size;
+    out[3 * r + 1] = plan[(size_t)r].rank;
+    out[3 * r + 2] = plan[(size_t)r].leader;
+  }
+}
+
+}  // extern "C"
+
+// One rank of mnccl_bootstrap_split_selftest: a split of `parent` by (color, key), then on the child
+// star one all-gather of the members' parent ranks -- which must come back in the plan's order --
+// and one barrier.  0, or -2 wrong slot, -3 wrong gathered order, -4 a socket where none is due.
+static int split_round(mnccl::Bootstrap& parent, int n, const int* colors, const int* keys, double timeout_s) {
+  const int me = parent.rank();
+  std::vector<mnccl::SplitSlot> plan((size_t)n);
+  mnccl::split_plan(n, colors, keys, plan.data());
+  mnccl::Bootstrap child;
+  int port = -1;
+  const mnccl::SplitSlot s = mnccl::split_bootstrap(parent, colors[me], keys[me], timeout_s, &child, &port);
+  const mnccl::SplitSlot want = plan[(size_t)me];
+  if (s.size != want.size || s.rank != want.rank || s.leader != want.leader) return -2;
+  if (s.size == 0) return child.nranks() == 0 && port == 0 ? 0 : -4;
+  if (child.rank() != s.rank || child.nranks() != s.size || (s.size == 1) != (port == 0)) return -4;
+  const int32_t mine = me;
+  std::vector<int32_t> all((size_t)s.size, -1);
+  child.allgather(&mine, all.data(), sizeof mine);
+  child.barrier();
+  for (int q = 0; q < n; ++q)
+    if (plan[(size_t)q].size > 0 && plan[(size_t)q].leader == s.leader && all[(size_t)plan[(size_t)q].rank] != q) return -3;
+  return 0;
+}
+
+extern "C" {
+
+// The two-round bootstrap of ncclCommSplit (csrc/bootstrap.h split_bootstrap) with n ranks as threads
+// of this process over 127.0.0.1:port: the parent star connects, splits by (colors, keys), every
+// child star runs split_round's all-gather and barrier, then the parent star all-gathers again (it
+// still works), splits a second time with the keys negated (every group in reverse order), and runs
+// a last barrier.  0 on success, -1 an exception, -5 the parent's all-gather came back wrong, or the
+// first failing rank's split_round code.
+int mnccl_bootstrap_split_selftest(int n, int port, const int* colors, const int* keys, int timeout_ms) {
+  if (n < 1 || n > 64) return -1;
+  const double timeout_s = timeout_ms / 1000.0;
+  std::vector<int> rcs((size_t)n, 0), neg((size_t)n);
+  for (int r = 0; r < n; ++r) neg[(size_t)r] = -keys[r];
+  auto rank_main = [&](int r) {
+    try {
+      mnccl::Bootstrap parent;
+      parent.connect(r, n, "127.0.0.1", port, timeout_s);
+      int rc = split_round(parent, n, colors, keys, timeout_s);
+      const int32_t mine = 100 + r;
+      std::vector<int32_t> all((size_t)n, -1);
+      parent.allgather(&mine, all.data(), sizeof mine);
+      for (int q = 0; q < n && rc == 0; ++q)
+        if (all[(size_t)q] != 100 + q) rc = -5;
+      if (rc == 0) rc = split_round(parent, n, colors, neg.data(), timeout_s);
+      parent.barrier();
+      rcs[(size_t)r] = rc;
+    } catch (const std::exception& e) {
+      fprintf(stderr, "bootstrap split selftest rank %d: %s\n", r, e.what());
+      rcs[(size_t)r] = -1;
+    }
+  };
+  std::vector<std::thread> ts;
+  for (int r = 0; r < n; ++r) ts.emplace_back(rank_main, r);
+  for (auto& t : ts) t.join();
+  for (int rc : rcs)
+    if (rc != 0) return rc;
+  return 0;
 }
 
 }  // extern "C"

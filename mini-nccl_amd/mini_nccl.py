@@ -41,6 +41,9 @@ ncclSum, ncclProd, ncclMax, ncclMin, ncclAvg = 0, 1, 2, 3, 4
 ncclScalarDevice, ncclScalarHostImmediate = 0, 1
 MNCCL_FIRST_USER_OP = 5
 
+# ncclCommSplit: the color of a rank that joins no new communicator
+NCCL_SPLIT_NOCOLOR = -1
+
 # mncclAlgo_t (mncclAlgoDirect = 1 was removed in mncclVersion 400)
 ALGO_AUTO, ALGO_RING, ALGO_READ, ALGO_ONESHOT, ALGO_READ_GRID = -1, 0, 2, 3, 4
 
@@ -102,6 +105,7 @@ SIGNATURES = {
     "ncclGroupEnd": (_I, []),
     "ncclRedOpCreatePreMulSum": (_I, [ctypes.POINTER(_I), _VP, _I, _I, _VP]),
     "ncclRedOpDestroy": (_I, [_I, _VP]),
+    "ncclCommSplit": (_I, [_VP, _I, _I, ctypes.POINTER(_VP), _VP]),
     "mncclLocalReduce": (_I, [_VP, _VP, _VP, _SZ, _I, _I, _VP]),
     "mncclDataTypeSize": (_I, [_I, ctypes.POINTER(_SZ)]),
     "mncclCommGetAsyncError": (_I, [_VP, ctypes.POINTER(_I)]),
@@ -225,6 +229,28 @@ class Comm:
         self.handle = ctypes.c_void_p()
         check(lib.ncclCommInitRank(ctypes.byref(self.handle), nranks, rank, ip.encode() if ip else None),
               "ncclCommInitRank")
+
+    @classmethod
+    def _adopt(cls, handle):
+        c = cls.__new__(cls)
+        c.handle = handle
+        return c
+
+    def split_rc(self, color, key=0):
+        """ncclCommSplit's result code (does not raise) and the new Comm, or None where the library
+        returned no communicator (NCCL_SPLIT_NOCOLOR, or a failure)."""
+        h = ctypes.c_void_p()
+        rc = load().ncclCommSplit(self.handle, int(color), int(key), ctypes.byref(h), None)
+        return rc, (Comm._adopt(h) if rc == ncclSuccess and h else None)
+
+    def split(self, color, key=0):
+        """ncclCommSplit (collective over this communicator's ranks): the ranks passing the same
+        color >= 0 form a new communicator, ordered by key (ties: by the rank here).  Returns the new
+        Comm, or None for NCCL_SPLIT_NOCOLOR.  The child is independent of this communicator and is
+        destroyed on its own."""
+        rc, child = self.split_rc(color, key)
+        check(rc, "ncclCommSplit")
+        return child
 
     def all_reduce(self, send_ptr, recv_ptr, count, dtype=ncclFloat, op=ncclSum, stream=0):
         """Returns the ncclResult_t (does not raise) -- the reference's calling convention."""
