@@ -38,6 +38,15 @@
  *                        (expert-parallel dispatch / combine: every rank sends every peer a different
  *                        number of tokens, possibly none).
  *
+ * and the all-reduce's halves with per-rank counts, which neither NCCL nor RCCL has (callers there
+ * compose them from broadcasts / reduces inside one group, which this library does not take), under
+ * the library's prefix and in MPI's argument order (data-parallel attention in front of
+ * expert-parallel MLPs, FSDP-style sharding of a dimension the rank count does not divide):
+ *
+ *   mncclAllGatherv      every rank's recv gets rank q's send at elements [rdispls[q], + recvcounts[q]).
+ *   mncclReduceScatterv  rank r's recv = the reduction over all ranks of elements [sdispls[r],
+ *                        + sendcounts[r]) of their send, in ncclReduceScatter's association.
+ *
  * and RCCL's rooted data movers (torch.distributed.gather / scatter, metrics or KV blocks collected
  * on one rank, shards dealt out of one rank):
  *
@@ -90,7 +99,9 @@ extern "C" {
    ncclRedOpDestroy were added the same way; still 600: ncclGather and ncclScatter were added the
    same way (detected by symbol); still 600: ncclSend / ncclRecv push straight into a recvbuff that
    lies in a registered window (no new symbol; mncclCommInfo_t grew, same prefix: p2p_direct_recvs,
-   p2p_direct_sends -- mncclCommGetInfoV writes them to a caller whose struct has room) */
+   p2p_direct_sends -- mncclCommGetInfoV writes them to a caller whose struct has room); still 600:
+   mncclAllGatherv and mncclReduceScatterv were added the same way (detected by symbol;
+   mncclCommInfo_t did not grow) */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -384,6 +395,77 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
                            const size_t recvcounts[], const size_t rdispls[], ncclDataType_t datatype, ncclComm_t comm,
                            hipStream_t stream);
 
+/* The all-reduce's halves with per-rank counts.  Neither NCCL nor RCCL has them, so they carry the
+ * library's prefix and MPI's argument order (MPI_Allgatherv / MPI_Reduce_scatter with displacements).
+ * Counts and displacements are in elements; the two arrays are host arrays of nranks entries, read
+ * before the call returns (a captured call bakes them into the graph).  Each call has an ARRAY side
+ * with nranks blocks (mncclAllGatherv's recv, mncclReduceScatterv's send), block q at elements
+ * [displs[q], displs[q] + counts[q]), and a SCALAR side, this rank's one block.
+ *
+ * mncclAllGatherv.  Rank q's `sendcount` elements end up at elements [rdispls[q], rdispls[q] +
+ * recvcounts[q]) of every rank's recvbuff, byte for byte.  No arithmetic: any datatype ncclAllGather
+ * takes, the fp8 types included, moved by element size.  Bytes of recvbuff outside every block are
+ * never written.  In place: sendbuff == recvbuff + rdispls[rank] elements.
+ *
+ * mncclReduceScatterv.  Every rank's sendbuff holds block q at [sdispls[q], sdispls[q] +
+ * sendcounts[q]); rank r's recvbuff gets the reduction of block r over all ranks in the all-reduce's
+ * association for chunk r: acc = x_r, then acc = op(x_q, acc) for q = r+1 .. r-1 (mod nranks).  With
+ * equal counts and contiguous displacements the result is ncclReduceScatter's, bit for bit, on every
+ * schedule.  Datatypes and ops as ncclReduceScatter: the four built-in ops and
+ * ncclRedOpCreatePreMulSum handles; the fp8 types, re-encoded after every step; ncclAvg and the
+ * integer types other than ncclInt32 are ncclInternalError.  In place: recvbuff == sendbuff +
+ * sdispls[rank] elements.
+ *
+ * Both.  The arrays must be IDENTICAL on every rank, and the scalar count must equal the array's
+ * entry for `rank`: one byte offset then serves every peer's buffer.
+ *
+ * Checks, in this order (no exception crosses the boundary):
+ *  1. a NULL comm or a NULL array: ncclInvalidArgument;
+ *  2. a group open on this thread: ncclInvalidUsage, the group stays open and clean;
+ *  3. an unsupported datatype or op: ncclInternalError, before the communicator is read (a user-op
+ *     handle is looked up in the communicator afterwards, as in ncclReduceScatter);
+ *  4. with the communicator: the sticky error first; then, each ncclInvalidArgument with nothing
+ *     launched or negotiated and the communicator still usable: the scalar count differs from the
+ *     array's entry for `rank`; a NULL data buffer on a side that has a non-zero count (a rank whose
+ *     block is empty may pass NULL for its scalar side; both may be NULL when every count is 0); a
+ *     displ + count or a byte size that overflows size_t; two non-empty blocks of the array side that
+ *     overlap -- on BOTH calls: an in-place mncclReduceScatterv writes block `rank` of a buffer the
+ *     peers are reading other blocks of; the scalar-side buffer overlapping any non-empty block
+ *     without being the in-place form;
+ *  5. after the per-call rendezvous -- every rank sees every rank's arrays -- ranks whose arrays
+ *     differ in any entry: ncclInvalidUsage on every rank alike, nothing launched, the communicator
+ *     still usable; the same when the ranks differ in the collective, the datatype, the op, a
+ *     pre-multiplied sum's scalar bits or the schedule choice (mncclCommSetAlgo);
+ *  6. every count 0 on every rank: ncclSuccess, nothing launched.  A rank whose own count is 0 still
+ *     takes part in the rendezvous and the protocol;
+ *  7. nranks == 1: one device copy when the pointers differ; for a pre-multiplied sum the scale
+ *     kernel, as ncclReduceScatter at one rank.
+ * Blocking mode, stream ordering, sticky errors and the watchdog as ncclReduceScatter / ncclAllGather.
+ *
+ * Schedules.  Where ncclAllToAllv would run the read schedule -- device buffers every rank can map,
+ * a topology that allows read -- two persistent kernels in ncclReduceScatter's / ncclAllGather's
+ * protocol whose geometry follows the LARGEST block, M = max(counts) * element size: rank r's slices
+ * start at byte displs[r] * element size of the array-side buffers and are clamped to its own block,
+ * so a rank with a short or empty block moves only what it has; no padding crosses a link and
+ * nothing is packed.  The gather loads each slice of sendbuff once and stores it into its own and
+ * every peer's recvbuff.  A rank takes the 16-byte path when every rank's buffers are dword-aligned
+ * and its own block's byte offset and byte length are multiples of 4, the element path otherwise;
+ * ranks of one call may differ in that, the bits do not (mncclCommInfo_t.last_algo: mncclAlgoRead).
+ * Otherwise -- a forced ring, a topology that refuses read, host buffers (pinned or pageable) -- the
+ * ring's halves on blocks PADDED to Mpad, M rounded up to 16 bytes, through a device stage of
+ * nranks * Mpad bytes per communicator: the gather packs its block, runs the ring all-gather and
+ * unpacks nranks blocks; the reduce-scatter packs nranks blocks, runs the ring reduce-scatter and
+ * copies its block out; the padding's results are discarded (last_algo: mncclAlgoRing).  The stage
+ * may have to be allocated, so a call captured into a HIP graph cannot take the fallback: if it would
+ * and any rank's stream is capturing, every rank returns ncclInvalidUsage with nothing launched.  A
+ * captured call on the read schedule replays correctly.  No one-shot, grid or registered-window form
+ * (mncclCommInfo_t.window_calls does not move). */
+ncclResult_t mncclAllGatherv(const void* sendbuff, size_t sendcount, void* recvbuff, const size_t recvcounts[],
+                             const size_t rdispls[], ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
+ncclResult_t mncclReduceScatterv(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                                 size_t recvcount, ncclDataType_t datatype, ncclRedOp_t op, ncclComm_t comm,
+                                 hipStream_t stream);
+
 /* Point to point, NCCL's names and signatures.
  *
  * Data.  The `count` elements of an ncclSend arrive, byte for byte, in the matching ncclRecv on `peer`
@@ -403,7 +485,8 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
  * leaves the communicator usable.  A group may hold several sends to one peer and several recvs from
  * one peer: they run in call order.  At most 64 operations fit in a group (kMaxGroupOps); one more is
  * ncclInvalidUsage.  DEFERRED COLLECTIVES ARE OUT OF SCOPE: ncclAllReduce, ncclReduceScatter,
- * ncclAllGather, ncclBroadcast, ncclReduce, ncclAllToAll, ncclAllToAllv, ncclGather or ncclScatter called while a group is open
+ * ncclAllGather, ncclBroadcast, ncclReduce, ncclAllToAll, ncclAllToAllv, ncclGather, ncclScatter, mncclAllGatherv or
+ * mncclReduceScatterv called while a group is open
  * return ncclInvalidUsage (after their NULL and count == 0 checks) with nothing launched, and the
  * group stays open and clean; with no group open they behave exactly as before.
  *

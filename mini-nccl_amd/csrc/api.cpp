@@ -348,6 +348,55 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
   }
 }
 
+// The halves with per-rank counts (mini_nccl_ext.h): the communicator and the two arrays, the open
+// group, then the datatype and the op; the data buffers may be NULL where the counts are zero, so
+// they are checked with the counts where the communicator's rank and size are known (Comm::vhalf,
+// vhalves.h).
+ncclResult_t mncclAllGatherv(const void* sendbuff, size_t sendcount, void* recvbuff, const size_t recvcounts[],
+                             const size_t rdispls[], ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
+  if (!comm || !recvcounts || !rdispls) return ncclInvalidArgument;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
+  RoctxRange range("mini_ncclAllGatherv");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] AllGatherv Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->all_gather_v(sendbuff, sendcount, recvbuff, recvcounts, rdispls, (int)datatype,
+                                                       stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] AllGatherv Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
+ncclResult_t mncclReduceScatterv(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                                 size_t recvcount, ncclDataType_t datatype, ncclRedOp_t op, ncclComm_t comm,
+                                 hipStream_t stream) {
+  if (!comm || !sendcounts || !sdispls) return ncclInvalidArgument;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
+  RoctxRange range("mini_ncclReduceScatterv");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] ReduceScatterv Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  int kop = 0;
+  uint64_t scalar = 0;
+  const ncclResult_t orc = resolve_op("ReduceScatterv", reinterpret_cast<const Comm*>(comm), datatype, op, &kop, &scalar);
+  if (orc != ncclSuccess) return orc;
+  try {
+    return reinterpret_cast<Comm*>(comm)->reduce_scatter_v(sendbuff, sendcounts, sdispls, recvbuff, recvcount,
+                                                           (int)datatype, kop, stream, scalar);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] ReduceScatterv Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
 // Point to point (mini_nccl_ext.h): the checks in the header's order.  Inside a group a call only
 // records its operation; outside, it is a group of one and launches at once.
 static ncclResult_t p2p_call(bool send, const void* buff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,

@@ -1146,21 +1146,26 @@ ncclResult_t Comm::rendezvous_failed(const std::exception& e, bool peer_gave_up,
   return sticky_;
 }
 
-bool Comm::gather_rows(const VarRow& mine, int dtype, VarRow* rows) {
+bool Comm::gather_rows(const VarRow& mine, int dtype, VarRow* rows, int coll, int op, uint64_t scalar) {
   struct Rec {
     VarRow row;
     int32_t dtype, coll;
+    int32_t op, pad;
+    uint64_t scalar;
   } me;
   memset(&me, 0, sizeof me);
   me.row = mine;
   me.dtype = dtype;
-  me.coll = kCollAllToAllV;
+  me.coll = coll;
+  me.op = op;
+  me.scalar = scalar;
   std::vector<Rec> all((size_t)nranks_);
   boot_.allgather(&me, all.data(), sizeof me);
   bool same = true;
   for (int q = 0; q < nranks_; ++q) {
-    rows[q] = all[(size_t)q].row;
-    same = same && all[(size_t)q].dtype == dtype && all[(size_t)q].coll == kCollAllToAllV;
+    const Rec& c = all[(size_t)q];
+    rows[q] = c.row;
+    same = same && c.dtype == dtype && c.coll == coll && c.op == op && c.scalar == scalar;
   }
   return same;
 }
@@ -1313,6 +1318,167 @@ ncclResult_t Comm::all_to_all_v(const void* send, const size_t* sendcounts, cons
     if (sendcounts[rank_])
       hip_check(hipMemcpyAsync(r0 + rdispls[rank_] * (size_t)esz, s0 + sdispls[rank_] * (size_t)esz,
                                sendcounts[rank_] * (size_t)esz, hipMemcpyDefault, stream), "own block");
+  }
+  return end_call(scope, stream, seq);
+}
+
+// mncclAllGatherv / mncclReduceScatterv.  all_to_all_v's call path with one row of counts and
+// displacements that every rank must pass alike: the caller's local errors first (vhalves.h: nothing
+// launched, nothing negotiated); then every rank's arrays reach every rank -- through the read
+// schedule's rendezvous wherever the board exists, whatever the schedule, else over the bootstrap --
+// and are compared for equality, with the collective, datatype, op, scalar bits and schedule choice.
+// The geometry follows M, the largest block in bytes.  On the read schedule: kernels.hip vhalf_push /
+// vhalf_fold with this rank's base and length, the one-block buffer's pointer shifted by -base as
+// Comm::make_params shifts the uniform halves' by -rank * chunk; the 16-byte path is this rank's own
+// choice (vhalf_vec).  Else the ring's halves on blocks padded to Mpad = M rounded up to 16 bytes, in
+// an n * Mpad stage and the in-place layout: the all-gather packs its own block into chunk `rank`,
+// runs the ring all-gather and unpacks the n blocks; the reduce-scatter packs the n blocks, runs the
+// ring reduce-scatter with Mpad / esz elements and copies its block out of chunk `rank`.  The padding
+// is never initialised: its results are discarded.  The stage may have to be allocated, which a graph
+// capture cannot do: if the decision is the fallback and ANY rank is capturing, every rank returns
+// ncclInvalidUsage.  A rank whose own count is 0 still takes part in the rendezvous and the protocol.
+ncclResult_t Comm::vhalf(int coll, void* array_buf, const size_t* counts, const size_t* displs, void* one_buf,
+                         size_t one_count, int dtype, int op, hipStream_t stream, uint64_t scalar) {
+  if (sticky_ != ncclSuccess) return sticky_;
+  if (check_status() != ncclSuccess) return sticky_;
+  const bool gather = coll == kCollAllGatherV;
+  const char* const name = gather ? "mncclAllGatherv" : "mncclReduceScatterv";
+  const int n = nranks_, esz = dtype_size(dtype);
+  const int local = vhalf_check_local(n, rank_, esz, array_buf, counts, displs, one_buf, one_count);
+  if (local != kVHalfOk) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s: %s\n", rank_, name,
+            local == kVHalfCountMismatch  ? "the scalar count differs from the array's entry for this rank"
+            : local == kVHalfNullBuffer   ? "a NULL buffer with a non-zero count"
+            : local == kVHalfOverflow     ? "a displacement plus count, or a byte size, overflows size_t"
+            : local == kVHalfBlockOverlap ? "two blocks overlap"
+                                          : "the one-block buffer overlaps a block and the call is not in place");
+    return ncclInvalidArgument;
+  }
+  char* const arr = static_cast<char*>(array_buf);
+  char* const one = static_cast<char*>(one_buf);
+  const size_t mine = one_count * (size_t)esz;
+  const size_t base = one_count ? displs[rank_] * (size_t)esz : 0;  // an empty block's displacement is never used
+  if (n == 1) {
+    if (one_count == 0) return ncclSuccess;
+    const CallScope scope = begin_call(stream);
+    const void* s = gather ? one : arr + base;
+    void* r = gather ? arr + base : one;
+    if (op == kPreMulSum && !gather) scale_one_rank(s, r, one_count, dtype, scalar, scope, stream);
+    else if (s != r) hip_check(hipMemcpyAsync(r, s, mine, hipMemcpyDefault, stream), "copy");
+    return end_call(scope, stream, 0);
+  }
+  const CallScope scope = begin_call(stream);
+  auto leave = [&](ncclResult_t rc) {
+    if (scope.cur_dev != device_) hipSetDevice(scope.cur_dev);
+    return rc;
+  };
+  VarRow row, rows[kMaxRanks];
+  memset(&row, 0, sizeof row);
+  for (int q = 0; q < n; ++q) {
+    row.sendcounts[q] = counts[q];
+    row.rdispls[q] = displs[q];
+  }
+  row.flags = (uint32_t)kVarSameRows | (scope.capturing() ? (uint32_t)kVarCapturing : 0u);
+  const uint64_t sbits = op == kPreMulSum ? scalar : 0;
+
+  PeerBuffers::Decision d = PeerBuffers::kFallback;
+  const char* psend[kMaxRanks] = {};
+  const char* precv[kMaxRanks] = {};
+  bool vec_all = false;
+  // a buffer this rank does not use (its counts zero: it may be NULL) is stood in for by the other
+  // one, as the rooted collectives do; a rank with neither by the communicator's stub
+  const void* const send = gather ? one : arr;
+  void* const recv = gather ? arr : one;
+  const void* rsend = send ? send : recv;
+  void* rrecv = recv ? recv : const_cast<void*>(send);
+  if (pbuf_.available()) {
+    const bool read_ok = ((algo_ == 2 || algo_ == 4) && (!auto_ || topo_read_)) || (algo_ == 3 && topo_read_);
+    if (!rsend && read_ok) {
+      if (!var_stub_ && hipMalloc((void**)&var_stub_, 256) != hipSuccess) {
+        (void)hipGetLastError();
+        var_stub_ = nullptr;
+      }
+      rsend = rrecv = var_stub_;
+    }
+    bool eligible = false;
+    if (read_ok && rsend) {
+      pbuf_.reap(rsend, rrecv);
+      bool local_s = false, local_r = false;
+      const void* ks = rsend;
+      const void* kr = rrecv;
+      const bool dev_s = pbuf_.known(rsend) ? (local_s = true) : reach(rsend, &ks, &local_s) == Reach::kDevice;
+      const bool dev_r = pbuf_.known(rrecv) ? (local_r = true) : reach(rrecv, &kr, &local_r) == Reach::kDevice;
+      eligible = dev_s && dev_r && local_s && local_r;
+    }
+    try {
+      d = pbuf_.negotiate(rsend, rrecv, eligible, 0, dtype, op, cfg_.timeout_ms / 1000.0 + 2.0,
+                          [this] { wait_previous_call(); }, psend, precv, &vec_all, (auto_ ? 0xff : algo_) | coll << 8,
+                          &row, rows, sbits);
+    } catch (const PeerGaveUp& e) {
+      return rendezvous_failed(e, true, scope.cur_dev);
+    } catch (const std::exception& e) {
+      return rendezvous_failed(e, false, scope.cur_dev);
+    }
+    if (d == PeerBuffers::kWindowPeer) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: a peer ran this call on registered windows where this rank called %s; "
+              "communicator is no longer usable\n", rank_, name);
+      sticky_ = ncclInvalidUsage;
+      abort_peers();
+      return leave(sticky_);
+    }
+    if (d == PeerBuffers::kMismatch) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: the ranks passed different counts or displacements, or called different "
+              "collectives / datatypes / ops (or scalars) / schedules (mncclCommSetAlgo)\n", rank_, name);
+      return leave(ncclInvalidUsage);
+    }
+  } else if (!gather_rows(row, dtype, rows, coll, op, sbits) || vhalf_rows_differ(n, rows) != 0) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s: the ranks passed different counts or displacements, or called different "
+            "collectives / datatypes / ops (or scalars)\n", rank_, name);
+    return leave(ncclInvalidUsage);
+  }
+  const size_t M = (size_t)vhalf_max_count(n, rows[0]) * (size_t)esz;  // the largest block: the same everywhere
+  if (M == 0) return leave(ncclSuccess);  // every count is 0 on every rank: nothing launched
+  if (d != PeerBuffers::kRead && varblock_any_capturing(n, rows)) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s: this call runs the padded ring, whose stage cannot be allocated inside a "
+            "HIP graph capture (some rank's stream is capturing)\n", rank_, name);
+    return leave(ncclInvalidUsage);
+  }
+  uint32_t seq = ++call_seq_;
+  if (seq == 0) seq = ++call_seq_;
+  if (d == PeerBuffers::kRead) {
+    VHalfArgs v;
+    v.base = base;
+    v.bytes = mine;
+    int A = 0;
+    CollParams p = make_params(2, rsend, rrecv, M, seq, psend, precv, 0, 0, coll, 0, 0, &A);
+    p.scale = sbits;
+    // the one-block buffer, shifted so that this rank's block of it is the buffer itself (never
+    // dereferenced below the buffer: every slice starts at v.base)
+    if (gather) p.send -= base;
+    else p.recv -= base;
+    hip_check(launch_vhalf(dtype, op, vhalf_vec(vec_all, base, mine), A / geo_.waves, cfg_.threads, p, v, stream),
+              "kernel launch");
+    last_algo_ = 2;
+  } else {
+    const size_t Mpad = (M + 15) & ~(size_t)15;
+    ensure_stage((size_t)n * Mpad, stream);
+    char* const own = stage_ + (size_t)rank_ * Mpad;
+    if (gather) {
+      if (mine) hip_check(hipMemcpyAsync(own, one, mine, hipMemcpyDefault, stream), "pack");
+      launch(0, own, stage_, Mpad, dtype, kSum, stream, seq, true, nullptr, nullptr, 0, 0, kCollAllGather);
+      for (int q = 0; q < n; ++q) {
+        if (!counts[q] || (q == rank_ && one == arr + base)) continue;  // (in place: the own block is there)
+        hip_check(hipMemcpyAsync(arr + displs[q] * (size_t)esz, q == rank_ ? one : stage_ + (size_t)q * Mpad,
+                                 counts[q] * (size_t)esz, hipMemcpyDefault, stream), "unpack");
+      }
+    } else {
+      for (int q = 0; q < n; ++q)
+        if (counts[q])
+          hip_check(hipMemcpyAsync(stage_ + (size_t)q * Mpad, arr + displs[q] * (size_t)esz, counts[q] * (size_t)esz,
+                                   hipMemcpyDefault, stream), "pack");
+      launch(0, stage_, own, Mpad, dtype, op, stream, seq, true, nullptr, nullptr, 0, 0, kCollReduceScatter, 0, 0, scalar);
+      if (mine) hip_check(hipMemcpyAsync(one, own, mine, hipMemcpyDefault, stream), "own block");
+    }
   }
   return end_call(scope, stream, seq);
 }

@@ -129,6 +129,24 @@ class Comm {
   ncclResult_t all_to_all_v(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
                             const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream);
 
+  // The halves with per-rank counts (mncclAllGatherv / mncclReduceScatterv, mini_nccl_ext.h; counts and
+  // displacements in elements, host arrays of n entries read before the call returns, the same on
+  // every rank): rank q's send becomes elements [rdispls[q], +recvcounts[q]) of every rank's recv;
+  // rank r's recv gets the reduction of elements [sdispls[r], +sendcounts[r]) of every rank's send in
+  // the all-reduce's association for chunk r.  One call path for both (comm.cpp vhalf), modelled on
+  // all_to_all_v: the local checks (vhalves.h), a rendezvous that carries every rank's arrays to every
+  // rank and compares them for equality, then the read schedule (kernels.hip vhalf_push / vhalf_fold)
+  // or, where the rendezvous decides against it, the ring's halves on blocks padded to the largest one.
+  ncclResult_t all_gather_v(const void* send, size_t sendcount, void* recv, const size_t* recvcounts,
+                            const size_t* rdispls, int dtype, hipStream_t stream) {
+    return vhalf(kCollAllGatherV, recv, recvcounts, rdispls, const_cast<void*>(send), sendcount, dtype, kSum, stream, 0);
+  }
+  ncclResult_t reduce_scatter_v(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
+                                size_t recvcount, int dtype, int op, hipStream_t stream, uint64_t scalar = 0) {
+    return vhalf(kCollReduceScatterV, const_cast<void*>(send), sendcounts, sdispls, recv, recvcount, dtype, op, stream,
+                 scalar);
+  }
+
   // Point to point (NCCL's ncclSend / ncclRecv inside ncclGroupStart / ncclGroupEnd; api.cpp keeps
   // the group per thread, p2p.h its rules).  p2p_validate: one operation against the group recorded
   // so far -- the peer's range, the byte size, the overlaps (p2p.h p2p_check_op), then the buffer's
@@ -230,7 +248,13 @@ class Comm {
   ncclResult_t end_call(const CallScope& sc, hipStream_t stream, uint32_t seq);
   // every rank's ncclAllToAllv row where the board is unavailable: over the bootstrap, like
   // mncclCommLinkProbe's records.  False: the ranks disagree on the collective or the datatype
-  bool gather_rows(const VarRow& mine, int dtype, VarRow* rows);
+  // (mncclAllGatherv / mncclReduceScatterv pass their collective, op and scalar bits: compared too)
+  bool gather_rows(const VarRow& mine, int dtype, VarRow* rows, int coll = kCollAllToAllV, int op = 0,
+                   uint64_t scalar = 0);
+  // mncclAllGatherv / mncclReduceScatterv: array_buf / counts / displs the side with n blocks (the
+  // gather's recv, the scatter's send), one_buf / one_count this rank's one block
+  ncclResult_t vhalf(int coll, void* array_buf, const size_t* counts, const size_t* displs, void* one_buf,
+                     size_t one_count, int dtype, int op, hipStream_t stream, uint64_t scalar);
   // the one call path of the eight collectives; count: the all-reduce's and the rooted ones', per
   // rank for the halves, per block for the all-to-all, the gather and the scatter
   ncclResult_t collective(int coll, const void* send, void* recv, size_t count, int dtype, int op,
@@ -305,7 +329,7 @@ class Comm {
 
   char* stage_ = nullptr;         // device staging copy for pageable host buffers (grown on demand)
   size_t stage_bytes_ = 0;
-  char* var_stub_ = nullptr;      // ncclAllToAllv: stands in for a rank's NULL buffers in the rendezvous
+  char* var_stub_ = nullptr;      // ncclAllToAllv (and the halves with per-rank counts): stands in for a rank's NULL buffers in the rendezvous
                                   // (an idle rank passes none); allocated on first need
 
   hipEvent_t order_ev_ = nullptr;     // recorded after every call: cross-stream ordering, and the

@@ -125,6 +125,21 @@ struct VarBlockArgs {
 // every rank), p.peer_recv every rank's recv.  By element size (1 / 2 / 4 / 8 from dtype): no arithmetic.
 hipError_t launch_varblock(int dtype, int channels, int threads, const CollParams& p, const VarBlockArgs& v,
                            hipStream_t stream);
+// mncclReduceScatterv / mncclAllGatherv on the read schedule (kernels.hip vhalf_fold / vhalf_push):
+// this rank's block of the array-side buffers, a second by-value kernel argument (CollParams stays
+// byte for byte what it was).  The arrays are the same on every rank, so `base` is the block's byte
+// offset in EVERY rank's array-side buffer.
+struct VHalfArgs {
+  uint64_t base;   // displs[rank] * element size
+  uint64_t bytes;  // counts[rank] * element size (0: this rank only takes part in the protocol)
+};
+// p: p.coll kCollReduceScatterV or kCollAllGatherV; the geometry for chunk_bytes = the call's largest
+// block (the same on every rank); the one-block buffer's pointer shifted by -v.base (the fold's p.recv,
+// the push's p.send), p.peer_send / p.peer_recv every rank's array-side buffer.  vec: this rank's
+// alone (vhalves.h vhalf_vec).  The fold takes scatter_fold's datatypes and ops (p.scale the scalar of
+// kPreMulSum); the push goes by element size (1 / 2 / 4 / 8 from dtype) and ignores op.
+hipError_t launch_vhalf(int dtype, int op, bool vec, int channels, int threads, const CollParams& p, const VHalfArgs& v,
+                        hipStream_t stream);
 // ncclSend / ncclRecv (kernels.hip p2p_kernel): one launch for a whole group.  p: the communicator's
 // mailbox, scratch, counters, control words and timeout as every kernel gets them (send / recv and
 // the call geometry unused); a (p2p.h P2pArgs, a second by-value argument): per directed pair the

@@ -31,6 +31,10 @@
 //  varblock_push  the variable all-to-all (ncclAllToAllv) on the same protocol: exchange_push with a
 //                 length and two offsets per destination, the slices cut for the largest block of
 //                 the whole matrix.  Its fallback is the ring's all-to-all on padded blocks.
+//  vhalf_fold / vhalf_push   the halves with per-rank counts (mncclReduceScatterv / mncclAllGatherv)
+//                 on the same protocol: scatter_fold and gather_push with a per-rank base and
+//                 length, the slices cut for the largest block.  Their fallback is the ring's
+//                 halves on padded blocks.
 //  p2p_kernel     point to point (ncclSend / ncclRecv, one launch per group): a send is the sender's
 //                 half of one ring hop to an arbitrary peer, a recv the receiver's half, on the
 //                 ring's scratch, flags and counters; every directed pair of the group on waves of
@@ -1136,9 +1140,14 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) fp8_read(CollPa
 // body(coff, len, lane): the slice at byte coff = r * chunk_bytes + s * slice_bytes, len bytes long.
 // ROOTED (root_fold / root_relay): the chunks are ceil(count / n) elements, so each slice's length
 // is additionally clamped to the buffer's end (schedule.h rooted_len).
-template <bool ROOTED = false, typename Body>
+// VAR (vhalf_fold / vhalf_push, per-rank counts): the call's geometry is the LARGEST block's, this
+// rank's slices start at byte vbase of the array-side buffers and their lengths are clamped to its own
+// block of vbytes (schedule.h vhalf_len) -- only the body is skipped once the block has run out, START
+// and DONE are exchanged all the same.  Nothing of the protocol below depends on the block, nor on the
+// body's VEC: it counts messages by p.iters alone, so ranks of one call may run different paths.
+template <bool ROOTED = false, bool VAR = false, typename Body>
 __device__ __forceinline__ void read_half(const CollParams& p, u64 (*s_tx)[kMaxRanks], u64 (*s_rx)[kMaxRanks],
-                                          const Body& body) {
+                                          const Body& body, u64 vbase = 0, u64 vbytes = 0) {
   signal_start(p);
   const WaveId id = wave_id();
   const int lane = id.lane, w = id.w, C = p.pipes, A = id.C;
@@ -1163,9 +1172,10 @@ __device__ __forceinline__ void read_half(const CollParams& p, u64 (*s_tx)[kMaxR
   acquire_sys(p.sys_fence);
   for (uint32_t j = 0; j < iters; ++j) {
     const u64 s = (u64)j * A + w;
-    const uint32_t len = ROOTED ? (uint32_t)rooted_len(p.total_bytes, (u64)r * p.chunk_bytes, p.chunk_bytes, p.slice_bytes, s)
-                                : (uint32_t)slice_len(p.chunk_bytes, p.slice_bytes, s);
-    const u64 coff = (u64)r * p.chunk_bytes + s * p.slice_bytes;
+    const uint32_t len = VAR      ? (uint32_t)vhalf_len(vbytes, p.slice_bytes, s)
+                         : ROOTED ? (uint32_t)rooted_len(p.total_bytes, (u64)r * p.chunk_bytes, p.chunk_bytes, p.slice_bytes, s)
+                                  : (uint32_t)slice_len(p.chunk_bytes, p.slice_bytes, s);
+    const u64 coff = VAR ? vbase + s * p.slice_bytes : (u64)r * p.chunk_bytes + s * p.slice_bytes;
     if (len) body(coff, len, lane);
   }
   // DONE: every load of a peer's send has returned and every push into a peer's recv has landed
@@ -1326,6 +1336,66 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) gather_push(Col
 template <bool VEC>
 __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) byte_gather(CollParams p) {
   gather_body<1, VEC>(p);
+}
+
+// ---------------------------------------------------------------- the halves with per-rank counts
+// mncclReduceScatterv (vhalf_fold) and mncclAllGatherv (vhalf_push) on device buffers every rank can
+// share: scatter_fold and gather_push with a per-rank base and length (kernels.h VHalfArgs, a second
+// by-value argument), in read_half<VAR>'s protocol message for message.  The arrays are the same on
+// every rank, so one byte offset serves every rank's array-side buffer: rank r's block sits at byte
+// v.base of every send (the fold) / of every recv (the push).  The geometry is the largest block's
+// (p.chunk_bytes = M on every rank); a rank whose block is short or empty runs fewer or no bodies
+// and the same START and DONE.
+// Fold: rank r folds its block out of every rank's send at v.base, in the all-reduce's order for
+// chunk r (read_fold<.., PUSH = false>), into its recv -- p.recv is recv - v.base (Comm::vhalf), as
+// scatter_fold's is recv - r * chunk_bytes, and is never dereferenced below recv.  In place (recv ==
+// send + v.base): only rank r reads block r of anyone's send, and it stores a batch after that
+// batch's loads; the blocks do not overlap (vhalves.h), so no peer reads what it writes.
+// Push: each slice of send is loaded ONCE (p.send is send - v.base) and stored at v.base of this
+// rank's recv and of every peer's (copy_push_slice); in place, the own store is dropped.
+// (The one-byte entry points are vhalf_fp8 / vhalf_byte, not fp8_* / byte_* like the other families':
+// every name of this family starts with what it belongs to.)
+// VEC is this rank's alone (vhalves.h vhalf_vec): a rank whose base or length is odd takes the
+// element path while its peers take vectors -- see read_half: the protocol does not see it.
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) vhalf_fold(CollParams p, VHalfArgs v) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half<false, true>(
+      p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, OPC, VEC, false>(p, coff, len, lane); },
+      v.base, v.bytes);
+}
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) scaled_vhalf(CollParams p, VHalfArgs v) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half<false, true>(
+      p, s_tx, s_rx,
+      [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, kPreMulSum, VEC, false>(p, coff, len, lane); }, v.base,
+      v.bytes);
+}
+template <typename T, int OPC, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) vhalf_fp8(CollParams p, VHalfArgs v) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half<false, true>(
+      p, s_tx, s_rx, [&p](u64 coff, uint32_t len, int lane) { (void)read_fold<T, OPC, VEC, false>(p, coff, len, lane); },
+      v.base, v.bytes);
+}
+template <int ESZ, bool VEC>
+__device__ __forceinline__ void vhalf_push_body(const CollParams& p, const VHalfArgs& v) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half<false, true>(
+      p, s_tx, s_rx,
+      [&p](u64 coff, uint32_t len, int lane) {
+        copy_push_slice<ESZ, VEC, true>(p, p.send, p.send != p.recv, p.n - 1, 0, coff, len, lane);
+      },
+      v.base, v.bytes);
+}
+template <int ESZ, bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) vhalf_push(CollParams p, VHalfArgs v) {
+  vhalf_push_body<ESZ, VEC>(p, v);
+}
+template <bool VEC>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) vhalf_byte(CollParams p, VHalfArgs v) {
+  vhalf_push_body<1, VEC>(p, v);
 }
 
 // ---------------------------------------------------------------- the rooted collectives
@@ -2595,6 +2665,35 @@ hipError_t launch_persistent(int kernel, int dtype, int op, bool vec, int C, int
 #undef COPIES
 #undef FOLDS
 #undef FP8_FOLDS
+}
+
+hipError_t launch_vhalf(int dtype, int op, bool vec, int C, int nt, const CollParams& p, const VHalfArgs& v,
+                        hipStream_t st) {
+  if (p.n < 2 || v.bytes > p.chunk_bytes) return hipErrorInvalidValue;
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(C), dim3(nt), 0, st, p, v);
+    return hipGetLastError();
+  };
+  if (p.coll == kCollAllGatherV) {
+    if (dtype_size(dtype) == 1) return for_vec(vec, [&](auto e) { return go(vhalf_byte<decltype(e)::value>); });
+    return for_size_vec(dtype, vec, [&](auto e, auto w) { return go(vhalf_push<decltype(e)::value, decltype(w)::value>); });
+  }
+  if (p.coll != kCollReduceScatterV) return hipErrorInvalidValue;
+  if (is_fp8(dtype))
+    return for_fp8(dtype, [&](auto t) {
+      return for_fp8_op(op, [&](auto o) {
+        return for_vec(vec, [&](auto w) {
+          return go(vhalf_fp8<typename decltype(t)::type, decltype(o)::value, decltype(w)::value>);
+        });
+      });
+    });
+  if (op == kPreMulSum)
+    return for_dtype(dtype, [&](auto t) {
+      return for_vec(vec, [&](auto w) { return go(scaled_vhalf<typename decltype(t)::type, decltype(w)::value>); });
+    });
+  return for_type_op_vec(dtype, op, vec, [&](auto t, auto o, auto w) {
+    return go(vhalf_fold<typename decltype(t)::type, decltype(o)::value, decltype(w)::value>);
+  });
 }
 
 hipError_t launch_varblock(int dtype, int C, int nt, const CollParams& p, const VarBlockArgs& v, hipStream_t st) {

@@ -643,7 +643,10 @@ PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, 
     mismatch = mismatch || (!row && c.count != count) || c.dtype != dtype || c.op != op || c.scalar != scalar || c.form != form;
   }
   // ncclAllToAllv: every pair's counts instead of the scalar count (only rows of this collective)
-  if (row && rows_out && !mismatch) mismatch = varblock_matrix_mismatch(nranks_, rows_out) != 0;
+  // (mncclAllGatherv / mncclReduceScatterv: the rows must be equal instead, vhalves.h; ranks that
+  // differ in the collective differ in `form` above)
+  if (row && rows_out && !mismatch)
+    mismatch = (row->flags & kVarSameRows ? vhalf_rows_differ(nranks_, rows_out) : varblock_matrix_mismatch(nranks_, rows_out)) != 0;
   const Decision d = mismatch ? kMismatch : all ? kRead : kFallback;
   *vec_all = aligned;
   if (d != kRead) return d;

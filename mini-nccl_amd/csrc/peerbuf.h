@@ -31,6 +31,7 @@
 #include "bootstrap.h"
 #include "ipcreg.h"
 #include "varblock.h"
+#include "vhalves.h"
 
 namespace mnccl {
 
@@ -73,6 +74,8 @@ class PeerBuffers {
   // record; `rows_out` then gets every rank's row (nranks entries, whatever the decision), and the
   // scalar `count` comparison is replaced by the matrix check (varblock.h): kMismatch when
   // sendcounts_r[q] != recvcounts_q[r] for some pair.  Calls that pass no row behave as before.
+  // A row flagged kVarSameRows (mncclAllGatherv / mncclReduceScatterv, vhalves.h) is compared for
+  // equality instead: kMismatch when some rank's counts or displacements differ from rank 0's.
   Decision negotiate(const void* send, const void* recv, bool eligible, uint64_t count, int dtype, int op,
                      double timeout_s, const std::function<void()>& sync_previous, const char** psend,
                      const char** precv, bool* vec_all, int form = 0, const VarRow* row = nullptr,

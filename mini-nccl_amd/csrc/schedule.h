@@ -138,6 +138,10 @@ MNCCL_HD RingOp ring_op(int n, int r, int k) {
 // The variable all-to-all (ncclAllToAllv, kCollAllToAllV) has no ring table of its own: off the read
 // schedule it runs the table above on blocks padded to the largest one (Comm::all_to_all_v).
 //
+// The halves with per-rank counts (mncclAllGatherv / mncclReduceScatterv, kCollAllGatherV /
+// kCollReduceScatterV) have none either: off the read schedule they run the two tables above on
+// blocks padded to the largest one (Comm::vhalf).
+//
 // Gather and scatter (ncclGather / ncclScatter; a chunk is one block of `count` elements, the root's
 // large buffer holds n of them; `root` is rank-uniform).  Both are a chain in ring direction, with
 // pos = (r - root) mod n the rank's place in it; the op count and each link's message count depend
@@ -156,7 +160,11 @@ MNCCL_HD RingOp ring_op(int n, int r, int k) {
 //   in place, as the ring's all-gather gets its own chunk.
 enum Coll : int {
   kCollAllReduce = 0, kCollReduceScatter = 1, kCollAllGather = 2, kCollBroadcast = 3, kCollReduce = 4, kCollAllToAll = 5,
-  kCollAllToAllV = 6, kCollGather = 7, kCollScatter = 8
+  kCollAllToAllV = 6, kCollGather = 7, kCollScatter = 8,
+  // the halves with per-rank counts (mncclAllGatherv / mncclReduceScatterv): like kCollAllToAllV they
+  // have no ring table of their own -- off the read schedule they run the ring's halves on blocks
+  // padded to the largest one (Comm::vhalf)
+  kCollAllGatherV = 9, kCollReduceScatterV = 10
 };
 
 // r, root: gather and scatter only (their op count depends on the rank's place in the chain; the
@@ -295,6 +303,19 @@ MNCCL_HD uint64_t varblock_len_at(uint64_t block_bytes, uint64_t slice_bytes, ui
 }
 MNCCL_HD uint64_t varblock_len(uint64_t block_bytes, uint64_t slice_bytes, uint64_t s) {
   return varblock_len_at(block_bytes, slice_bytes, s * slice_bytes);
+}
+
+// mncclReduceScatterv / mncclAllGatherv on the read schedule (kernels.hip vhalf_fold / vhalf_push):
+// the call's slices are cut for the LARGEST block of the call, M = max(counts) * element size (the
+// same on every rank), and rank r's slice s covers the bytes [base_r + s * slice_bytes, + vhalf_len)
+// of the array-side buffers, base_r = displs[r] * element size -- 0 once rank r's own block of
+// `block_bytes` has run out, and for an empty block: such a slice touches nothing, and the rank
+// still exchanges START and DONE.
+MNCCL_HD uint64_t vhalf_len(uint64_t block_bytes, uint64_t slice_bytes, uint64_t s) {
+  const uint64_t off = s * slice_bytes;
+  if (off >= block_bytes) return 0;
+  const uint64_t rest = block_bytes - off;
+  return rest < slice_bytes ? rest : slice_bytes;
 }
 
 // The rooted collectives' slices (ncclBroadcast / ncclReduce): the buffer's `total_bytes` are cut

@@ -13,6 +13,8 @@
 // mnccl_sim_varblock adds ncclAllToAllv (kernels.hip varblock_push; the ring on padded blocks).
 // mnccl_sim_all_collectives adds ncclGather / ncclScatter (the ring's chains, kernels.hip collect_push /
 // deal_push) to those seven.
+// mnccl_sim_vhalves adds mncclAllGatherv / mncclReduceScatterv (kernels.hip vhalf_push / vhalf_fold; the
+// ring's halves on padded blocks) to the eight with uniform counts.
 // mnccl_sim_p2p adds ncclSend / ncclRecv groups (kernels.hip p2p_kernel, one wave per (pair, pipeline)
 // from p2p.h's argument builder), every rank running its own list of launches, between collectives.
 // fp32 only (the schedule does not depend on the element type); ops as reference
@@ -24,6 +26,7 @@
 
 #include "p2p.h"
 #include "schedule.h"
+#include "vhalves.h"
 
 using namespace mnccl;
 
@@ -59,6 +62,9 @@ struct World {
   // ncclAllToAllv (coll 6) on the read schedule: per (source r, destination q), at [r * n + q], the
   // block's bytes and its byte offsets in r's send and in q's recv (kernels.h VarBlockArgs)
   const uint64_t *vbytes = nullptr, *vsrc = nullptr, *vdst = nullptr;
+  // mncclAllGatherv / mncclReduceScatterv (coll 9 / 10) on the read schedule: per rank, its block's byte
+  // offset in every rank's array-side buffer and its length (kernels.h VHalfArgs)
+  const uint64_t *hbase = nullptr, *hbytes = nullptr;
 
   // message `seq` from src to dst on pipeline w (schedule.h msg_slot_off: the receiver's scratch)
   char* slot(int src, int dst, int w, uint64_t seq) {
@@ -243,6 +249,31 @@ bool read_step(World& W, Prog& P) {
       if (len) memcpy((char*)W.recv[q] + W.vdst[i] + soff, (const char*)W.send[r] + W.vsrc[i] + soff, (size_t)len);
     }
   };
+  // kernels.hip vhalf_fold: slice `it` of the largest-block geometry, clamped to this rank's own block
+  // (schedule.h vhalf_len), folded out of every rank's send at hbase[r] in ring order into this rank's
+  // recv (W.recv[r] is recv - hbase[r]); every load of the slice first (in place)
+  auto vfold = [&](uint32_t it) {
+    const uint64_t s = (uint64_t)it * W.A + w;
+    const uint64_t len = vhalf_len(W.hbytes[r], W.slice, s), coff = W.hbase[r] + s * W.slice;
+    if (!len) return;
+    std::vector<float> res((size_t)(len / 4));
+    for (uint64_t i = 0; i < len / 4; ++i) {
+      float acc = ((const float*)((const char*)W.send[r] + coff))[i];
+      for (int k = 1; k < n; ++k) acc = apply(W.op, ((const float*)((const char*)W.send[direct_peer(n, r, k)] + coff))[i], acc);
+      res[(size_t)i] = acc;
+    }
+    memcpy((char*)W.recv[r] + coff, res.data(), (size_t)len);
+  };
+  // kernels.hip vhalf_push: the same slice of this rank's send (W.send[r] is send - hbase[r]) into
+  // hbase[r] of its own recv (not in place) and of every peer's
+  auto vpush = [&](uint32_t it) {
+    const uint64_t s = (uint64_t)it * W.A + w;
+    const uint64_t len = vhalf_len(W.hbytes[r], W.slice, s), coff = W.hbase[r] + s * W.slice;
+    if (!len) return;
+    const char* src = (const char*)W.send[r] + coff;
+    if (W.own[(size_t)r]) memcpy((char*)W.recv[r] + coff, src, (size_t)len);
+    for (int k = 1; k < n; ++k) memcpy((char*)W.recv[direct_peer(n, r, (k - 1 + w) % (n - 1) + 1)] + coff, src, (size_t)len);
+  };
   switch (P.j) {
     case 0:
       // START (kernels.hip read_kernel).  A registered-window call's signature is stored with it but
@@ -282,6 +313,8 @@ bool read_step(World& W, Prog& P) {
         else if (W.coll == kCollBroadcast) relay(P.it++);
         else if (W.coll == kCollAllToAll) exchange(P.it++);
         else if (W.coll == kCollAllToAllV) varexchange(P.it++);
+        else if (W.coll == kCollAllGatherV) vpush(P.it++);
+        else if (W.coll == kCollReduceScatterV) vfold(P.it++);
         else if (W.coll == kCollGather) collect(P.it++);
         else if (W.coll == kCollScatter) deal(P.it++);
         else fold(P.it++);
@@ -382,9 +415,11 @@ int run_call(World& W, int code, int coll, uint64_t count, const float* const* s
   W.total_bytes = rooted ? count * 4 : 0;
   W.chunk_bytes = chunk * 4;
   if (coll == kCollAllToAllV) W.chunk_bytes = count;  // (run_var_call: the largest block, in bytes)
+  const bool vhalf = coll == kCollAllGatherV || coll == kCollReduceScatterV;
+  if (vhalf) W.chunk_bytes = count;  // (run_vhalf_call: the largest block, in bytes)
   W.send.assign(send, send + n);
   W.recv.assign(recv, recv + n);
-  W.own.assign((size_t)n, 1);
+  if (!vhalf) W.own.assign((size_t)n, 1);  // (run_vhalf_call has set it and shifted the pointers)
   if (gs) {
     // Comm::collective: a non-root's large buffer (it may be NULL) is stood in for by its one-block
     // buffer; one rank: a copy; on the ring the root's own block reaches its place by a copy before
@@ -452,7 +487,7 @@ int run_call(World& W, int code, int coll, uint64_t count, const float* const* s
         if (s != d) memcpy(d, s, (size_t)W.chunk_bytes);
         continue;
       }
-      if (coll == kCollAllToAllV) continue;  // read schedule only: the kernel moves the own block too
+      if (coll == kCollAllToAllV || vhalf) continue;  // read schedule only: the kernel moves the own block too
       if (coll == kCollAllToAll) {
         // no pointer shift and no in-place form; the ring moves the blocks between ranks only, the
         // own block reaches the own recv by a copy before the launch (Comm::collective)
@@ -581,6 +616,82 @@ int run_var_call(World& W, int code, int esz, const uint64_t* counts, const uint
       const char* from = q == r ? send[r] + sdispls[(size_t)r * n + r] * esz : out[(size_t)r].data() + (size_t)q * Mpad;
       memcpy(recv[r] + rdispls[(size_t)r * n + q] * esz, from, (size_t)c);
     }
+  return 0;
+}
+
+// One mncclAllGatherv (coll 9) / mncclReduceScatterv (coll 10) call on the state W, as Comm::vhalf runs
+// it.  counts / displs: n entries in elements of esz bytes, the same on every rank (the caller has
+// checked the rules, vhalves.h); array[r] rank r's buffer with the n blocks (the gather's recv, the
+// scatter's send), one[r] its one block (NULL allowed where counts[r] is 0).  The geometry follows M,
+// the largest block in bytes.  Read (code 2): kernels.hip vhalf_push / vhalf_fold through read_step,
+// the one-block buffer's pointer shifted by -base.  Ring (code 0): an n * Mpad stage per rank in the
+// in-place layout -- the gather packs its block into chunk r, runs the ring all-gather and unpacks the
+// n blocks; the scatter packs the n blocks, runs the ring reduce-scatter and copies chunk r out.
+// The fold is fp32 (esz 4), as everywhere in this simulator.
+int run_vhalf_call(World& W, int code, int coll, int esz, const uint64_t* counts, const uint64_t* displs,
+                   char* const* array, char* const* one, uint64_t slice_bytes, uint64_t min_slice, uint64_t schedule_seed,
+                   uint64_t& rng, uint64_t& steps) {
+  const int n = W.n;
+  const bool gather = coll == kCollAllGatherV;
+  if ((code != 0 && code != 2) || (!gather && esz != 4)) return -2;
+  uint64_t M = 0;
+  for (int q = 0; q < n; ++q) M = counts[q] * (uint64_t)esz > M ? counts[q] * (uint64_t)esz : M;
+  if (M == 0) return 0;  // nothing launched
+  if (n == 1) {
+    char* blk = array[0] + displs[0] * esz;
+    if (blk != one[0]) memcpy(gather ? blk : one[0], gather ? one[0] : blk, (size_t)M);
+    return 0;
+  }
+  if (code == 2) {
+    std::vector<uint64_t> hb((size_t)n), hl((size_t)n);
+    std::vector<const float*> sp((size_t)n);
+    std::vector<float*> rp((size_t)n);
+    W.own.assign((size_t)n, 1);
+    for (int r = 0; r < n; ++r) {
+      hl[(size_t)r] = counts[r] * (uint64_t)esz;
+      hb[(size_t)r] = counts[r] ? displs[r] * (uint64_t)esz : 0;  // an empty block's displacement is never used
+      // Comm::vhalf: a NULL one-block buffer is stood in for by the other; then shifted by -base
+      char* o = one[r] ? one[r] : array[r];
+      sp[(size_t)r] = (const float*)(gather ? o - hb[(size_t)r] : array[r]);
+      rp[(size_t)r] = (float*)(gather ? array[r] : o - hb[(size_t)r]);
+      W.own[(size_t)r] = (const void*)sp[(size_t)r] != (const void*)rp[(size_t)r];
+    }
+    W.hbase = hb.data();
+    W.hbytes = hl.data();
+    const int rc = run_call(W, 2, coll, M, sp.data(), rp.data(), slice_bytes, min_slice, schedule_seed, rng, steps);
+    W.hbase = W.hbytes = nullptr;
+    return rc;
+  }
+  const uint64_t Mpad = (M + 15) & ~(uint64_t)15;
+  std::vector<std::vector<char>> stage((size_t)n, std::vector<char>((size_t)(n * Mpad), (char)0x5c));
+  std::vector<const float*> sp((size_t)n);
+  std::vector<float*> rp((size_t)n);
+  for (int r = 0; r < n; ++r) {
+    char* st = stage[(size_t)r].data();
+    if (gather) {
+      if (counts[r]) memcpy(st + (size_t)r * Mpad, one[r], (size_t)(counts[r] * esz));
+    } else {
+      for (int q = 0; q < n; ++q)
+        if (counts[q]) memcpy(st + (size_t)q * Mpad, array[r] + displs[q] * esz, (size_t)(counts[q] * esz));
+    }
+    sp[(size_t)r] = (const float*)(gather ? st + (size_t)r * Mpad : st);
+    rp[(size_t)r] = (float*)(gather ? st : st + (size_t)r * Mpad);
+  }
+  const int rc = run_call(W, 0, gather ? kCollAllGather : kCollReduceScatter, Mpad / 4, sp.data(), rp.data(), slice_bytes,
+                          min_slice, schedule_seed, rng, steps);
+  if (rc != 0) return rc;
+  for (int r = 0; r < n; ++r) {
+    const char* st = stage[(size_t)r].data();
+    if (!gather) {
+      if (counts[r]) memcpy(one[r], st + (size_t)r * Mpad, (size_t)(counts[r] * esz));
+      continue;
+    }
+    for (int q = 0; q < n; ++q) {
+      char* blk = array[r] + displs[q] * esz;
+      if (!counts[q] || (q == r && one[r] == blk)) continue;  // (in place: the own block is there)
+      memcpy(blk, q == r ? one[r] : st + (size_t)q * Mpad, (size_t)(counts[q] * esz));
+    }
+  }
   return 0;
 }
 
@@ -1167,6 +1278,45 @@ int mnccl_sim_all_collectives(int n, int calls, const int* coll, const int* sche
   return 0;
 }
 
+// mnccl_sim_all_collectives' eight collectives with uniform counts (every Coll but ncclAllToAllv) and
+// mncclAllGatherv / mncclReduceScatterv (schedule.h Coll 9 / 10), in any order, on either schedule, on
+// the one communicator state.  For a call of collective 9 / 10, counts[i] is ignored and vcounts /
+// vdispls + i * n hold the call's n counts and displacements in elements (of esz bytes for the gather,
+// of 4 for the fold: fp32), the same on every rank; send[i * n + r] / recv[i * n + r] are rank r's
+// sendbuff / recvbuff as the C call takes them (the one-block buffer may be NULL where counts[r] is 0).
+int mnccl_sim_vhalves(int n, int calls, const int* coll, const int* sched, const uint64_t* counts, const int* roots,
+                      const float* const* send, float* const* recv, int esz, const uint64_t* vcounts,
+                      const uint64_t* vdispls, int op, uint64_t slice_bytes, uint64_t min_slice, int channels, int slots,
+                      uint64_t schedule_seed, uint64_t* steps_out) {
+  if (n < 1 || n > 16 || channels < 1 || slots < 1 || slice_bytes < 4 || slice_bytes % 4 || calls < 0) return -2;
+  if (esz != 1 && esz != 2 && esz != 4 && esz != 8) return -2;
+  World W;
+  init_world(W, n, channels, slots, op, slice_bytes);
+  uint64_t steps = 0;
+  uint64_t rng = schedule_seed * 6364136223846793005ull + 1442695040888963407ull;
+  for (int call = 0; call < calls; ++call) {
+    const int c = coll[call];
+    if (c < kCollAllReduce || c > kCollReduceScatterV || c == kCollAllToAllV) return -2;
+    if (c != kCollAllReduce && sched[call] != 0 && sched[call] != 2) return -2;
+    int rc;
+    if (c == kCollAllGatherV || c == kCollReduceScatterV) {
+      if (!vcounts || !vdispls) return -2;
+      char* const* s = (char* const*)(send + (size_t)call * n);
+      char* const* r = (char* const*)(recv + (size_t)call * n);
+      rc = run_vhalf_call(W, sched[call], c, c == kCollAllGatherV ? esz : 4, vcounts + (size_t)call * n,
+                          vdispls + (size_t)call * n, c == kCollAllGatherV ? r : s, c == kCollAllGatherV ? s : r, slice_bytes,
+                          min_slice, schedule_seed, rng, steps);
+    } else {
+      if (counts[call] == 0) return -2;
+      rc = run_call(W, sched[call], c, counts[call], send + (size_t)call * n, recv + (size_t)call * n, slice_bytes,
+                    min_slice, schedule_seed, rng, steps, roots[call]);
+    }
+    if (rc != 0) return rc;
+  }
+  if (steps_out) *steps_out = steps;
+  return 0;
+}
+
 // One read call (push form) on registered windows: every rank's START carries sigs[r] and every
 // pipeline compares its peers' with its own before touching data (kernels.hip starts_agree).
 // mismatch_out[r] = pipelines of rank r that gave up.  0: every pipeline ran; 1: some gave up
@@ -1360,6 +1510,30 @@ int mnccl_varblock_matrix_mismatch(int n, const uint64_t* sendcounts, const uint
 }
 uint64_t mnccl_varblock_len(uint64_t block_bytes, uint64_t slice_bytes, uint64_t s) {
   return mnccl::varblock_len(block_bytes, slice_bytes, s);
+}
+
+// csrc/vhalves.h, the host-side rules of mncclAllGatherv / mncclReduceScatterv, and schedule.h's length
+// rule for them.  mnccl_vhalf_rows_differ: counts / displs are n x n, row r what rank r passed.
+int mnccl_vhalf_check_local(int n, int rank, int esz, const void* array_buf, const size_t* counts, const size_t* displs,
+                            const void* one_buf, size_t one_count) {
+  return mnccl::vhalf_check_local(n, rank, esz, array_buf, counts, displs, one_buf, one_count);
+}
+int mnccl_vhalf_rows_differ(int n, const uint64_t* counts, const uint64_t* displs) {
+  if (n < 1 || n > mnccl::kVarMaxRanks) return -1;
+  mnccl::VarRow rows[mnccl::kVarMaxRanks];
+  memset(rows, 0, sizeof rows);
+  for (int r = 0; r < n; ++r)
+    for (int q = 0; q < n; ++q) {
+      rows[r].sendcounts[q] = counts[(size_t)r * n + q];
+      rows[r].rdispls[q] = displs[(size_t)r * n + q];
+    }
+  return mnccl::vhalf_rows_differ(n, rows);
+}
+uint64_t mnccl_vhalf_len(uint64_t block_bytes, uint64_t slice_bytes, uint64_t s) {
+  return mnccl::vhalf_len(block_bytes, slice_bytes, s);
+}
+int mnccl_vhalf_vec(int vec_all, uint64_t base_bytes, uint64_t block_bytes) {
+  return mnccl::vhalf_vec(vec_all != 0, base_bytes, block_bytes) ? 1 : 0;
 }
 
 // Config::from_env() rendered to text; -1 if the environment is invalid.

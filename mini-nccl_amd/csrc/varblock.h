@@ -23,7 +23,12 @@ struct VarRow {
   uint32_t flags;  // kVarCapturing
   uint32_t pad;
 };
-enum : uint32_t { kVarCapturing = 1u };  // this rank's stream is being captured into a graph
+enum : uint32_t {
+  kVarCapturing = 1u,  // this rank's stream is being captured into a graph
+  // the row of an mncclAllGatherv / mncclReduceScatterv call (vhalves.h): counts in sendcounts, displs
+  // in rdispls; the ranks' rows must be EQUAL, where ncclAllToAllv's must be each other's transpose
+  kVarSameRows = 2u
+};
 
 // The local checks' verdicts, in the order they are made
 enum VarLocal : int {

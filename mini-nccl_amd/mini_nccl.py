@@ -97,6 +97,8 @@ SIGNATURES = {
     "ncclAllToAll": (_I, [_VP, _VP, _SZ, _I, _VP, _VP]),
     "ncclAllToAllv": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ),
                            _I, _VP, _VP]),
+    "mncclAllGatherv": (_I, [_VP, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _I, _VP, _VP]),
+    "mncclReduceScatterv": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclGather": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclScatter": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclSend": (_I, [_VP, _SZ, _I, _I, _VP, _VP]),
@@ -289,6 +291,26 @@ class Comm:
         arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
         return load().ncclAllToAllv(send_ptr, arrays[0], arrays[1], recv_ptr, arrays[2], arrays[3], dtype, self.handle,
                                     stream)
+
+    def all_gather_v(self, send_ptr, sendcount, recv_ptr, recvcounts, rdispls, dtype=ncclFloat, stream=0):
+        """mncclAllGatherv: rank q's `sendcount` elements of send end up at elements [rdispls[q],
+        rdispls[q] + recvcounts[q]) of every rank's recv.  recvcounts / rdispls are Python sequences of
+        nranks entries, the same on every rank (read before the call returns); sendcount must be
+        recvcounts[rank]; a rank whose block is empty may pass 0 / None for send.  In place: send is
+        recv + rdispls[rank] elements.  Returns the ncclResult_t."""
+        arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (recvcounts, rdispls)]
+        return load().mncclAllGatherv(send_ptr, sendcount, recv_ptr, arrays[0], arrays[1], dtype, self.handle, stream)
+
+    def reduce_scatter_v(self, send_ptr, sendcounts, sdispls, recv_ptr, recvcount, dtype=ncclFloat, op=ncclSum,
+                         stream=0):
+        """mncclReduceScatterv: recv gets the reduction over all ranks of elements [sdispls[rank],
+        sdispls[rank] + sendcounts[rank]) of their send, in ncclReduceScatter's association.
+        sendcounts / sdispls are Python sequences of nranks entries, the same on every rank;
+        recvcount must be sendcounts[rank]; a rank whose block is empty may pass 0 / None for recv.  In
+        place: recv is send + sdispls[rank] elements.  Returns the ncclResult_t."""
+        arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls)]
+        return load().mncclReduceScatterv(send_ptr, arrays[0], arrays[1], recv_ptr, recvcount, dtype, op, self.handle,
+                                          stream)
 
     def gather(self, send_ptr, recv_ptr, sendcount, dtype=ncclFloat, root=0, stream=0):
         """ncclGather: the root's recv holds nranks * sendcount elements, rank q's send at

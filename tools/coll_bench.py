@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times ncclReduceScatter, ncclAllGather, ncclBroadcast, ncclReduce, ncclAllToAll, ncclAllToAllv,
-ncclGather, ncclScatter and grouped ncclSend / ncclRecv beside ncclAllReduce on one communicator.
+ncclGather, ncclScatter, mncclAllGatherv, mncclReduceScatterv and grouped ncclSend / ncclRecv beside
+ncclAllReduce on one communicator.
 
     python tools/coll_bench.py --gpus 4 [--same-device] [--bytes N] [--rounds R] [--calls K] [--warmup W]
                                [--kinds all_reduce,reduce_scatter,...] [--dtype f32|bf16]
@@ -51,6 +52,16 @@ persistent form (mncclAlgoRead), fp32 Sum, stream-ordered (MINI_NCCL_BLOCKING=0)
                     gather_over_gather_p2p, scatter_over_scatter_p2p, *_over_all_gather, with the
                     spreads of the groups' and the all-gather's own rounds as the yardsticks
 
+    all_gather_v / reduce_scatter_v   mncclAllGatherv / mncclReduceScatterv with uniform counts and
+                    contiguous displacements: the uniform halves' bytes, so *_v_over_* is the v form's
+                    own overhead (only the clamp differs), beside all_gather_spread / reduce_scatter_spread
+    all_gather_v_skew / reduce_scatter_v_skew   the same total bytes skewed: rank 0 holds half of them,
+                    the other ranks share the rest evenly.  Beside each, what a caller without the v
+                    forms runs: every block padded to the largest and the uniform half called on them,
+    all_gather_padded / reduce_scatter_padded   ncclAllGather / ncclReduceScatter with count = the
+                    largest block (n / 2 chunks) on buffers of n such blocks -- WITHOUT the pack and
+                    unpack passes a caller also pays.  Ratios *_v_skew_over_*_padded
+
 (broadcast: every rank loads one chunk of the root's send and stores it into all n recvs; reduce:
 every rank loads its chunk from all n sends and stores it into the root's recv -- on the one-GPU
 proxy the all-gather's and the reduce-scatter's bytes, the yardsticks of the two ratios
@@ -82,7 +93,12 @@ for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "mini-nccl_amd")):
 
 KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "all_gather", "broadcast", "reduce",
          "all_to_all", "all_to_all_v", "all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
-         "p2p_neighbor_win", "p2p_all_pairs_win", "gather", "gather_p2p", "scatter", "scatter_p2p")
+         "p2p_neighbor_win", "p2p_all_pairs_win", "gather", "gather_p2p", "scatter", "scatter_p2p",
+         "all_gather_v", "reduce_scatter_v", "all_gather_v_skew", "reduce_scatter_v_skew", "all_gather_padded",
+         "reduce_scatter_padded")
+# the kinds that need the padded buffers (n blocks of the skewed shape's largest block)
+PADDED_KINDS = ("all_gather_padded", "reduce_scatter_padded")
+VHALF_SKEW = ("all_gather_v_skew", "reduce_scatter_v_skew") + PADDED_KINDS
 # the kinds --dtype bf16 can time (the others' helpers are written for fp32 elements)
 # the kinds that run while big_b is a registered window, and the scratch form each is measured against
 WIN_KINDS = {"p2p_neighbor_win": "p2p_neighbor", "p2p_all_pairs_win": "p2p_all_pairs"}
@@ -105,6 +121,31 @@ def v_call(M, comm, send, recv, C, rank, stream):
     args = (arr(sc), arr(starts(sc)), arr(rc), arr(starts(rc)))
     f = M.load().ncclAllToAllv
     return lambda: f(send, args[0], args[1], recv, args[2], args[3], M.ncclFloat, comm.handle, stream)
+
+
+def half_skew_counts(n, chunk):
+    """n * chunk elements in all: rank 0 holds half, the others share the rest evenly (the remainder
+    goes to the last rank)."""
+    total = n * chunk
+    if n == 1:
+        return [total]
+    rest = total - total // 2
+    counts = [total // 2] + [rest // (n - 1)] * (n - 1)
+    counts[-1] += rest - sum(counts[1:])
+    return counts
+
+
+def vhalf_calls(M, comm, big_a, big_b, one, counts, rank, stream):
+    """(mncclAllGatherv, mncclReduceScatterv) with contiguous displacements for `counts`, fp32, the
+    arrays built once: the gather from `one` into big_b, the fold from big_a into `one` (the uniform
+    kinds pass the uniform halves' own one-chunk buffer, so only the call differs; the skewed kinds,
+    whose largest block is n / 2 chunks, the head of the other large buffer)."""
+    n = len(counts)
+    arr = lambda xs: (ctypes.c_size_t * n)(*[int(x) for x in xs])
+    c, d = arr(counts), arr([int(sum(counts[:q])) for q in range(n)])
+    L, mine = M.load(), int(counts[rank])
+    return (lambda: L.mncclAllGatherv(one or big_a, mine, big_b, c, d, M.ncclFloat, comm.handle, stream),
+            lambda: L.mncclReduceScatterv(big_a, c, d, one or big_b, mine, M.ncclFloat, M.ncclSum, comm.handle, stream))
 
 
 def p2p_call(M, comm, ops, stream):
@@ -173,6 +214,20 @@ def rank_main(a):
     for k, base in WIN_KINDS.items():
         calls[k] = calls[base]
     kinds = tuple(a.kinds.split(","))
+    calls["all_gather_v"], calls["reduce_scatter_v"] = vhalf_calls(M, comm, big_a.ptr, big_b.ptr, small.ptr, [chunk] * n, a.rank,
+                                                                 st.handle)
+    skew = half_skew_counts(n, chunk)
+    calls["all_gather_v_skew"], calls["reduce_scatter_v_skew"] = vhalf_calls(M, comm, big_a.ptr, big_b.ptr, None, skew, a.rank,
+                                                                           st.handle)
+    pads = []
+    if any(k in PADDED_KINDS for k in kinds):
+        # every block padded to the largest: n blocks of max(skew) elements (allocated only when timed)
+        pads = [hip_rt.DeviceBuffer(n * max(skew) * 4, fresh=True), hip_rt.DeviceBuffer(max(skew) * 4, fresh=True)]
+        for b in pads:
+            b.fill_byte(0)
+        calls["all_gather_padded"] = lambda: comm.all_gather(pads[1].ptr, pads[0].ptr, max(skew), M.ncclFloat, st.handle)
+        calls["reduce_scatter_padded"] = lambda: comm.reduce_scatter(pads[0].ptr, pads[1].ptr, max(skew), M.ncclFloat,
+                                                                     M.ncclSum, st.handle)
     window = [None]
 
     def set_window(k, on):
@@ -222,7 +277,7 @@ def rank_main(a):
     err = comm.async_error()
     H.hipEventDestroy(e0)
     H.hipEventDestroy(e1)
-    for b in (big_a, big_b, small):
+    for b in [big_a, big_b, small] + pads:
         b.free()
     st.destroy()
     comm.destroy()
@@ -296,7 +351,8 @@ def main():
         "rounds_ms": {k: [round(x, 4) for x in v] for k, v in rounds.items()},
         "hbm_bytes": {k: (2 * n if k in ("all_reduce", "all_reduce_premul", "all_to_all", "all_to_all_v") else n + 1) * chunk_bytes
                       for k in kinds if k not in ("all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
-                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") and k not in WIN_KINDS},
+                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") + VHALF_SKEW
+                      and k not in WIN_KINDS},
         "ratio": dict([(f"{k}_over_all_reduce", round(med[k] / med["all_reduce"], 4)) for k in kinds if k != "all_reduce"] +
                       [(f"{k}_over_{y}", round(med[k] / med[y], 4))
                        for k, y in (("reduce", "reduce_scatter"), ("broadcast", "all_gather"), ("all_to_all", "all_gather"),
@@ -337,6 +393,17 @@ def main():
     for k in ("gather", "gather_p2p", "scatter", "scatter_p2p", "p2p_neighbor", "p2p_all_pairs"):
         if k in rounds:
             res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
+    # the halves with per-rank counts: the uniform matrix beside the uniform halves (their own spreads
+    # are the yardsticks), the skewed one beside padding to the largest block
+    for k, y in (("all_gather_v", "all_gather"), ("reduce_scatter_v", "reduce_scatter"),
+                 ("all_gather_v_skew", "all_gather_padded"), ("reduce_scatter_v_skew", "reduce_scatter_padded")):
+        if k in med and y in med:
+            res["ratio"][f"{k}_over_{y}"] = round(med[k] / med[y], 4)
+    for k in ("all_gather_v", "reduce_scatter_v") + VHALF_SKEW:
+        if k in rounds:
+            res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
+    if any(k in VHALF_SKEW for k in kinds):
+        res["half_skew_counts"] = half_skew_counts(n, chunk_bytes // 4)
     if "all_gather" in rounds:
         res["all_gather_spread"] = round((max(rounds["all_gather"]) - min(rounds["all_gather"])) / med["all_gather"], 4)
     print(json.dumps(res))
