@@ -37,6 +37,8 @@
  *   ncclAllToAllv        the same exchange with a count and a displacement per peer on both sides
  *                        (expert-parallel dispatch / combine: every rank sends every peer a different
  *                        number of tokens, possibly none).
+ *   mncclAllToAllvRows   ncclAllToAllv whose send blocks are rows of a matrix picked by a device-side
+ *                        index list (a MoE router's output as it is: no permutation pass in front).
  *
  * and the all-reduce's halves with per-rank counts, which neither NCCL nor RCCL has (callers there
  * compose them from broadcasts / reduces inside one group, which this library does not take), under
@@ -101,7 +103,7 @@ extern "C" {
    lies in a registered window (no new symbol; mncclCommInfo_t grew, same prefix: p2p_direct_recvs,
    p2p_direct_sends -- mncclCommGetInfoV writes them to a caller whose struct has room); still 600:
    mncclAllGatherv and mncclReduceScatterv were added the same way (detected by symbol;
-   mncclCommInfo_t did not grow) */
+   mncclCommInfo_t did not grow); still 600: mncclAllToAllvRows was added the same way */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -394,6 +396,61 @@ ncclResult_t ncclScatter(const void* sendbuff, void* recvbuff, size_t recvcount,
 ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                            const size_t recvcounts[], const size_t rdispls[], ncclDataType_t datatype, ncclComm_t comm,
                            hipStream_t stream);
+
+/* ncclAllToAllv whose send blocks are gathered by a device-side list of row indices: what a MoE router
+ * hands over -- a token matrix in token order and an index list sorted by expert -- goes out as it
+ * is, with no permutation pass of the caller's in front and no k packed copies of a top-k token.
+ * Neither NCCL nor RCCL has it, so it carries the library's prefix.
+ *
+ * sendbuff is a matrix of `nrows` rows: row t starts at element t * rowstride and its first `rowcount`
+ * elements travel (rowstride >= rowcount: a column slice of a wider matrix is fine).  rowidx is an
+ * array of int32 in DEVICE memory of this rank's GPU (or pinned host memory), read by the kernel when
+ * the call runs, never by the host.  sendcounts / sdispls are in rows and index rowidx: the block for
+ * rank q is the rows rowidx[sdispls[q] + i], i < sendcounts[q], in that order.  Indices may repeat
+ * within a block and across blocks, and the peers' ranges of rowidx may overlap.  recvcounts /
+ * rdispls are in rows of the dense recvbuff: rank r's block lands at elements [rdispls[r] * rowcount,
+ * (rdispls[r] + recvcounts[r]) * rowcount) of rank q's recvbuff, its rows packed with no stride.
+ * Datatypes as ncclAllToAllv (no arithmetic: by element size, the fp8 types included).
+ *
+ * Result.  Byte for byte what ncclAllToAllv delivers from a send buffer packed with packed[j] =
+ * row rowidx[j]; bytes of recv outside every block are never written.
+ * An index outside [0, nrows), negative ones included, delivers a row of ZERO bytes and never causes
+ * an access outside sendbuff -- the host cannot see the indices, so this is part of the contract.
+ * Capture.  Counts, displacements and pointers are baked into a captured graph; the CONTENTS of
+ * rowidx are not: a replay gathers by whatever the array holds when it runs, so a router may rewrite
+ * it between replays as long as the counts stay what they were.
+ *
+ * Checks, in ncclAllToAllv's order (no exception crosses the boundary):
+ *  1. a NULL comm or a NULL count / displacement array: ncclInvalidArgument;
+ *  2. a group is open: ncclInvalidUsage, the group stays clean (no deferred collectives);
+ *  3. an unsupported datatype: ncclInternalError, before the communicator is read;
+ *  4. with the communicator, each ncclInvalidArgument with nothing launched or negotiated and the
+ *     communicator still usable: rowcount == 0 with any non-zero count; rowstride < rowcount; nrows >
+ *     INT32_MAX; a NULL sendbuff or rowidx unless every sendcount is 0, a NULL recvbuff unless every
+ *     recvcount is 0; a displ + count, a byte size or an address that overflows size_t (a single row
+ *     of 2 GiB or more is refused as that); two non-empty recv blocks that overlap; a non-empty recv
+ *     block that overlaps the send matrix's byte extent or the used part of rowidx; a rowidx that is
+ *     neither device memory of this GPU nor pinned host memory;
+ *  5. after the per-call rendezvous, sendcounts_r[q] != recvcounts_q[r] for any pair, or ranks that
+ *     differ in the collective, the datatype, rowcount or the schedule choice: ncclInvalidUsage on
+ *     every rank alike, nothing launched, the communicator still usable;
+ *  6. every count on every rank 0: ncclSuccess, nothing launched;
+ *  7. nranks == 1: the local gather kernel alone (a count mismatch is still ncclInvalidUsage).
+ * An idle rank still takes part and may pass NULL buffers.  Blocking mode, stream ordering, sticky
+ * errors and the watchdog as ncclAllToAllv.
+ *
+ * Schedules.  Where ncclAllToAllv would run the read schedule: a persistent kernel in its protocol
+ * and geometry that loads each row where the index points and pushes it straight into its place in
+ * the peer's recvbuff -- one pass over the bytes.  A destination goes in 16-byte vectors when
+ * sendbuff, rowstride and rowcount in bytes, and its address in the peer's recvbuff are all
+ * dword-aligned; each row's last bytes % 16 bytes, and every other destination, go element by element
+ * (last_algo: mncclAlgoRead).  Otherwise (a forced ring, host data buffers, a topology that refuses
+ * read) a gather kernel packs each peer's block into ncclAllToAllv's padded stage and the rest is its
+ * fallback, with its cost and its refusal under capture (last_algo: mncclAlgoRing). */
+ncclResult_t mncclAllToAllvRows(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                                const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                                const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
+                                ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
 
 /* The all-reduce's halves with per-rank counts.  Neither NCCL nor RCCL has them, so they carry the
  * library's prefix and MPI's argument order (MPI_Allgatherv / MPI_Reduce_scatter with displacements).

@@ -348,6 +348,31 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
   }
 }
 
+// The same gathered by row index (mini_nccl_ext.h): ncclAllToAllv's checks in its order; the data
+// buffers and the index list may be NULL on a rank whose counts are all zero, so they are checked with
+// the counts (Comm::all_to_all_v_rows, rowblock.h).
+ncclResult_t mncclAllToAllvRows(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                                const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                                const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
+                                ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
+  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
+  RoctxRange range("mini_ncclAllToAllvRows");
+  if (!dtype_ok(datatype)) {
+    fprintf(stderr, "[Mini-NCCL] AllToAllvRows Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->all_to_all_v_rows(sendbuff, nrows, rowstride, rowidx, sendcounts, sdispls, recvbuff,
+                                                            recvcounts, rdispls, rowcount, (int)datatype, stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] AllToAllvRows Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
 // The halves with per-rank counts (mini_nccl_ext.h): the communicator and the two arrays, the open
 // group, then the datatype and the op; the data buffers may be NULL where the counts are zero, so
 // they are checked with the counts where the communicator's rank and size are known (Comm::vhalf,

@@ -1183,29 +1183,121 @@ bool Comm::gather_rows(const VarRow& mine, int dtype, VarRow* rows, int coll, in
 // and ANY rank is capturing (its flag rides in its row), every rank returns ncclInvalidUsage.
 // A rank whose counts are all zero still takes part in the rendezvous and the protocol: its peers
 // exchange among themselves and every pair's counters advance alike.
-ncclResult_t Comm::all_to_all_v(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
-                                const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream) {
+//
+// mncclAllToAllvRows (rows != nullptr) is the same call with rows for elements: counts and
+// displacements in rows of rows->rowcount elements, so a block's unit is `unit` bytes where
+// ncclAllToAllv's is the element; the send side is a matrix read through rows->rowidx (rowblock.h has
+// its local rules), the rendezvous row carries kVarRows and the row's length, which the ranks must pass
+// alike.  On the read schedule: kernels.hip rows_push.  Else ONE rows_pack launch gathers the blocks
+// where the copies above pack them -- the peers' into the stage at q * Mpad, the own one straight into
+// recv -- and the exchange and the unpack are the ones above.  One rank: rows_pack alone.
+ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
+                                const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream,
+                                const RowsCall* rows_call) {
   if (sticky_ != ncclSuccess) return sticky_;
   if (check_status() != ncclSuccess) return sticky_;
   const int n = nranks_, esz = dtype_size(dtype);
-  const int local = varblock_check_local(n, esz, send, sendcounts, sdispls, recv, recvcounts, rdispls);
-  if (local != kVarOk) {
-    fprintf(stderr, "[Mini-NCCL] rank %d: ncclAllToAllv: %s\n", rank_,
-            local == kVarNullBuffer    ? "a NULL buffer with a non-zero count"
-            : local == kVarOverflow    ? "a displacement plus count, or a byte size, overflows size_t"
-            : local == kVarRecvOverlap ? "two recv blocks overlap"
-                                       : "a recv block overlaps a send block (there is no in-place form)");
-    return ncclInvalidArgument;
+  const char* const name = rows_call ? "mncclAllToAllvRows" : "ncclAllToAllv";
+  const int coll = rows_call ? kCollAllToAllVRows : kCollAllToAllV;
+  if (rows_call) {
+    const int local = rows_check_local(n, esz, send, rows_call->nrows, rows_call->rowstride, rows_call->rowidx, sendcounts,
+                                       sdispls, recv, recvcounts, rdispls, rows_call->rowcount);
+    if (local != kRowsOk) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: %s\n", rank_, name,
+              local == kRowsZeroRow       ? "rowcount is 0 with a non-zero count"
+              : local == kRowsStride      ? "rowstride is smaller than rowcount"
+              : local == kRowsTooManyRows ? "nrows is beyond what an int32 index can name"
+              : local == kRowsNullBuffer  ? "a NULL buffer or index list with a non-zero count"
+              : local == kRowsOverflow    ? "a displacement plus count, a byte size or an address overflows size_t (or a row "
+                                            "is 2 GiB or longer)"
+              : local == kRowsRecvOverlap ? "two recv blocks overlap"
+                                          : "a recv block overlaps the send matrix or the index list");
+      return ncclInvalidArgument;
+    }
+  } else {
+    const int local = varblock_check_local(n, esz, send, sendcounts, sdispls, recv, recvcounts, rdispls);
+    if (local != kVarOk) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: ncclAllToAllv: %s\n", rank_,
+              local == kVarNullBuffer    ? "a NULL buffer with a non-zero count"
+              : local == kVarOverflow    ? "a displacement plus count, or a byte size, overflows size_t"
+              : local == kVarRecvOverlap ? "two recv blocks overlap"
+                                         : "a recv block overlaps a send block (there is no in-place form)");
+      return ncclInvalidArgument;
+    }
   }
+  // a block's unit in bytes: the element, or the row
+  const size_t unit = rows_call ? rows_call->rowcount * (size_t)esz : (size_t)esz;
+  bool sends = false;
+  for (int q = 0; q < n; ++q) sends = sends || sendcounts[q] != 0;
+  const int32_t* kidx = rows_call ? rows_call->rowidx : nullptr;  // the index list as the kernels address it
+  if (rows_call && sends) {
+    // the kernels read the list themselves: device memory of this GPU, or pinned host memory
+    const void* kp = kidx;
+    bool local_i = false;
+    const Reach how = reach(kidx, &kp, &local_i);
+    if (!(how == Reach::kMapped || (how == Reach::kDevice && local_i))) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: rowidx is neither device memory of this GPU nor pinned host memory\n", rank_,
+              name);
+      return ncclInvalidArgument;
+    }
+    kidx = static_cast<const int32_t*>(kp);
+  }
+  // The gather as a grid launch (one rank, and the padded ring): block q's rows packed at dst[q]
+  // (nullptr: not this launch's), all of it memory a kernel can address.  The matrix is read where it
+  // lies when it is device or pinned memory; a pageable one goes through `extra` bytes of stage first
+  // (src_extra; the caller sizes the stage), as the own block does when recv is no device memory.
+  const size_t src_extra = rows_call && sends
+                               ? (size_t)rows_extent_bytes(rows_call->nrows, rows_call->rowstride, rows_call->rowcount, esz)
+                               : 0;
+  auto how = [&](const void* p) {
+    const void* k = p;
+    bool l = false;
+    return reach(p, &k, &l);
+  };
+  const bool src_via = src_extra && how(send) == Reach::kStaged;
+  auto pack_rows = [&](char* const* dst, char* src_stage) {
+    const void* src = send;
+    bool l = false;
+    if (reach(send, &src, &l) == Reach::kStaged) {
+      hip_check(hipMemcpyAsync(src_stage, send, src_extra, hipMemcpyDefault, stream), "stage in");
+      src = src_stage;
+    }
+    RowsPackArgs a;
+    memset(&a, 0, sizeof a);
+    a.src = static_cast<const char*>(src);
+    a.rowidx = kidx;
+    a.stride_bytes = (uint64_t)rows_call->rowstride * (uint64_t)esz;
+    a.row_bytes = (uint32_t)unit;
+    a.nrows = (uint32_t)rows_call->nrows;
+    a.n = n;
+    for (int q = 0; q < n; ++q) {
+      if (!dst[q] || !sendcounts[q]) continue;
+      a.dst[q] = dst[q];
+      a.idx_off[q] = sdispls[q];
+      a.count[q] = sendcounts[q];
+      if (rows_vec_ok(src, a.stride_bytes, unit, (uint64_t)(uintptr_t)dst[q])) a.vec_mask |= 1u << q;
+    }
+    hip_check(launch_rows_pack(dtype, a, stream), "kernel launch");
+  };
   if (n == 1) {
     if (sendcounts[0] != recvcounts[0]) {
-      fprintf(stderr, "[Mini-NCCL] rank 0: ncclAllToAllv: sendcounts[0] != recvcounts[0]\n");
+      fprintf(stderr, "[Mini-NCCL] rank 0: %s: sendcounts[0] != recvcounts[0]\n", name);
       return ncclInvalidUsage;
     }
     if (sendcounts[0] == 0) return ncclSuccess;
     const CallScope scope = begin_call(stream);
-    hip_check(hipMemcpyAsync((char*)recv + rdispls[0] * (size_t)esz, (const char*)send + sdispls[0] * (size_t)esz,
-                             sendcounts[0] * (size_t)esz, hipMemcpyDefault, stream), "copy");
+    if (rows_call) {
+      char* to = (char*)recv + rdispls[0] * unit;
+      const size_t own = sendcounts[0] * unit, own_pad = (own + 15) & ~(size_t)15;
+      const bool via = how(recv) != Reach::kDevice;
+      if (via || src_via) ensure_stage((via ? own_pad : 0) + (src_via ? src_extra : 0), stream);
+      char* const packed = via ? stage_ : to;
+      pack_rows(&packed, stage_ + (via ? own_pad : 0));
+      if (via) hip_check(hipMemcpyAsync(to, packed, own, hipMemcpyDefault, stream), "own block");
+    } else {
+      hip_check(hipMemcpyAsync((char*)recv + rdispls[0] * (size_t)esz, (const char*)send + sdispls[0] * (size_t)esz,
+                               sendcounts[0] * (size_t)esz, hipMemcpyDefault, stream), "copy");
+    }
     return end_call(scope, stream, 0);
   }
   const CallScope scope = begin_call(stream);
@@ -1220,7 +1312,8 @@ ncclResult_t Comm::all_to_all_v(const void* send, const size_t* sendcounts, cons
     mine.recvcounts[q] = recvcounts[q];
     mine.rdispls[q] = rdispls[q];
   }
-  mine.flags = scope.capturing() ? (uint32_t)kVarCapturing : 0u;
+  mine.flags = (scope.capturing() ? (uint32_t)kVarCapturing : 0u) | (rows_call ? (uint32_t)kVarRows : 0u);
+  mine.pad = rows_call ? (uint32_t)rows_call->rowcount : 0u;  // (below 2^31: rows_check_local)
 
   PeerBuffers::Decision d = PeerBuffers::kFallback;
   const char* psend[kMaxRanks] = {};
@@ -1252,7 +1345,7 @@ ncclResult_t Comm::all_to_all_v(const void* send, const size_t* sendcounts, cons
     try {
       d = pbuf_.negotiate(rsend, rrecv, eligible, 0, dtype, 0, cfg_.timeout_ms / 1000.0 + 2.0,
                           [this] { wait_previous_call(); }, psend, precv, &vec_all,
-                          (auto_ ? 0xff : algo_) | kCollAllToAllV << 8, &mine, rows);
+                          (auto_ ? 0xff : algo_) | coll << 8, &mine, rows);
     } catch (const PeerGaveUp& e) {
       return rendezvous_failed(e, true, scope.cur_dev);
     } catch (const std::exception& e) {
@@ -1260,33 +1353,50 @@ ncclResult_t Comm::all_to_all_v(const void* send, const size_t* sendcounts, cons
     }
     if (d == PeerBuffers::kWindowPeer) {
       fprintf(stderr, "[Mini-NCCL] rank %d: a peer ran this call on registered windows where this rank called "
-              "ncclAllToAllv; communicator is no longer usable\n", rank_);
+              "%s; communicator is no longer usable\n", rank_, name);
       sticky_ = ncclInvalidUsage;
       abort_peers();
       return leave(sticky_);
     }
     if (d == PeerBuffers::kMismatch) {
-      fprintf(stderr, "[Mini-NCCL] rank %d: ncclAllToAllv: some rank's sendcounts[q] differs from rank q's recvcounts "
-              "for it, or the ranks called different collectives / datatypes / schedules (mncclCommSetAlgo)\n", rank_);
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: some rank's sendcounts[q] differs from rank q's recvcounts "
+              "for it, or the ranks called different collectives / datatypes%s / schedules (mncclCommSetAlgo)\n", rank_, name,
+              rows_call ? " / rowcounts" : "");
       return leave(ncclInvalidUsage);
     }
-  } else if (!gather_rows(mine, dtype, rows) || varblock_matrix_mismatch(n, rows) != 0) {
-    fprintf(stderr, "[Mini-NCCL] rank %d: ncclAllToAllv: some rank's sendcounts[q] differs from rank q's recvcounts "
-            "for it, or the ranks passed different datatypes\n", rank_);
+  } else if (!gather_rows(mine, dtype, rows, coll) || varblock_matrix_mismatch(n, rows) != 0 ||
+             varblock_rowcounts_differ(n, rows)) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s: some rank's sendcounts[q] differs from rank q's recvcounts "
+            "for it, or the ranks passed different datatypes%s\n", rank_, name, rows_call ? " / rowcounts" : "");
     return leave(ncclInvalidUsage);
   }
-  const size_t M = (size_t)varblock_max_count(n, rows) * (size_t)esz;  // the largest block: the same everywhere
+  const size_t M = (size_t)varblock_max_count(n, rows) * unit;  // the largest block: the same everywhere
   if (M == 0) return leave(ncclSuccess);  // nobody sends anything: nothing launched on any rank
   if (d != PeerBuffers::kRead && varblock_any_capturing(n, rows)) {
-    fprintf(stderr, "[Mini-NCCL] rank %d: ncclAllToAllv: this call runs the padded ring, whose stage cannot be "
-            "allocated inside a HIP graph capture (some rank's stream is capturing)\n", rank_);
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s: this call runs the padded ring, whose stage cannot be "
+            "allocated inside a HIP graph capture (some rank's stream is capturing)\n", rank_, name);
     return leave(ncclInvalidUsage);
   }
   uint32_t seq = ++call_seq_;
   if (seq == 0) seq = ++call_seq_;
   const char* s0 = static_cast<const char*>(send);
   char* r0 = static_cast<char*>(recv);
-  if (d == PeerBuffers::kRead) {
+  if (d == PeerBuffers::kRead && rows_call) {
+    const void* recv_of[kMaxRanks];
+    uint64_t peer_rdispl[kMaxRanks];
+    for (int q = 0; q < n; ++q) {
+      recv_of[q] = q == rank_ ? (const char*)rrecv : precv[q];
+      peer_rdispl[q] = rows[q].rdispls[rank_];
+    }
+    RowsArgs v;
+    // (an idle rank's stand-in send is never read: its counts are all zero)
+    rows_fill_args(&v, n, esz, rsend, rows_call->nrows, rows_call->rowstride, kidx ? kidx : (const int32_t*)rsend,
+                   sendcounts, sdispls, rows_call->rowcount, recv_of, peer_rdispl);
+    int A = 0;
+    const CollParams p = make_params(2, rsend, rrecv, M, seq, psend, precv, 0, 0, coll, 0, 0, &A);
+    hip_check(launch_rows(dtype, A / geo_.waves, cfg_.threads, p, v, stream), "kernel launch");
+    last_algo_ = 2;
+  } else if (d == PeerBuffers::kRead) {
     VarBlockArgs v;
     memset(&v, 0, sizeof v);
     for (int q = 0; q < n; ++q) {
@@ -1303,19 +1413,29 @@ ncclResult_t Comm::all_to_all_v(const void* send, const size_t* sendcounts, cons
     last_algo_ = 2;
   } else {
     const size_t Mpad = (M + 15) & ~(size_t)15;
-    ensure_stage(2 * (size_t)n * Mpad, stream);
+    ensure_stage(2 * (size_t)n * Mpad + (src_via ? src_extra : 0), stream);
     char* in = stage_;
     char* out = stage_ + (size_t)n * Mpad;
+    if (rows_call && sends) {
+      // (block `rank` of the stage's first half is free: the own block when recv is no device memory)
+      const bool via = sendcounts[rank_] && how(recv) != Reach::kDevice;
+      char* to[kMaxRanks] = {};
+      for (int q = 0; q < n; ++q) to[q] = q == rank_ && !via ? r0 + rdispls[q] * unit : in + (size_t)q * Mpad;
+      pack_rows(to, stage_ + 2 * (size_t)n * Mpad);
+      if (via)
+        hip_check(hipMemcpyAsync(r0 + rdispls[rank_] * unit, to[rank_], sendcounts[rank_] * unit, hipMemcpyDefault, stream),
+                  "own block");
+    }
     for (int q = 0; q < n; ++q)
-      if (q != rank_ && sendcounts[q])
+      if (!rows_call && q != rank_ && sendcounts[q])
         hip_check(hipMemcpyAsync(in + (size_t)q * Mpad, s0 + sdispls[q] * (size_t)esz, sendcounts[q] * (size_t)esz,
                                  hipMemcpyDefault, stream), "pack");
     launch(0, in, out, Mpad, dtype, kSum, stream, seq, true, nullptr, nullptr, 0, 0, kCollAllToAll);
     for (int q = 0; q < n; ++q)
       if (q != rank_ && recvcounts[q])
-        hip_check(hipMemcpyAsync(r0 + rdispls[q] * (size_t)esz, out + (size_t)q * Mpad, recvcounts[q] * (size_t)esz,
+        hip_check(hipMemcpyAsync(r0 + rdispls[q] * unit, out + (size_t)q * Mpad, recvcounts[q] * unit,
                                  hipMemcpyDefault, stream), "unpack");
-    if (sendcounts[rank_])
+    if (!rows_call && sendcounts[rank_])
       hip_check(hipMemcpyAsync(r0 + rdispls[rank_] * (size_t)esz, s0 + sdispls[rank_] * (size_t)esz,
                                sendcounts[rank_] * (size_t)esz, hipMemcpyDefault, stream), "own block");
   }

@@ -127,7 +127,20 @@ class Comm {
   // rank whatever the schedule, then the read schedule (kernels.hip varblock_push) or, where the
   // rendezvous decides against it, the ring's all-to-all on blocks padded to the largest one.
   ncclResult_t all_to_all_v(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
-                            const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream);
+                            const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream) {
+    return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, nullptr);
+  }
+  // The same with the send blocks gathered by row index (mncclAllToAllvRows, mini_nccl_ext.h; counts
+  // and displacements in rows): the block for rank q is the rows rowidx[sdispls[q] + i] of the
+  // nrows x rowstride matrix at `send`, rowcount elements each.  all_to_all_v's call path with the
+  // rules of rowblock.h: kernels.hip rows_push on the read schedule; else rows_pack gathers the blocks
+  // into the padded ring's stage where ncclAllToAllv copies them there.
+  ncclResult_t all_to_all_v_rows(const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                                 const size_t* sendcounts, const size_t* sdispls, void* recv, const size_t* recvcounts,
+                                 const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream) {
+    const RowsCall rows{nrows, rowstride, rowcount, rowidx};
+    return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
+  }
 
   // The halves with per-rank counts (mncclAllGatherv / mncclReduceScatterv, mini_nccl_ext.h; counts and
   // displacements in elements, host arrays of n entries read before the call returns, the same on
@@ -251,6 +264,15 @@ class Comm {
   // (mncclAllGatherv / mncclReduceScatterv pass their collective, op and scalar bits: compared too)
   bool gather_rows(const VarRow& mine, int dtype, VarRow* rows, int coll = kCollAllToAllV, int op = 0,
                    uint64_t scalar = 0);
+  // the one call path of ncclAllToAllv (rows == nullptr: counts and displacements in elements of
+  // `send`) and mncclAllToAllvRows (in rows of the matrix `rows` describes at `send`)
+  struct RowsCall {
+    size_t nrows, rowstride, rowcount;
+    const int32_t* rowidx;
+  };
+  ncclResult_t var_exchange(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
+                            const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream,
+                            const RowsCall* rows);
   // mncclAllGatherv / mncclReduceScatterv: array_buf / counts / displs the side with n blocks (the
   // gather's recv, the scatter's send), one_buf / one_count this rank's one block
   ncclResult_t vhalf(int coll, void* array_buf, const size_t* counts, const size_t* displs, void* one_buf,

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "p2p.h"
+#include "rowblock.h"
 
 namespace mnccl {
 
@@ -125,6 +126,28 @@ struct VarBlockArgs {
 // every rank), p.peer_recv every rank's recv.  By element size (1 / 2 / 4 / 8 from dtype): no arithmetic.
 hipError_t launch_varblock(int dtype, int channels, int threads, const CollParams& p, const VarBlockArgs& v,
                            hipStream_t stream);
+// mncclAllToAllvRows on the read schedule (kernels.hip rows_push): RowsArgs (rowblock.h), a second
+// by-value kernel argument.  p: p.coll kCollAllToAllVRows; the all-to-all's geometry for chunk_bytes =
+// the largest block of the whole matrix in bytes, p.send the matrix, p.peer_recv every rank's recv.
+// By element size (1 / 2 / 4 / 8 from dtype).  Refuses a block longer than the geometry's or not a
+// whole number of rows.
+hipError_t launch_rows(int dtype, int channels, int threads, const CollParams& p, const RowsArgs& v, hipStream_t stream);
+// The same gather into local memory as a plain grid launch (kernels.hip rows_pack): rows
+// rowidx[idx_off[q] + i], i < count[q], of the matrix at src land packed at dst[q], for every q < n.
+struct RowsPackArgs {
+  const char* src;
+  const int32_t* rowidx;
+  uint64_t stride_bytes;  // rowstride * element size
+  uint32_t row_bytes;     // rowcount * element size
+  uint32_t nrows;         // indices outside [0, nrows) give rows of zero bytes
+  char* dst[16];
+  uint64_t idx_off[16];
+  uint64_t count[16];     // rows (0: nothing for q)
+  uint32_t vec_mask;      // bit q: src, stride_bytes, row_bytes and dst[q] are dword-aligned
+  int32_t n;
+  uint32_t lanes_log2_vec, lanes_log2_elem;  // set by the launcher: lanes per row on either path
+};
+hipError_t launch_rows_pack(int dtype, RowsPackArgs a, hipStream_t stream);
 // mncclReduceScatterv / mncclAllGatherv on the read schedule (kernels.hip vhalf_fold / vhalf_push):
 // this rank's block of the array-side buffers, a second by-value kernel argument (CollParams stays
 // byte for byte what it was).  The arrays are the same on every rank, so `base` is the block's byte

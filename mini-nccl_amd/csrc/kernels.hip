@@ -31,6 +31,10 @@
 //  varblock_push  the variable all-to-all (ncclAllToAllv) on the same protocol: exchange_push with a
 //                 length and two offsets per destination, the slices cut for the largest block of
 //                 the whole matrix.  Its fallback is the ring's all-to-all on padded blocks.
+//  rows_push / rows_pack   the variable all-to-all whose blocks are rows of a matrix named by a
+//                 device-side index list (mncclAllToAllvRows): varblock_push's protocol and geometry,
+//                 the gather fused into the push's loads; rows_pack is the same gather as a grid
+//                 kernel into local memory (one rank, and the padded ring's stage).
 //  vhalf_fold / vhalf_push   the halves with per-rank counts (mncclReduceScatterv / mncclAllGatherv)
 //                 on the same protocol: scatter_fold and gather_push with a per-rank base and
 //                 length, the slices cut for the largest block.  Their fallback is the ring's
@@ -1848,6 +1852,230 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) byte_varblock(C
   varblock_body<1>(p, v);
 }
 
+// ---------------------------------------------------------------- the variable all-to-all by rows
+// mncclAllToAllvRows (rows_push): varblock_push whose block for rank q is not a range of send but the
+// rows rowidx[idx_off[q] + i] of a strided matrix, gathered on the way out -- the permutation pass a
+// MoE dispatch otherwise runs first (a read and a write of everything sent, and k packed copies of a
+// top-k token) is the push's own load.  read_half's protocol message for message, the call's geometry
+// the largest block's as there; the blocks are VIRTUAL packed sequences of rows, so slice [a, b) of a
+// block begins and ends inside rows.  rowblock.h has the rule that makes that exact: a row moves as
+// units at fixed places of the row (16-byte vectors from its start, then elements), and a unit
+// belongs to the slice holding its first byte.  Every access stays inside its row: the source by the
+// row's own descriptor (wide rows) or pointer (narrow rows), the destination by the descriptor of the
+// row segment or of the slice plus the one straddling vector.
+//
+// An index outside [0, nrows) -- the host never sees the indices -- gives a row of zero bytes and no
+// access: a wide row's descriptor gets num_records 0, so its loads return 0 (the short-slice loops'
+// trick); a narrow row's lane skips its load.  The index list is read here, at run time: a captured
+// call gathers by whatever the list holds when the graph is replayed.
+//
+// Wide rows (>= kRowsWideVectors vectors, 1 KiB), rows_wide: the wave walks one row segment at a time
+// in batches of V vectors per lane with varblock_push_vec's two register sets -- the next batch's
+// loads, of the next row or the next destination as it may be, leave before this batch is stored.  Up
+// to 64 of the slice's indices arrive in one coalesced load, lane i holding row i's; each row's index
+// is made wave-uniform with readlane for its descriptor and range-checked once; the following 64 are
+// fetched when a batch of indices is begun, a whole batch ahead of their use.
+// Narrow rows, and every element, rows_packed: a pass covers 64 / units rows, lane l serving row
+// l / units, unit l % units with its own index (a 256-byte row keeps 64 lanes busy, not 16); rows of
+// 64 units and more of a kind (the elements of a destination off the vector path) take the wave whole.
+// Own data is loaded non-temporally; the peers' recv -- and the own one, which the own block goes to
+// -- is stored with the sc0 sc1 stores the coherence argument of the file header needs.
+typedef v4u v4u_dw __attribute__((aligned(4)));  // a vector at a dword-aligned address (valid on gfx950)
+
+constexpr int kRowsV = 4;  // 4 KiB per batch: a 2048-element bf16 row is one batch, a 7168-element one 3.5
+
+template <int V>
+__device__ __forceinline__ void rows_wide(const CollParams& p, const RowsArgs& v, uint64_t soff, u64 j0, int lane) {
+  constexpr uint32_t step = 64 * V;
+  const int n = p.n, r = p.rank, first = wave_id().w % (n - 1);
+  const uint32_t rb = v.row_bytes, nv = rb >> 4;
+  auto dest = [&](int k) { return k < n - 1 ? direct_peer(n, r, 1 + (first + k) % (n - 1)) : r; };
+  // the walk's place (wave-uniform but the indices): destination k, row j of it, vector i of the row
+  // segment's nseg; [soff, b) the slice of destination k's block
+  int k = -1;
+  u64 j = 0, b = 0, jb = 0, ioff = 0;
+  uint32_t i = 0, nseg = 0;
+  char* dbase = nullptr;
+  int32_t ic = -1, in = -1;  // lane l: the index of row jb + l, and of row jb + 64 + l
+  rsrc_t src = make_rsrc(p.send, 0), dst = src;
+  auto fetch = [&](u64 base) -> int32_t {
+    const u64 row = base + (u64)lane;
+    return row * rb < b ? v.rowidx[ioff + row] : -1;
+  };
+  auto open_dest = [&]() {  // destination k: false when it has no vector in this slice
+    const int q = dest(k);
+    const u64 len = (v.vec_mask >> q) & 1u ? varblock_len_at(v.bytes[q], p.slice_bytes, soff) : 0;
+    if (len == 0) return false;
+    b = soff + len;
+    j = jb = j0;
+    dbase = (q == r ? p.recv : const_cast<char*>(p.peer_recv[q])) + v.dst_off[q];
+    ioff = v.idx_off[q];
+    ic = fetch(jb);
+    in = fetch(jb + 64);
+    return true;
+  };
+  auto open_row = [&]() {  // row j of destination k: its vectors in this slice, its descriptors
+    if (j - jb >= 64) {
+      jb += 64;
+      ic = in;
+      in = fetch(jb + 64);
+    }
+    const int32_t idx = __builtin_amdgcn_readlane(ic, __builtin_amdgcn_readfirstlane((int)(j - jb)));
+    const bool valid = (uint32_t)idx < v.nrows;  // (negative indices are large as unsigned)
+    uint32_t i0, i1;
+    rows_units(soff, b, j * rb, 0, 16, nv, &i0, &i1);
+    nseg = i1 - i0;
+    i = 0;
+    src = make_rsrc(p.send + (valid ? (u64)(uint32_t)idx * v.stride_bytes : 0) + (u64)i0 * 16, valid ? nseg * 16 : 0u);
+    dst = make_rsrc(dbase + j * rb + (u64)i0 * 16, nseg * 16);
+  };
+  // the next batch: its descriptors and first vector; false after the slice's last
+  auto next = [&](rsrc_t& s, rsrc_t& d, uint32_t& at) {
+    for (;;) {
+      if (k >= 0 && i < nseg) {
+        s = src;
+        d = dst;
+        at = i;
+        i += step;
+        return true;
+      }
+      if (k >= 0 && (j + 1) * rb < b) {
+        ++j;
+      } else {
+        do {
+          if (++k >= n) return false;
+        } while (!open_dest());
+      }
+      open_row();
+    }
+  };
+  auto load = [&](v4u(&x)[V], rsrc_t s, uint32_t at) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) x[u] = ld_nt16(s, (at + (uint32_t)(u * 64 + lane)) * 16);
+  };
+  auto store = [&](v4u(&x)[V], rsrc_t d, uint32_t at) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) st_slot16(d, (at + (uint32_t)(u * 64 + lane)) * 16, x[u]);
+  };
+  rsrc_t s0, d0, s1, d1;
+  uint32_t a0, a1;
+  v4u xa[V], xb[V];
+  if (!next(s0, d0, a0)) return;
+  load(xa, s0, a0);
+  for (;;) {
+    bool more = next(s1, d1, a1);
+    if (more) load(xb, s1, a1);
+    store(xa, d0, a0);
+    if (!more) break;
+    more = next(s0, d0, a0);
+    if (more) load(xa, s0, a0);
+    store(xb, d1, a1);
+    if (!more) break;
+  }
+}
+
+// Units of U bytes (16: vectors; else elements) at row offsets lo + c * U, c < cnt, of the rows of one
+// destination's slice [soff, b): dst covers the slice from soff, up to the vector that straddles b.
+template <int U>
+__device__ __forceinline__ void rows_packed(const CollParams& p, const RowsArgs& v, uint64_t soff, uint64_t b, u64 j0,
+                                            u64 ioff, rsrc_t dst, uint32_t lo, uint32_t cnt, int lane) {
+  const uint32_t rb = v.row_bytes;
+  // this lane's unit c of `row`, whose index is idx, if the slice holds the unit's first byte
+  auto move = [&](u64 row, uint32_t c, int32_t idx) {
+    const u64 at = row * rb + lo + (u64)c * U;
+    if (at < soff || at >= b) return;
+    const bool valid = (uint32_t)idx < v.nrows;
+    const char* from = p.send + (u64)(uint32_t)idx * v.stride_bytes + lo + (u64)c * U;
+    const uint32_t to = (uint32_t)(at - soff);
+    if constexpr (U == 16) {
+      v4u x = {0u, 0u, 0u, 0u};
+      if (valid) x = __builtin_nontemporal_load(reinterpret_cast<const v4u_dw*>(from));
+      st_slot16(dst, to, x);
+    } else {
+      typename Scal<U>::U x = 0;
+      if (valid) x = __builtin_nontemporal_load(reinterpret_cast<const typename Scal<U>::U*>(from));
+      Scal<U>::st(dst, to, x);
+    }
+  };
+  if (cnt >= 64) {
+    for (u64 row = j0; row * rb < b; ++row) {
+      uint32_t c0, c1;
+      rows_units(soff, b, row * rb, lo, U, cnt, &c0, &c1);
+      const int32_t idx = v.rowidx[ioff + row];  // once per row: one address for the wave, a broadcast
+      for (uint32_t c = c0 + (uint32_t)lane; c < c1; c += 64) move(row, c, idx);
+    }
+  } else {
+    const uint32_t per = 64 / cnt, lr = (uint32_t)lane / cnt, lc = (uint32_t)lane % cnt;
+    if (lr >= per) return;  // (nothing below is a wave operation)
+    for (u64 row = j0 + lr; row * rb < b; row += per) move(row, lc, v.rowidx[ioff + row]);
+  }
+}
+
+// slice at byte `soff` of every block: the vector destinations' whole vectors, then the elements
+template <int ESZ>
+__device__ __forceinline__ void rows_slice(const CollParams& p, const RowsArgs& v, uint64_t soff, int lane) {
+  const int n = p.n, r = p.rank;
+  const uint32_t rb = v.row_bytes, nv = rb >> 4;
+  const u64 j0 = soff / rb;  // the slice's first row: the same for every destination
+  if (v.vec_mask && nv >= kRowsWideVectors) rows_wide<kRowsV>(p, v, soff, j0, lane);
+  for (int k = 1; k <= n; ++k) {
+    const int q = direct_peer(n, r, k);  // k == n: this rank itself
+    const u64 len = varblock_len_at(v.bytes[q], p.slice_bytes, soff);
+    if (len == 0) continue;
+    const bool vec = (v.vec_mask >> q) & 1u;
+    // the slice's part of the block, and the rest of the vector that may straddle its end
+    const u64 rest = v.bytes[q] - soff;
+    const rsrc_t dst = make_rsrc((q == r ? p.recv : const_cast<char*>(p.peer_recv[q])) + v.dst_off[q] + soff,
+                                 (uint32_t)(rest < len + 16 ? rest : len + 16));
+    if (vec && nv > 0 && nv < kRowsWideVectors) rows_packed<16>(p, v, soff, soff + len, j0, v.idx_off[q], dst, 0, nv, lane);
+    const uint32_t lo = vec ? nv * 16 : 0u;
+    if (lo < rb) rows_packed<ESZ>(p, v, soff, soff + len, j0, v.idx_off[q], dst, lo, (rb - lo) / ESZ, lane);
+  }
+}
+
+// No arithmetic, so by element size only; the path is chosen per destination at run time.
+template <int ESZ>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) rows_push(CollParams p, RowsArgs v) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half(p, s_tx, s_rx, [&p, &v](u64 coff, uint32_t, int lane) {
+    rows_slice<ESZ>(p, v, coff - (u64)p.rank * p.chunk_bytes, lane);
+  });
+}
+
+// The same gather as a plain grid kernel, into local memory: mncclAllToAllvRows on one rank, and the
+// pack of its padded ring fallback (block q into the stage at q * Mpad, the own block into recv).
+// blockIdx.y is the destination; 2^lanes lanes share a row -- the power of two that a row's units
+// fill, the host's figure for the destination's own path (vectors or elements: a launch may mix
+// them) -- so narrow rows keep the lanes busy here too.  Same units, same zero rule.
+template <int ESZ>
+__global__ void __launch_bounds__(256) rows_pack(RowsPackArgs a) {
+  const int q = blockIdx.y;
+  const u64 count = a.count[q];
+  if (count == 0) return;
+  const bool vec = (a.vec_mask >> q) & 1u;
+  const uint32_t lanes = vec ? a.lanes_log2_vec : a.lanes_log2_elem;
+  const uint32_t rb = a.row_bytes, nv = vec ? rb >> 4 : 0u, g = 1u << lanes;
+  const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x, per = ((u64)gridDim.x * blockDim.x) >> lanes;
+  const uint32_t l = (uint32_t)t & (g - 1);
+  typedef typename Scal<ESZ>::U E;
+  for (u64 row = t >> lanes; row < count; row += per) {
+    const int32_t idx = a.rowidx[a.idx_off[q] + row];
+    const bool valid = (uint32_t)idx < a.nrows;
+    const char* from = a.src + (u64)(uint32_t)idx * a.stride_bytes;
+    char* to = a.dst[q] + row * rb;
+    for (uint32_t c = l; c < nv; c += g) {
+      v4u x = {0u, 0u, 0u, 0u};
+      if (valid) x = __builtin_nontemporal_load(reinterpret_cast<const v4u_dw*>(from + (u64)c * 16));
+      *reinterpret_cast<v4u_dw*>(to + (u64)c * 16) = x;
+    }
+    for (uint32_t o = nv * 16 + l * ESZ; o < rb; o += g * ESZ) {
+      E x = 0;
+      if (valid) x = *reinterpret_cast<const E*>(from + o);
+      *reinterpret_cast<E*>(to + o) = x;
+    }
+  }
+}
+
 // ---------------------------------------------------------------- point to point
 // ncclSend / ncclRecv (p2p_kernel): a send is the sender's half of one ring hop to an arbitrary
 // peer, a recv the receiver's half, on the scratch protocol of the file header -- the peer's region
@@ -2704,6 +2932,45 @@ hipError_t launch_varblock(int dtype, int C, int nt, const CollParams& p, const 
   }
   return for_elem_size(dtype, [&](auto e) {
     hipLaunchKernelGGL(varblock_push<decltype(e)::value>, dim3(C), dim3(nt), 0, st, p, v);
+    return hipGetLastError();
+  });
+}
+
+// (element size 1, fp8, is an instantiation like the others here: the path is chosen at run time)
+template <typename F>
+static hipError_t for_rows_size(int dtype, F&& f) {
+  return dtype_size(dtype) == 1 ? f(IntTag<1>{}) : for_elem_size(dtype, f);
+}
+
+hipError_t launch_rows(int dtype, int C, int nt, const CollParams& p, const RowsArgs& v, hipStream_t st) {
+  // (a rank whose counts are all zero passes a stand-in list, Comm::var_exchange: never read, but not NULL)
+  if (p.coll != kCollAllToAllVRows || p.n < 2 || v.row_bytes == 0 || !v.rowidx) return hipErrorInvalidValue;
+  for (int q = 0; q < p.n; ++q)
+    if (v.bytes[q] > p.chunk_bytes || v.bytes[q] % v.row_bytes) return hipErrorInvalidValue;
+  return for_rows_size(dtype, [&](auto e) {
+    hipLaunchKernelGGL(rows_push<decltype(e)::value>, dim3(C), dim3(nt), 0, st, p, v);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_rows_pack(int dtype, RowsPackArgs a, hipStream_t st) {
+  if (a.n < 1 || a.n > kMaxRanks || a.row_bytes == 0 || !a.rowidx) return hipErrorInvalidValue;
+  u64 most = 0;
+  for (int q = 0; q < a.n; ++q) most = a.count[q] > most ? a.count[q] : most;
+  if (most == 0) return hipSuccess;
+  // the lanes of a row: the power of two its units fill, up to a wave -- vectors (and a tail) for the
+  // destinations on the 16-byte path, elements for the others; the grid is sized for the wider of the two
+  auto lanes_for = [](uint32_t units) {
+    uint32_t l = 0;
+    while (l < 6 && (1u << l) < units) ++l;
+    return l;
+  };
+  a.lanes_log2_vec = lanes_for((a.row_bytes + 15) / 16);
+  a.lanes_log2_elem = lanes_for(a.row_bytes / (uint32_t)dtype_size(dtype));
+  const u64 rows_per_block = 256u >> a.lanes_log2_elem, want = (most + rows_per_block - 1) / rows_per_block;
+  const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);  // the rest by the grid's stride
+  return for_rows_size(dtype, [&](auto e) {
+    hipLaunchKernelGGL(rows_pack<decltype(e)::value>, dim3(blocks, (unsigned)a.n), dim3(256), 0, st, a);
     return hipGetLastError();
   });
 }

@@ -646,7 +646,8 @@ PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, 
   // (mncclAllGatherv / mncclReduceScatterv: the rows must be equal instead, vhalves.h; ranks that
   // differ in the collective differ in `form` above)
   if (row && rows_out && !mismatch)
-    mismatch = (row->flags & kVarSameRows ? vhalf_rows_differ(nranks_, rows_out) : varblock_matrix_mismatch(nranks_, rows_out)) != 0;
+    mismatch = (row->flags & kVarSameRows ? vhalf_rows_differ(nranks_, rows_out) : varblock_matrix_mismatch(nranks_, rows_out)) != 0 ||
+               ((row->flags & kVarRows) && varblock_rowcounts_differ(nranks_, rows_out));  // (mncclAllToAllvRows: the row's length too)
   const Decision d = mismatch ? kMismatch : all ? kRead : kFallback;
   *vec_all = aligned;
   if (d != kRead) return d;

@@ -164,7 +164,10 @@ enum Coll : int {
   // the halves with per-rank counts (mncclAllGatherv / mncclReduceScatterv): like kCollAllToAllV they
   // have no ring table of their own -- off the read schedule they run the ring's halves on blocks
   // padded to the largest one (Comm::vhalf)
-  kCollAllGatherV = 9, kCollReduceScatterV = 10
+  kCollAllGatherV = 9, kCollReduceScatterV = 10,
+  // mncclAllToAllvRows: kCollAllToAllV with the send blocks gathered by row index (rowblock.h); its
+  // fallback is kCollAllToAllV's padded ring behind a gather kernel
+  kCollAllToAllVRows = 11
 };
 
 // r, root: gather and scatter only (their op count depends on the rank's place in the chain; the

@@ -1512,6 +1512,84 @@ uint64_t mnccl_varblock_len(uint64_t block_bytes, uint64_t slice_bytes, uint64_t
   return mnccl::varblock_len(block_bytes, slice_bytes, s);
 }
 
+// csrc/rowblock.h, the host-side rules of mncclAllToAllvRows, for the CPU suite: one rank's local checks
+// (a RowsLocal verdict; the buffers are only compared, never dereferenced), the matrix's byte extent,
+// the slice rule, and the per-destination argument block (out: n bytes[], n dst_off[], then vec_mask).
+int mnccl_sim_rows_check_local(int n, int esz, const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                               const size_t* sendcounts, const size_t* sdispls, const void* recv, const size_t* recvcounts,
+                               const size_t* rdispls, size_t rowcount) {
+  if (n < 1 || n > mnccl::kVarMaxRanks || esz < 1) return -2;
+  return mnccl::rows_check_local(n, esz, send, nrows, rowstride, rowidx, sendcounts, sdispls, recv, recvcounts, rdispls,
+                                 rowcount);
+}
+uint64_t mnccl_sim_rows_extent(uint64_t nrows, uint64_t rowstride, uint64_t rowcount, int esz) {
+  return mnccl::rows_extent_bytes(nrows, rowstride, rowcount, esz);
+}
+void mnccl_sim_rows_units(uint64_t a, uint64_t b, uint64_t row_start, uint32_t lo, uint32_t u, uint32_t cnt, uint32_t* out) {
+  mnccl::rows_units(a, b, row_start, lo, u, cnt, &out[0], &out[1]);
+}
+int mnccl_sim_rows_args(int n, int esz, uint64_t send_addr, size_t nrows, size_t rowstride, const size_t* sendcounts,
+                        const size_t* sdispls, size_t rowcount, const uint64_t* recv_addr, const uint64_t* peer_rdispl,
+                        uint64_t* out) {
+  if (n < 1 || n > mnccl::kVarMaxRanks) return -2;
+  const void* recv_of[mnccl::kVarMaxRanks];
+  for (int q = 0; q < n; ++q) recv_of[q] = (const void*)(uintptr_t)recv_addr[q];
+  mnccl::RowsArgs v;
+  mnccl::rows_fill_args(&v, n, esz, (const void*)(uintptr_t)send_addr, nrows, rowstride, nullptr, sendcounts, sdispls,
+                        rowcount, recv_of, peer_rdispl);
+  for (int q = 0; q < n; ++q) {
+    out[q] = v.bytes[q];
+    out[n + q] = v.dst_off[q];
+  }
+  out[2 * n] = v.vec_mask;
+  return 0;
+}
+
+// kernels.hip rows_push as the slices walk it, on host memory: rank r's matrix send[r] (nrows[r] x
+// rowstride[r] elements) and list rowidx[r]; counts / sdispls / rdispls n x n, row r what rank r
+// passed (counts[r * n + q] rows from r to q; rdispls[q * n + r] where they land in recv[q]).  The
+// 16-byte path is chosen per destination from send_addr / recv_addr, the addresses the buffers stand
+// for.  Every slice of the largest-block geometry, every destination, every row's units by
+// rows_units.  0; -2 bad arguments; -3 when some byte of a block is not stored exactly once.
+int mnccl_sim_rows_exchange(int n, int esz, uint64_t slice_bytes, const uint8_t* const* send, const uint64_t* nrows,
+                            const uint64_t* rowstride, const int32_t* const* rowidx, const uint64_t* counts,
+                            const uint64_t* sdispls, uint8_t* const* recv, const uint64_t* rdispls, uint64_t rowcount,
+                            const uint64_t* send_addr, const uint64_t* recv_addr) {
+  if (n < 1 || n > mnccl::kVarMaxRanks || esz < 1 || slice_bytes == 0 || rowcount == 0) return -2;
+  const uint64_t rb = rowcount * (uint64_t)esz;
+  uint64_t M = 0;
+  for (int i = 0; i < n * n; ++i) M = counts[i] * rb > M ? counts[i] * rb : M;
+  for (int r = 0; r < n; ++r)
+    for (int q = 0; q < n; ++q) {
+      const uint64_t bytes = counts[r * n + q] * rb, stride = rowstride[r] * (uint64_t)esz;
+      uint8_t* const to = recv[q] + rdispls[q * n + r] * rb;
+      const bool vec = bytes && mnccl::rows_vec_ok((const void*)(uintptr_t)send_addr[r], stride, rb,
+                                                   recv_addr[q] + rdispls[q * n + r] * rb);
+      const uint32_t nv = vec ? (uint32_t)(rb >> 4) : 0u, lo = nv * 16;
+      std::vector<uint8_t> stored((size_t)bytes, 0);
+      auto unit = [&](uint64_t j, uint32_t off, uint32_t len) {
+        const int32_t idx = rowidx[r][sdispls[r * n + q] + j];
+        for (uint32_t i = 0; i < len; ++i) {
+          to[j * rb + off + i] = (uint64_t)(uint32_t)idx < nrows[r] && idx >= 0 ? send[r][(uint64_t)idx * stride + off + i] : 0;
+          ++stored[(size_t)(j * rb + off + i)];
+        }
+      };
+      for (uint64_t a = 0; a < M; a += slice_bytes) {
+        const uint64_t b = a + mnccl::varblock_len_at(bytes, slice_bytes, a);
+        for (uint64_t j = a / rb; b > a && j * rb < b; ++j) {
+          uint32_t i0, i1;
+          mnccl::rows_units(a, b, j * rb, 0, 16, nv, &i0, &i1);
+          for (uint32_t i = i0; i < i1; ++i) unit(j, i * 16, 16);
+          mnccl::rows_units(a, b, j * rb, lo, (uint32_t)esz, (uint32_t)((rb - lo) / (uint64_t)esz), &i0, &i1);
+          for (uint32_t i = i0; i < i1; ++i) unit(j, lo + i * (uint32_t)esz, (uint32_t)esz);
+        }
+      }
+      for (uint8_t c : stored)
+        if (c != 1) return -3;
+    }
+  return 0;
+}
+
 // csrc/vhalves.h, the host-side rules of mncclAllGatherv / mncclReduceScatterv, and schedule.h's length
 // rule for them.  mnccl_vhalf_rows_differ: counts / displs are n x n, row r what rank r passed.
 int mnccl_vhalf_check_local(int n, int rank, int esz, const void* array_buf, const size_t* counts, const size_t* displs,

@@ -27,7 +27,10 @@ enum : uint32_t {
   kVarCapturing = 1u,  // this rank's stream is being captured into a graph
   // the row of an mncclAllGatherv / mncclReduceScatterv call (vhalves.h): counts in sendcounts, displs
   // in rdispls; the ranks' rows must be EQUAL, where ncclAllToAllv's must be each other's transpose
-  kVarSameRows = 2u
+  kVarSameRows = 2u,
+  // the row of an mncclAllToAllvRows call (rowblock.h): counts and displacements in matrix rows, the
+  // row's length in elements in `pad` -- which the ranks must pass alike (varblock_rowcounts_differ)
+  kVarRows = 4u
 };
 
 // The local checks' verdicts, in the order they are made
@@ -84,6 +87,13 @@ inline int varblock_matrix_mismatch(int n, const VarRow* rows) {
     for (int q = 0; q < n; ++q)
       if (rows[r].sendcounts[q] != rows[q].recvcounts[r]) return 1 + r * n + q;
   return 0;
+}
+
+// mncclAllToAllvRows (rows with kVarRows): some rank passed another rowcount
+inline bool varblock_rowcounts_differ(int n, const VarRow* rows) {
+  for (int r = 1; r < n; ++r)
+    if (rows[r].pad != rows[0].pad) return true;
+  return false;
 }
 
 // The largest block of the matrix in elements: the call's geometry follows it (the same on every rank)

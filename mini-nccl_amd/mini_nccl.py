@@ -97,6 +97,8 @@ SIGNATURES = {
     "ncclAllToAll": (_I, [_VP, _VP, _SZ, _I, _VP, _VP]),
     "ncclAllToAllv": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ),
                            _I, _VP, _VP]),
+    "mncclAllToAllvRows": (_I, [_VP, _SZ, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, ctypes.POINTER(_SZ),
+                                ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllGatherv": (_I, [_VP, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _I, _VP, _VP]),
     "mncclReduceScatterv": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclGather": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
@@ -291,6 +293,17 @@ class Comm:
         arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
         return load().ncclAllToAllv(send_ptr, arrays[0], arrays[1], recv_ptr, arrays[2], arrays[3], dtype, self.handle,
                                     stream)
+
+    def all_to_all_v_rows(self, send_ptr, nrows, rowstride, rowidx_ptr, sendcounts, sdispls, recv_ptr, recvcounts, rdispls,
+                          rowcount, dtype=ncclFloat, stream=0):
+        """mncclAllToAllvRows: all_to_all_v whose block for rank q is the rows rowidx[sdispls[q] + i],
+        i < sendcounts[q], of the nrows x rowstride matrix at send_ptr, `rowcount` elements of each;
+        rowidx_ptr is a DEVICE array of int32 read when the call runs (an index outside [0, nrows)
+        delivers a row of zero bytes).  Counts and displacements are in rows on both sides; recv is
+        dense, rows of rowcount elements.  Returns the ncclResult_t."""
+        arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
+        return load().mncclAllToAllvRows(send_ptr, nrows, rowstride, rowidx_ptr, arrays[0], arrays[1], recv_ptr, arrays[2],
+                                         arrays[3], rowcount, dtype, self.handle, stream)
 
     def all_gather_v(self, send_ptr, sendcount, recv_ptr, recvcounts, rdispls, dtype=ncclFloat, stream=0):
         """mncclAllGatherv: rank q's `sendcount` elements of send end up at elements [rdispls[q],
