@@ -39,6 +39,8 @@
  *                        number of tokens, possibly none).
  *   mncclAllToAllvRows   ncclAllToAllv whose send blocks are rows of a matrix picked by a device-side
  *                        index list (a MoE router's output as it is: no permutation pass in front).
+ *   mncclAllToAllvCombine  the way back: the token owner pulls the top-k rows of each token out of the
+ *                        experts' send buffers and folds them by gate weight (no packed recv, no atomics).
  *
  * and the all-reduce's halves with per-rank counts, which neither NCCL nor RCCL has (callers there
  * compose them from broadcasts / reduces inside one group, which this library does not take), under
@@ -451,6 +453,65 @@ ncclResult_t mncclAllToAllvRows(const void* sendbuff, size_t nrows, size_t rowst
                                 const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                                 const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
                                 ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
+
+/* The way back of the same layer: ncclAllToAllv whose packed recv is never built, because the token
+ * owner folds the up to top-k returned rows of each token, each times its gate weight, into one
+ * output row -- one pass over the bytes, deterministic, no atomics.  Detected by symbol
+ * (MNCCL_VERSION stays 600).  It is called with mncclAllToAllvRows' two pairs of count arrays
+ * swapped, and slotidx[t * topk + k] is the position in that call's rowidx of token t's k-th copy.
+ *
+ * The send side is dense, the layout mncclAllToAllvRows delivered: the block for rank q is rows
+ * [sdispls[q], sdispls[q] + sendcounts[q]) of sendbuff, rows of `rowcount` elements with no stride.  On
+ * rank r the VIRTUAL packed sequence P has P[rdispls[q] + i] = row sdispls_q[r] + i of rank q's
+ * sendbuff, i < recvcounts[q]: what ncclAllToAllv would deliver.  recvbuff is a matrix of `nrows` rows,
+ * row t at element t * rowstride (rowstride >= rowcount); its first rowcount elements are written,
+ * the elements between rows never.  slotidx (int32) and weights (float, or NULL: every weight 1) hold
+ * nrows * topk entries in DEVICE memory of this rank's GPU or pinned host memory; the kernel reads them
+ * when the call runs, the host never: a captured call reads them at replay, so a router may rewrite
+ * both between replays while the counts stay what they were.  Counts and displacements are in rows,
+ * host arrays of nranks entries read before the call returns.  nrows and topk are each rank's own.
+ *
+ * Result, bit for bit on every schedule.  For row t, element e: acc = +0.0f; for k = 0 .. topk-1 in
+ * that order, j = slotidx[t * topk + k]: when j lies in a non-empty block [rdispls[q], rdispls[q] +
+ * recvcounts[q]), acc = acc + round_f32(weights[t * topk + k] * float(P[j][e])) -- one IEEE single
+ * multiply and one IEEE single add, never fused -- and otherwise (negative, beyond or between the
+ * blocks) the slot contributes nothing whatever its weight holds and causes no access; y[t][e] is acc
+ * rounded once to the datatype, to nearest even.  Every row t < nrows is written; a token with no
+ * valid slot gets zeros.  ncclFloat, ncclFloat16 and ncclBfloat16.
+ *
+ * Checks, in mncclAllToAllvRows' order (no exception crosses the boundary):
+ *  1. a NULL comm or a NULL count / displacement array: ncclInvalidArgument;
+ *  2. a group is open: ncclInvalidUsage, the group stays clean;
+ *  3. any other datatype: ncclInternalError, before the communicator is read;
+ *  4. with the communicator, each ncclInvalidArgument with nothing launched or negotiated and the
+ *     communicator still usable: topk outside [1, 16]; rowcount == 0 with a non-zero count or nrows;
+ *     rowstride < rowcount; nrows * topk > INT32_MAX; a NULL sendbuff with a non-zero sendcount; a NULL
+ *     recvbuff or slotidx with nrows > 0; a size or an address that overflows (a row of 2 GiB or more
+ *     counts as that); two non-empty blocks of the virtual sequence that overlap; the recv matrix's byte
+ *     extent overlapping a non-empty send block, slotidx or weights; a slotidx or weights that is neither
+ *     device memory of this GPU nor pinned host memory;
+ *  5. after the per-call rendezvous, sendcounts_r[q] != recvcounts_q[r] for any pair, or ranks that
+ *     differ in the collective, the datatype, rowcount or the schedule choice: ncclInvalidUsage on every
+ *     rank alike, nothing launched, the communicator still usable;
+ *  6. a rank with nrows == 0 still serves its sendbuff, a rank with no send counts still pulls;
+ *  7. every count on every rank 0: the rows are zero-filled by the local kernel alone;
+ *  8. nranks == 1: the local kernel alone, P the own block.
+ * Blocking mode, stream ordering, sticky errors and the watchdog as ncclAllToAllv.
+ *
+ * Schedules.  Where ncclAllToAllv would run the read schedule: a persistent kernel in its protocol that
+ * loads each source row out of the peer's sendbuff where the slot points and stores the folded row --
+ * every returned row is read once and every output row written once (a count from the schedule; the
+ * composed form writes and reads a packed buffer of everything returned besides).  The geometry is
+ * the longest output matrix of any rank.  16-byte vectors when every peer's sendbuff, recvbuff, and
+ * rowstride and rowcount in bytes are dword-aligned; each row's last bytes % 16 bytes, and every other
+ * call, go element by element (last_algo: mncclAlgoRead).  Otherwise (a forced ring, host data
+ * buffers, a topology that refuses read) ncclAllToAllv's padded ring delivers the packed sequence into
+ * the device stage and the local kernel folds out of it, with the ring's cost and its refusal under
+ * capture (last_algo: mncclAlgoRing). */
+ncclResult_t mncclAllToAllvCombine(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                                   size_t nrows, size_t rowstride, const int32_t* slotidx, const float* weights, int topk,
+                                   const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
+                                   ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
 
 /* The all-reduce's halves with per-rank counts.  Neither NCCL nor RCCL has them, so they carry the
  * library's prefix and MPI's argument order (MPI_Allgatherv / MPI_Reduce_scatter with displacements).

@@ -1442,6 +1442,235 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
   return end_call(scope, stream, seq);
 }
 
+// mncclAllToAllvCombine.  var_exchange's call path with the rules of combine.h: the caller's local
+// errors first (nothing launched, nothing negotiated); then every rank's counts reach every rank, with
+// two things ncclAllToAllv keeps private -- the rank's SEND displacements (the puller computes where
+// its rows lie in the peer's send) and its output rows, because the read schedule's geometry is the
+// longest output matrix of any rank, M = max(nrows) * row bytes, the same everywhere; a rank whose own
+// matrix is shorter skips the bodies of the slices past it (read_half<VAR>).  On the read schedule:
+// kernels.hip combine_fold.  Else ncclAllToAllv's padded ring delivers the virtual packed sequence into
+// the stage, behind the ring's 2 n Mpad bytes, and combine_local folds out of it; a pageable recv gets
+// its rows through one more dense stage region and a strided copy.  Every count zero on every rank:
+// combine_local alone zero-fills (no protocol: every rank sees the same matrix); one rank: the same
+// kernel on the own block.  A rank with no output rows still serves its send; one with no send counts
+// still pulls.
+ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv, size_t nrows,
+                           size_t rowstride, const int32_t* slotidx, const float* weights, int topk,
+                           const size_t* recvcounts, const size_t* rdispls, size_t rowcount, int dtype,
+                           hipStream_t stream) {
+  if (sticky_ != ncclSuccess) return sticky_;
+  if (check_status() != ncclSuccess) return sticky_;
+  const int n = nranks_, esz = dtype_size(dtype), coll = kCollAllToAllVCombine;
+  const char* const name = "mncclAllToAllvCombine";
+  const int local = combine_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights, topk,
+                                        recvcounts, rdispls, rowcount);
+  if (local != kCombineOk) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s: %s\n", rank_, name,
+            local == kCombineTopk           ? "topk is outside [1, 16]"
+            : local == kCombineZeroRow      ? "rowcount is 0 with a non-zero count or nrows"
+            : local == kCombineStride       ? "rowstride is smaller than rowcount"
+            : local == kCombineTooManySlots ? "nrows * topk is beyond what an int32 can count"
+            : local == kCombineNullBuffer   ? "a NULL sendbuff with a non-zero count, or a NULL recvbuff / slotidx with rows"
+            : local == kCombineOverflow     ? "a displacement plus count, a byte size or an address overflows size_t (or a row "
+                                              "is 2 GiB or longer)"
+            : local == kCombineRecvOverlap  ? "two blocks of the virtual sequence overlap"
+                                            : "the recv matrix overlaps a send block, slotidx or weights");
+    return ncclInvalidArgument;
+  }
+  const size_t rb = rowcount * (size_t)esz;
+  auto how = [&](const void* p) {
+    const void* k = p;
+    bool l = false;
+    return reach(p, &k, &l);
+  };
+  // the kernels read the lists themselves: device memory of this GPU, or pinned host memory
+  const int32_t* kslot = slotidx;
+  const float* kw = weights;
+  for (int i = 0; i < 2 && nrows; ++i) {
+    const void* list = i ? (const void*)weights : (const void*)slotidx;
+    if (!list) continue;
+    const void* kp = list;
+    bool local_l = false;
+    const Reach r = reach(list, &kp, &local_l);
+    if (!(r == Reach::kMapped || (r == Reach::kDevice && local_l))) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: %s is neither device memory of this GPU nor pinned host memory\n", rank_, name,
+              i ? "weights" : "slotidx");
+      return ncclInvalidArgument;
+    }
+    if (i) kw = static_cast<const float*>(kp);
+    else kslot = static_cast<const int32_t*>(kp);
+  }
+  // combine_local out of `packed` (block q at row disp[q] of it), into recv where a kernel can address
+  // it, else into a dense region at stage_ + out_at that a strided copy empties; the stage is sized by
+  // the caller
+  const bool out_via = nrows && how(recv) == Reach::kStaged;
+  const size_t out_bytes = out_via ? nrows * rb : 0;
+  auto fold_local = [&](const char* packed, const size_t* disp, size_t out_at) {
+    const void* out = recv;
+    bool l = false;
+    if (nrows) (void)reach(recv, &out, &l);
+    const void* send_of[kMaxRanks];
+    uint64_t at[kMaxRanks];
+    for (int q = 0; q < n; ++q) {
+      send_of[q] = packed;
+      at[q] = disp[q];
+    }
+    CombineArgs v;
+    combine_fill_args(&v, n, esz, out_via ? stage_ + out_at : out, nrows, out_via ? rowcount : rowstride, kslot, kw, topk,
+                      recvcounts, rdispls, rowcount, send_of, at);
+    hip_check(launch_combine_local(dtype, n, v, packed, out_via ? stage_ + out_at : const_cast<void*>(out), stream),
+              "kernel launch");
+    if (out_via)
+      hip_check(hipMemcpy2DAsync(recv, rowstride * (size_t)esz, stage_ + out_at, rb, rb, nrows, hipMemcpyDefault, stream),
+                "rows out");
+  };
+  const size_t none[kMaxRanks] = {};
+  if (n == 1) {
+    if (sendcounts[0] != recvcounts[0]) {
+      fprintf(stderr, "[Mini-NCCL] rank 0: %s: sendcounts[0] != recvcounts[0]\n", name);
+      return ncclInvalidUsage;
+    }
+    if (nrows == 0) return ncclSuccess;
+    const CallScope scope = begin_call(stream);
+    const size_t own = sendcounts[0] * rb, own_pad = (own + 15) & ~(size_t)15;
+    const void* src = send;
+    bool l = false;
+    const bool in_via = own && reach(send, &src, &l) == Reach::kStaged;
+    if (in_via || out_via) ensure_stage((in_via ? own_pad : 0) + out_bytes, stream);
+    if (in_via) hip_check(hipMemcpyAsync(stage_, (const char*)send + sdispls[0] * rb, own, hipMemcpyDefault, stream), "stage in");
+    fold_local(in_via ? stage_ : static_cast<const char*>(src), in_via ? none : sdispls, in_via ? own_pad : 0);
+    return end_call(scope, stream, 0);
+  }
+  const CallScope scope = begin_call(stream);
+  auto leave = [&](ncclResult_t rc) {
+    if (scope.cur_dev != device_) hipSetDevice(scope.cur_dev);
+    return rc;
+  };
+  VarRow mine, rows[kMaxRanks];
+  memset(&mine, 0, sizeof mine);
+  for (int q = 0; q < n; ++q) {
+    mine.sendcounts[q] = sendcounts[q];
+    mine.recvcounts[q] = recvcounts[q];
+    mine.rdispls[q] = sendcounts[q] ? sdispls[q] : 0;  // (kVarCombine: the SEND displacements travel)
+  }
+  mine.flags = (scope.capturing() ? (uint32_t)kVarCapturing : 0u) | (uint32_t)kVarCombine;
+  mine.pad = (uint32_t)rowcount;  // (below 2^31: combine_check_local)
+  mine.nrows = nrows;
+
+  PeerBuffers::Decision d = PeerBuffers::kFallback;
+  const char* psend[kMaxRanks] = {};
+  const char* precv[kMaxRanks] = {};
+  // a buffer this rank does not use (it may be NULL) is stood in for by the other one; a rank with
+  // neither by the communicator's stub
+  const void* rsend = send ? send : recv;
+  void* rrecv = recv ? recv : const_cast<void*>(send);
+  if (pbuf_.available()) {
+    const bool read_ok = ((algo_ == 2 || algo_ == 4) && (!auto_ || topo_read_)) || (algo_ == 3 && topo_read_);
+    if (!rsend && read_ok) {
+      if (!var_stub_ && hipMalloc((void**)&var_stub_, 256) != hipSuccess) {
+        (void)hipGetLastError();
+        var_stub_ = nullptr;
+      }
+      rsend = rrecv = var_stub_;
+    }
+    bool eligible = false;
+    if (read_ok && rsend) {
+      pbuf_.reap(rsend, rrecv);
+      bool local_s = false, local_r = false;
+      const void* ks = rsend;
+      const void* kr = rrecv;
+      const bool dev_s = pbuf_.known(rsend) ? (local_s = true) : reach(rsend, &ks, &local_s) == Reach::kDevice;
+      const bool dev_r = pbuf_.known(rrecv) ? (local_r = true) : reach(rrecv, &kr, &local_r) == Reach::kDevice;
+      eligible = dev_s && dev_r && local_s && local_r;
+    }
+    bool vec_all = false;
+    try {
+      d = pbuf_.negotiate(rsend, rrecv, eligible, 0, dtype, 0, cfg_.timeout_ms / 1000.0 + 2.0,
+                          [this] { wait_previous_call(); }, psend, precv, &vec_all, (auto_ ? 0xff : algo_) | coll << 8, &mine,
+                          rows);
+    } catch (const PeerGaveUp& e) {
+      return rendezvous_failed(e, true, scope.cur_dev);
+    } catch (const std::exception& e) {
+      return rendezvous_failed(e, false, scope.cur_dev);
+    }
+    if (d == PeerBuffers::kWindowPeer) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: a peer ran this call on registered windows where this rank called %s; "
+              "communicator is no longer usable\n", rank_, name);
+      sticky_ = ncclInvalidUsage;
+      abort_peers();
+      return leave(sticky_);
+    }
+    if (d == PeerBuffers::kMismatch) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: some rank's sendcounts[q] differs from rank q's recvcounts for it, or the "
+              "ranks called different collectives / datatypes / rowcounts / schedules (mncclCommSetAlgo)\n", rank_, name);
+      return leave(ncclInvalidUsage);
+    }
+  } else if (!gather_rows(mine, dtype, rows, coll) || varblock_matrix_mismatch(n, rows) != 0 ||
+             varblock_rowcounts_differ(n, rows)) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s: some rank's sendcounts[q] differs from rank q's recvcounts for it, or the "
+            "ranks passed different datatypes / rowcounts\n", rank_, name);
+    return leave(ncclInvalidUsage);
+  }
+  const size_t M = (size_t)combine_max_rows(n, rows) * rb;  // the longest output: the same everywhere
+  if (M == 0) return leave(ncclSuccess);                     // nobody has a row to write
+  const size_t Mb = (size_t)varblock_max_count(n, rows) * rb;  // the largest block
+  if (Mb == 0) {
+    // nobody sends anything: the rows are zero-filled by the local kernel alone, no protocol
+    if (nrows == 0) return leave(ncclSuccess);
+    if (out_via) ensure_stage(out_bytes, stream);
+    fold_local(nullptr, none, 0);
+    return end_call(scope, stream, 0);
+  }
+  if (d != PeerBuffers::kRead && varblock_any_capturing(n, rows)) {
+    fprintf(stderr, "[Mini-NCCL] rank %d: %s: this call runs the padded ring, whose stage cannot be allocated inside a "
+            "HIP graph capture (some rank's stream is capturing)\n", rank_, name);
+    return leave(ncclInvalidUsage);
+  }
+  uint32_t seq = ++call_seq_;
+  if (seq == 0) seq = ++call_seq_;
+  if (d == PeerBuffers::kRead) {
+    const void* send_of[kMaxRanks];
+    uint64_t peer_sdispl[kMaxRanks];
+    for (int q = 0; q < n; ++q) {
+      send_of[q] = q == rank_ ? (const char*)rsend : psend[q];
+      peer_sdispl[q] = rows[q].rdispls[rank_];
+    }
+    CombineArgs v;
+    // (a rank without rows passes a stand-in list: never read)
+    combine_fill_args(&v, n, esz, rrecv, nrows, rowstride, nrows ? kslot : (const int32_t*)rsend, nrows ? kw : nullptr, topk,
+                      recvcounts, rdispls, rowcount, send_of, peer_sdispl);
+    int A = 0;
+    const CollParams p = make_params(2, rsend, rrecv, M, seq, psend, precv, 0, 0, coll, 0, 0, &A);
+    hip_check(launch_combine(dtype, A / geo_.waves, cfg_.threads, p, v, stream), "kernel launch");
+    last_algo_ = 2;
+  } else {
+    const size_t Mpad = (Mb + 15) & ~(size_t)15;
+    size_t P = 0;  // the virtual sequence's end, in bytes
+    for (int q = 0; q < n; ++q)
+      if (recvcounts[q]) P = std::max(P, (size_t)(rdispls[q] + recvcounts[q]) * rb);
+    const size_t Ppad = (P + 15) & ~(size_t)15;
+    ensure_stage(2 * (size_t)n * Mpad + Ppad + out_bytes, stream);
+    char* in = stage_;
+    char* out = stage_ + (size_t)n * Mpad;
+    char* packed = stage_ + 2 * (size_t)n * Mpad;
+    const char* s0 = static_cast<const char*>(send);
+    for (int q = 0; q < n; ++q)
+      if (q != rank_ && sendcounts[q])
+        hip_check(hipMemcpyAsync(in + (size_t)q * Mpad, s0 + sdispls[q] * rb, sendcounts[q] * rb, hipMemcpyDefault, stream),
+                  "pack");
+    launch(0, in, out, Mpad, dtype, kSum, stream, seq, true, nullptr, nullptr, 0, 0, kCollAllToAll);
+    for (int q = 0; q < n; ++q)
+      if (q != rank_ && recvcounts[q])
+        hip_check(hipMemcpyAsync(packed + rdispls[q] * rb, out + (size_t)q * Mpad, recvcounts[q] * rb, hipMemcpyDefault, stream),
+                  "unpack");
+    if (sendcounts[rank_])
+      hip_check(hipMemcpyAsync(packed + rdispls[rank_] * rb, s0 + sdispls[rank_] * rb, sendcounts[rank_] * rb,
+                               hipMemcpyDefault, stream), "own block");
+    fold_local(packed, rdispls, 2 * (size_t)n * Mpad + Ppad);
+  }
+  return end_call(scope, stream, seq);
+}
+
 // mncclAllGatherv / mncclReduceScatterv.  all_to_all_v's call path with one row of counts and
 // displacements that every rank must pass alike: the caller's local errors first (vhalves.h: nothing
 // launched, nothing negotiated); then every rank's arrays reach every rank -- through the read

@@ -142,6 +142,17 @@ class Comm {
     return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
   }
 
+  // The way back (mncclAllToAllvCombine, mini_nccl_ext.h; counts and displacements in rows): the dense
+  // send blocks are what ncclAllToAllv would deliver into a packed recv, which is never built -- row t
+  // of the nrows x rowstride matrix at `recv` becomes the sum over k < topk of weights[t * topk + k]
+  // times row slotidx[t * topk + k] of that virtual sequence, in float, in slot order.  A call path
+  // of its own (comm.cpp combine) modelled on all_to_all_v's, with the rules of combine.h: kernels.hip
+  // combine_fold on the read schedule; else ncclAllToAllv's padded ring into a packed stage and
+  // combine_local out of it.
+  ncclResult_t combine(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv, size_t nrows,
+                       size_t rowstride, const int32_t* slotidx, const float* weights, int topk, const size_t* recvcounts,
+                       const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream);
+
   // The halves with per-rank counts (mncclAllGatherv / mncclReduceScatterv, mini_nccl_ext.h; counts and
   // displacements in elements, host arrays of n entries read before the call returns, the same on
   // every rank): rank q's send becomes elements [rdispls[q], +recvcounts[q]) of every rank's recv;

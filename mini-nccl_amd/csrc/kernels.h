@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "combine.h"
 #include "p2p.h"
 #include "rowblock.h"
 
@@ -148,6 +149,15 @@ struct RowsPackArgs {
   uint32_t lanes_log2_vec, lanes_log2_elem;  // set by the launcher: lanes per row on either path
 };
 hipError_t launch_rows_pack(int dtype, RowsPackArgs a, hipStream_t stream);
+// mncclAllToAllvCombine on the read schedule (kernels.hip combine_fold): CombineArgs (combine.h), a
+// second by-value kernel argument.  p: p.coll kCollAllToAllVCombine; the geometry for chunk_bytes = the
+// longest output matrix of any rank in bytes of packed rows, p.recv this rank's matrix, p.peer_send
+// every rank's send (own at [rank]).  kF32 / kF16 / kBF16.  Refuses an output longer than the geometry's.
+hipError_t launch_combine(int dtype, int channels, int threads, const CollParams& p, const CombineArgs& v,
+                          hipStream_t stream);
+// The same fold as a plain grid launch out of one local buffer (kernels.hip combine_local): block q of
+// the virtual sequence lies at src + v.src_off[q], for every q < n.  No rows: nothing launched.
+hipError_t launch_combine_local(int dtype, int n, const CombineArgs& v, const void* src, void* recv, hipStream_t stream);
 // mncclReduceScatterv / mncclAllGatherv on the read schedule (kernels.hip vhalf_fold / vhalf_push):
 // this rank's block of the array-side buffers, a second by-value kernel argument (CollParams stays
 // byte for byte what it was).  The arrays are the same on every rank, so `base` is the block's byte

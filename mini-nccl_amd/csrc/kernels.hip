@@ -35,6 +35,11 @@
 //                 device-side index list (mncclAllToAllvRows): varblock_push's protocol and geometry,
 //                 the gather fused into the push's loads; rows_pack is the same gather as a grid
 //                 kernel into local memory (one rank, and the padded ring's stage).
+//  combine_fold / combine_local   the way back of that layer (mncclAllToAllvCombine): the token owner
+//                 pulls the top-k rows of each of its tokens out of the peers' send, folds them by gate
+//                 weight in float in slot order and stores one row; vhalf_fold's protocol, the geometry
+//                 of the longest output; combine_local is the same fold as a grid kernel out of one
+//                 local packed buffer (one rank, and behind the padded ring).
 //  vhalf_fold / vhalf_push   the halves with per-rank counts (mncclReduceScatterv / mncclAllGatherv)
 //                 on the same protocol: scatter_fold and gather_push with a per-rank base and
 //                 length, the slices cut for the largest block.  Their fallback is the ring's
@@ -2076,6 +2081,280 @@ __global__ void __launch_bounds__(256) rows_pack(RowsPackArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- the combine
+// mncclAllToAllvCombine (combine_fold): rows_push transposed.  The token owner PULLS the up to topk
+// rows of each of its tokens out of the peers' dense send buffers (sc0 sc1 loads over the links,
+// between START and DONE as scatter_fold's), multiplies each by its gate weight and adds them in
+// float in slot order k = 0 .. topk-1, rounds once and stores one output row into its own strided
+// recv: one read of every returned row, one write of every output row, no packed buffer, no atomics,
+// the same bits whatever the slices.  read_half<VAR>'s protocol message for message; the call's
+// geometry is the longest output matrix of any rank, this rank's slices are cut out of the packed
+// sequence of ITS output rows and clamped to it, and rowblock.h rows_units says which units of a row
+// a slice stores (a unit belongs to the slice holding its first byte), so every output byte is stored
+// exactly once.  slotidx and weights are read here, at run time: a replayed graph folds by whatever
+// they hold then.
+//
+// A slot's position j of the virtual packed sequence belongs to rank q when a non-empty range
+// [lo[q], lo[q] + cnt[q]) holds it (combine.h combine_owner: a scan of at most 16 ranges); every other
+// j -- negative, beyond, in a gap -- contributes nothing and causes no access.
+//
+// Wide rows (the 16-byte path, >= kRowsWideVectors vectors), combine_wide: the wave walks one output
+// row segment at a time.  The slot indices and weights of 64 / topk rows arrive in one coalesced load
+// each, lane (t - tb) * topk + k holding row t's slot k, and the next 64 / topk rows' are fetched when
+// a batch of them is begun; a slot is made wave-uniform with readlane, its owner scanned on the
+// scalar side, and every source row gets a buffer descriptor of its own -- num_records 0 and weight 0
+// for a slot that contributes nothing, so its loads return 0, touch nothing, and add +0 (the sum
+// starts at +0 and can never be -0, so that leaves its bits alone).  A batch is V vectors per lane
+// from each of G sources, all loaded before the first product; topk > 8 continues into the same float
+// accumulators with a second group, so the order of the sum is the slots'.  G is a template
+// argument (1, 2, 4, 8 by topk): the descriptors and the loaded vectors are register arrays and must
+// be indexed by constants.
+// Narrow rows, every row's last row_bytes % 16 bytes, and every element off the 16-byte path,
+// combine_packed: rows_packed's lane assignment (lane l serves row l / units, unit l % units; rows
+// of 64 units and more take the wave whole); each lane runs its own slots, and the lanes of a pass
+// that read the same peer share one descriptor of that peer's block (a loop over the distinct peers
+// among the active lanes), so these loads are range-checked sc0 sc1 buffer loads too.
+// Products and sums never contract (fp contract off) and stay scalar f32 operations.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MNCCL_SCALAR_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define MNCCL_SCALAR_F32
+#endif
+
+template <typename T> struct CombineElem;  // an element's bits <-> float
+template <> struct CombineElem<float> {
+  __device__ static float up(uint32_t b) { return __uint_as_float(b); }
+  __device__ static uint32_t down(float f) { return __float_as_uint(f); }
+};
+template <> struct CombineElem<_Float16> {
+  __device__ static float up(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
+  __device__ static uint16_t down(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
+};
+template <> struct CombineElem<bf16_t> {
+  __device__ static float up(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
+  __device__ static uint16_t down(float f) { return f2bf(f).v; }
+};
+
+// acc[e] += w * x[e] over the elements of one vector: one IEEE multiply and one IEEE add each
+template <typename T>
+__device__ __forceinline__ MNCCL_SCALAR_F32 void combine_mac16(float (&acc)[16 / sizeof(T)], v4u x, float w) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if constexpr (sizeof(T) == 4) {
+      acc[c] = acc[c] + w * CombineElem<T>::up(x[c]);
+    } else {
+      acc[2 * c] = acc[2 * c] + w * CombineElem<T>::up((uint16_t)x[c]);
+      acc[2 * c + 1] = acc[2 * c + 1] + w * CombineElem<T>::up((uint16_t)(x[c] >> 16));
+    }
+  }
+}
+template <typename T>
+__device__ __forceinline__ v4u combine_pack16(const float (&acc)[16 / sizeof(T)]) {
+  v4u x;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if constexpr (sizeof(T) == 4) x[c] = CombineElem<T>::down(acc[c]);
+    else x[c] = (uint32_t)CombineElem<T>::down(acc[2 * c]) | (uint32_t)CombineElem<T>::down(acc[2 * c + 1]) << 16;
+  }
+  return x;
+}
+
+constexpr int kCombineV = 2;  // 2 KiB per source and batch: 8 sources are 64 registers of loads in flight
+
+template <typename T, int G, int V>
+__device__ __forceinline__ MNCCL_SCALAR_F32 void combine_wide(const CollParams& p, const CombineArgs& v, u64 soff, u64 b,
+                                                              int lane) {
+  constexpr int E = 16 / sizeof(T);
+  constexpr uint32_t step = 64 * V;
+  const int n = p.n;
+  const uint32_t rb = v.row_bytes, nv = rb >> 4, topk = v.topk, rpb = 64 / topk;
+  const u64 nslots = (u64)v.nrows * topk;
+  // lane l: entry l of the rpb rows from row `base` on (-1 / 0 past them and past the matrix)
+  auto fetch_i = [&](u64 base) -> int32_t {
+    const u64 e = base * topk + (u64)lane;
+    return (uint32_t)lane < rpb * topk && e < nslots ? v.slotidx[e] : -1;
+  };
+  auto fetch_w = [&](u64 base) -> float {
+    const u64 e = base * topk + (u64)lane;
+    return (uint32_t)lane < rpb * topk && e < nslots ? (v.weights ? v.weights[e] : 1.0f) : 0.0f;
+  };
+  u64 tb = soff / rb;
+  int32_t ic = fetch_i(tb), in = fetch_i(tb + rpb);
+  float wc = fetch_w(tb), wn = fetch_w(tb + rpb);
+  for (u64 t = tb; t * rb < b; ++t) {
+    if (t - tb >= rpb) {
+      tb += rpb;
+      ic = in;
+      wc = wn;
+      in = fetch_i(tb + rpb);
+      wn = fetch_w(tb + rpb);
+    }
+    uint32_t i0, i1;
+    rows_units(soff, b, t * rb, 0, 16, nv, &i0, &i1);
+    const uint32_t nseg = i1 - i0;
+    if (nseg == 0) continue;
+    const rsrc_t dst = make_rsrc(p.recv + t * v.stride_bytes + (u64)i0 * 16, nseg * 16);
+    const uint32_t s0 = (uint32_t)(t - tb) * topk;
+    rsrc_t src[G];
+    float w[G];
+    // slots k0 .. k0 + G - 1 of row t: their descriptors over the row segment, their weights
+    auto open = [&](uint32_t k0) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const uint32_t k = k0 + (uint32_t)g;
+        const int sl = __builtin_amdgcn_readfirstlane((int)(s0 + (k < topk ? k : 0u)));
+        const int32_t j = k < topk ? __builtin_amdgcn_readlane(ic, sl) : -1;
+        const float wk = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(wc), sl));
+        const int q = combine_owner(v, n, j);
+        const int qq = q < 0 ? 0 : q;
+        const char* from = p.peer_send[qq] + v.src_off[qq] + ((u64)(uint32_t)j - v.lo[qq]) * rb + (u64)i0 * 16;
+        src[g] = make_rsrc(q < 0 ? p.send : from, q < 0 ? 0u : nseg * 16);
+        w[g] = q < 0 ? 0.0f : wk;
+      }
+    };
+    if (topk <= (uint32_t)G) open(0);
+    for (uint32_t at = 0; at < nseg; at += step) {
+      float acc[V][E];
+#pragma unroll
+      for (int u = 0; u < V; ++u)
+#pragma unroll
+        for (int e = 0; e < E; ++e) acc[u][e] = 0.0f;
+      for (uint32_t k0 = 0; k0 < topk; k0 += G) {
+        if (topk > (uint32_t)G) open(k0);
+        v4u x[G][V];
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+          for (int u = 0; u < V; ++u) x[g][u] = ld_slot16(src[g], (at + (uint32_t)(u * 64 + lane)) * 16);
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+          for (int u = 0; u < V; ++u) combine_mac16<T>(acc[u], x[g][u], w[g]);
+      }
+#pragma unroll
+      for (int u = 0; u < V; ++u) st_slot16(dst, (at + (uint32_t)(u * 64 + lane)) * 16, combine_pack16<T>(acc[u]));
+    }
+  }
+}
+
+// One unit of U bytes (16: a vector; else one element) at byte `off` of output row `row`, by this lane
+// alone: its topk slots in order.  Rank q's send is peer_send[q], or `src` for every q (LOCAL).  The
+// loads go through one descriptor per distinct (peer, 2 GiB window of its block) among the active lanes.
+template <typename T, int U, bool LOCAL>
+__device__ __forceinline__ MNCCL_SCALAR_F32 void combine_unit(const CollParams* p, const char* src, char* recv,
+                                                              const CombineArgs& v, int n, u64 row, uint32_t off) {
+  constexpr int E = U / (int)sizeof(T);
+  typedef typename Scal<sizeof(T)>::U Bits;
+  const uint32_t rb = v.row_bytes, topk = v.topk;
+  float acc[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) acc[e] = 0.0f;
+  for (uint32_t k = 0; k < topk; ++k) {
+    const u64 at = row * topk + k;
+    const int32_t j = v.slotidx[at];
+    const float w = v.weights ? v.weights[at] : 1.0f;
+    int q = -1;
+    u64 qlo = 0;  // combine_owner, keeping the range's start (the ranges are read with uniform indices)
+    for (int s = 0; s < n; ++s) {
+      const u64 l = v.lo[s];
+      if (j >= 0 && (u64)j >= l && (u64)j - l < v.cnt[s]) q = s, qlo = l;
+    }
+    const bool valid = q >= 0;
+    const int qq = valid ? q : 0;
+    const u64 rel = ((u64)(uint32_t)j - qlo) * rb + off;  // the unit's byte offset in q's block
+    const uint32_t key = (uint32_t)qq | (uint32_t)(rel >> 31) << 4;
+    v4u x4 = {0u, 0u, 0u, 0u};
+    Bits x1 = 0;
+    bool pending = valid;
+    while (pending) {
+      const uint32_t kq = __builtin_amdgcn_readfirstlane(key);
+      if (key == kq) {
+        const int sq = (int)(kq & 15u);
+        const u64 win = (u64)(kq >> 4) << 31, left = v.cnt[sq] * rb - win;
+        const char* from = src;
+        if constexpr (!LOCAL) from = p->peer_send[sq];
+        const rsrc_t s = make_rsrc(from + v.src_off[sq] + win, (uint32_t)(left < 0x80000010ull ? left : 0x80000010ull));
+        if constexpr (U == 16) x4 = ld_slot16(s, (uint32_t)(rel - win));
+        else x1 = Scal<sizeof(T)>::ld(s, (uint32_t)(rel - win));
+        pending = false;
+      }
+    }
+    if (valid) {
+      if constexpr (U == 16) {
+        combine_mac16<T>(acc, x4, w);
+      } else {
+#pragma clang fp contract(off)
+        acc[0] = acc[0] + w * CombineElem<T>::up(x1);
+      }
+    }
+  }
+  char* to = recv + row * v.stride_bytes + off;
+  if constexpr (U == 16) __builtin_nontemporal_store(combine_pack16<T>(acc), reinterpret_cast<v4u_dw*>(to));
+  else *reinterpret_cast<Bits*>(to) = CombineElem<T>::down(acc[0]);
+}
+
+// Units of U bytes at row offsets lo + c * U, c < cnt, of the output rows of slice [soff, b)
+template <typename T, int U>
+__device__ __forceinline__ MNCCL_SCALAR_F32 void combine_packed(const CollParams& p, const CombineArgs& v, u64 soff, u64 b,
+                                                                uint32_t lo, uint32_t cnt, int lane) {
+  const uint32_t rb = v.row_bytes;
+  const u64 j0 = soff / rb;
+  if (cnt >= 64) {
+    for (u64 row = j0; row * rb < b; ++row) {
+      uint32_t c0, c1;
+      rows_units(soff, b, row * rb, lo, U, cnt, &c0, &c1);
+      for (uint32_t c = c0 + (uint32_t)lane; c < c1; c += 64) combine_unit<T, U, false>(&p, nullptr, p.recv, v, p.n, row, lo + c * U);
+    }
+  } else {
+    const uint32_t per = 64 / cnt, lr = (uint32_t)lane / cnt, lc = (uint32_t)lane % cnt;
+    if (lr >= per) return;
+    for (u64 row = j0 + lr; row * rb < b; row += per) {
+      const u64 at = row * rb + lo + (u64)lc * U;
+      if (at >= soff && at < b) combine_unit<T, U, false>(&p, nullptr, p.recv, v, p.n, row, lo + lc * U);
+    }
+  }
+}
+
+// slice [soff, b) of this rank's packed output rows
+template <typename T>
+__device__ __forceinline__ MNCCL_SCALAR_F32 void combine_slice(const CollParams& p, const CombineArgs& v, u64 soff, u64 b,
+                                                               int lane) {
+  const uint32_t rb = v.row_bytes, nv = v.vec ? rb >> 4 : 0u, lo = nv * 16;
+  if (nv >= kRowsWideVectors) {
+    if (v.topk <= 1) combine_wide<T, 1, kCombineV>(p, v, soff, b, lane);
+    else if (v.topk <= 2) combine_wide<T, 2, kCombineV>(p, v, soff, b, lane);
+    else if (v.topk <= 4) combine_wide<T, 4, kCombineV>(p, v, soff, b, lane);
+    else combine_wide<T, 8, kCombineV>(p, v, soff, b, lane);
+  } else if (nv > 0) {
+    combine_packed<T, 16>(p, v, soff, b, 0, nv, lane);
+  }
+  if (lo < rb) combine_packed<T, (int)sizeof(T)>(p, v, soff, b, lo, (rb - lo) / (uint32_t)sizeof(T), lane);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) MNCCL_SCALAR_F32 combine_fold(CollParams p, CombineArgs v) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half<false, true>(
+      p, s_tx, s_rx, [&p, &v](u64 coff, uint32_t len, int lane) { combine_slice<T>(p, v, coff, coff + len, lane); }, 0,
+      (u64)v.nrows * v.row_bytes);
+}
+
+// The same fold as a plain grid kernel out of ONE local buffer that holds block q at byte src_off[q]
+// (one rank; every count zero; the padded ring's packed stage): a thread per unit, the same units,
+// the same order of the sum.
+template <typename T>
+__global__ void __launch_bounds__(256) MNCCL_SCALAR_F32 combine_local(CombineArgs v, const char* src, char* recv, int n) {
+  const uint32_t rb = v.row_bytes, nv = v.vec ? rb >> 4 : 0u, lo = nv * 16, upr = nv + (rb - lo) / (uint32_t)sizeof(T);
+  const u64 total = (u64)v.nrows * upr;
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (u64)gridDim.x * blockDim.x) {
+    const u64 row = i / upr;
+    const uint32_t c = (uint32_t)(i % upr);
+    if (c < nv) combine_unit<T, 16, true>(nullptr, src, recv, v, n, row, c * 16);
+    else combine_unit<T, (int)sizeof(T), true>(nullptr, src, recv, v, n, row, lo + (c - nv) * (uint32_t)sizeof(T));
+  }
+}
+
 // ---------------------------------------------------------------- point to point
 // ncclSend / ncclRecv (p2p_kernel): a send is the sender's half of one ring hop to an arbitrary
 // peer, a recv the receiver's half, on the scratch protocol of the file header -- the peer's region
@@ -2971,6 +3250,46 @@ hipError_t launch_rows_pack(int dtype, RowsPackArgs a, hipStream_t st) {
   const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);  // the rest by the grid's stride
   return for_rows_size(dtype, [&](auto e) {
     hipLaunchKernelGGL(rows_pack<decltype(e)::value>, dim3(blocks, (unsigned)a.n), dim3(256), 0, st, a);
+    return hipGetLastError();
+  });
+}
+
+// the combine's datatypes: the ones with a float to fold in
+template <typename F>
+static hipError_t for_combine_type(int dtype, F&& f) {
+  switch (dtype) {
+    case kF32: return f(TypeTag<float>{});
+    case kF16: return f(TypeTag<_Float16>{});
+    case kBF16: return f(TypeTag<bf16_t>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+static bool combine_args_ok(const CombineArgs& v, int n) {
+  return n >= 1 && n <= kMaxRanks && v.topk >= 1 && v.topk <= (uint32_t)kCombineMaxTopk && (v.nrows == 0 || v.slotidx) &&
+         v.stride_bytes >= v.row_bytes;
+}
+
+hipError_t launch_combine(int dtype, int C, int nt, const CollParams& p, const CombineArgs& v, hipStream_t st) {
+  // (a rank with no output rows passes a stand-in list, Comm::combine: never read, but not NULL)
+  if (p.coll != kCollAllToAllVCombine || p.n < 2 || v.row_bytes == 0 || !v.slotidx || !combine_args_ok(v, p.n) ||
+      (u64)v.nrows * v.row_bytes > p.chunk_bytes)
+    return hipErrorInvalidValue;
+  return for_combine_type(dtype, [&](auto t) {
+    hipLaunchKernelGGL(combine_fold<typename decltype(t)::type>, dim3(C), dim3(nt), 0, st, p, v);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_combine_local(int dtype, int n, const CombineArgs& v, const void* src, void* recv, hipStream_t st) {
+  if (!combine_args_ok(v, n) || (v.nrows && (!recv || v.row_bytes == 0))) return hipErrorInvalidValue;
+  if (v.nrows == 0) return hipSuccess;
+  const uint32_t upr = v.vec ? (v.row_bytes >> 4) + (v.row_bytes & 15u) / (uint32_t)dtype_size(dtype)
+                             : v.row_bytes / (uint32_t)dtype_size(dtype);
+  const u64 want = ((u64)v.nrows * upr + 255) / 256;
+  const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);  // the rest by the grid's stride
+  return for_combine_type(dtype, [&](auto t) {
+    hipLaunchKernelGGL(combine_local<typename decltype(t)::type>, dim3(blocks), dim3(256), 0, st, v,
+                       static_cast<const char*>(src), static_cast<char*>(recv), n);
     return hipGetLastError();
   });
 }

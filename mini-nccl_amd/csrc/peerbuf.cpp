@@ -647,7 +647,7 @@ PeerBuffers::Decision PeerBuffers::negotiate_body(uint64_t k, const void* send, 
   // differ in the collective differ in `form` above)
   if (row && rows_out && !mismatch)
     mismatch = (row->flags & kVarSameRows ? vhalf_rows_differ(nranks_, rows_out) : varblock_matrix_mismatch(nranks_, rows_out)) != 0 ||
-               ((row->flags & kVarRows) && varblock_rowcounts_differ(nranks_, rows_out));  // (mncclAllToAllvRows: the row's length too)
+               ((row->flags & (kVarRows | kVarCombine)) && varblock_rowcounts_differ(nranks_, rows_out));  // (by rows: the row's length too)
   const Decision d = mismatch ? kMismatch : all ? kRead : kFallback;
   *vec_all = aligned;
   if (d != kRead) return d;

@@ -167,7 +167,10 @@ enum Coll : int {
   kCollAllGatherV = 9, kCollReduceScatterV = 10,
   // mncclAllToAllvRows: kCollAllToAllV with the send blocks gathered by row index (rowblock.h); its
   // fallback is kCollAllToAllV's padded ring behind a gather kernel
-  kCollAllToAllVRows = 11
+  kCollAllToAllVRows = 11,
+  // mncclAllToAllvCombine: the way back -- the owner pulls its tokens' rows out of the peers' send and
+  // folds them by weight (combine.h); its fallback is kCollAllToAllV's padded ring in front of a local fold
+  kCollAllToAllVCombine = 12
 };
 
 // r, root: gather and scatter only (their op count depends on the rank's place in the chain; the

@@ -1590,6 +1590,37 @@ int mnccl_sim_rows_exchange(int n, int esz, uint64_t slice_bytes, const uint8_t*
   return 0;
 }
 
+// csrc/combine.h, the host-side rules of mncclAllToAllvCombine, for the CPU suite: one rank's local
+// checks (a CombineLocal verdict; the buffers are only compared, never dereferenced), and the kernels'
+// argument block (out: n lo[], n cnt[], n src_off[], then vec) with the owner of each of `nj`
+// positions js[] of the virtual sequence (owners[]: a rank, or -1).
+int mnccl_sim_combine_check_local(int n, int esz, const void* send, const size_t* sendcounts, const size_t* sdispls,
+                                  const void* recv, size_t nrows, size_t rowstride, const int32_t* slotidx,
+                                  const float* weights, int topk, const size_t* recvcounts, const size_t* rdispls,
+                                  size_t rowcount) {
+  if (n < 1 || n > mnccl::kVarMaxRanks || esz < 1) return -2;
+  return mnccl::combine_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights, topk,
+                                    recvcounts, rdispls, rowcount);
+}
+int mnccl_sim_combine_args(int n, int esz, uint64_t recv_addr, size_t nrows, size_t rowstride, int topk,
+                           const size_t* recvcounts, const size_t* rdispls, size_t rowcount, const uint64_t* send_addr,
+                           const uint64_t* peer_sdispl, uint64_t* out, int nj, const int32_t* js, int* owners) {
+  if (n < 1 || n > mnccl::kVarMaxRanks) return -2;
+  const void* send_of[mnccl::kVarMaxRanks];
+  for (int q = 0; q < n; ++q) send_of[q] = (const void*)(uintptr_t)send_addr[q];
+  mnccl::CombineArgs v;
+  mnccl::combine_fill_args(&v, n, esz, (const void*)(uintptr_t)recv_addr, nrows, rowstride, nullptr, nullptr, topk, recvcounts,
+                           rdispls, rowcount, send_of, peer_sdispl);
+  for (int q = 0; q < n; ++q) {
+    out[q] = v.lo[q];
+    out[n + q] = v.cnt[q];
+    out[2 * n + q] = v.src_off[q];
+  }
+  out[3 * n] = v.vec;
+  for (int i = 0; i < nj; ++i) owners[i] = mnccl::combine_owner(v, n, js[i]);
+  return 0;
+}
+
 // csrc/vhalves.h, the host-side rules of mncclAllGatherv / mncclReduceScatterv, and schedule.h's length
 // rule for them.  mnccl_vhalf_rows_differ: counts / displs are n x n, row r what rank r passed.
 int mnccl_vhalf_check_local(int n, int rank, int esz, const void* array_buf, const size_t* counts, const size_t* displs,

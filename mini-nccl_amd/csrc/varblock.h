@@ -22,6 +22,7 @@ struct VarRow {
   uint64_t sendcounts[kVarMaxRanks], recvcounts[kVarMaxRanks], rdispls[kVarMaxRanks];  // elements
   uint32_t flags;  // kVarCapturing
   uint32_t pad;
+  uint64_t nrows;  // kVarCombine only (0 otherwise): the rank's output rows
 };
 enum : uint32_t {
   kVarCapturing = 1u,  // this rank's stream is being captured into a graph
@@ -30,7 +31,12 @@ enum : uint32_t {
   kVarSameRows = 2u,
   // the row of an mncclAllToAllvRows call (rowblock.h): counts and displacements in matrix rows, the
   // row's length in elements in `pad` -- which the ranks must pass alike (varblock_rowcounts_differ)
-  kVarRows = 4u
+  kVarRows = 4u,
+  // the row of an mncclAllToAllvCombine call (combine.h): counts in rows, the row's length in `pad` as
+  // above; the puller needs what ncclAllToAllv keeps private, so `rdispls` carries the rank's SEND
+  // displacements (its recv displacements name positions of a virtual sequence: nobody else's business),
+  // and `nrows` its output rows -- the call's geometry follows the longest output (combine_max_rows)
+  kVarCombine = 8u
 };
 
 // The local checks' verdicts, in the order they are made
@@ -89,7 +95,7 @@ inline int varblock_matrix_mismatch(int n, const VarRow* rows) {
   return 0;
 }
 
-// mncclAllToAllvRows (rows with kVarRows): some rank passed another rowcount
+// mncclAllToAllvRows / mncclAllToAllvCombine (rows with kVarRows / kVarCombine): some rank passed another rowcount
 inline bool varblock_rowcounts_differ(int n, const VarRow* rows) {
   for (int r = 1; r < n; ++r)
     if (rows[r].pad != rows[0].pad) return true;

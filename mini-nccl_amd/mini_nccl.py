@@ -99,6 +99,8 @@ SIGNATURES = {
                            _I, _VP, _VP]),
     "mncclAllToAllvRows": (_I, [_VP, _SZ, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, ctypes.POINTER(_SZ),
                                 ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
+    "mncclAllToAllvCombine": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _SZ, _VP, _VP, _I,
+                                   ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllGatherv": (_I, [_VP, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _I, _VP, _VP]),
     "mncclReduceScatterv": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclGather": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
@@ -304,6 +306,18 @@ class Comm:
         arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
         return load().mncclAllToAllvRows(send_ptr, nrows, rowstride, rowidx_ptr, arrays[0], arrays[1], recv_ptr, arrays[2],
                                          arrays[3], rowcount, dtype, self.handle, stream)
+
+    def all_to_all_v_combine(self, send_ptr, sendcounts, sdispls, recv_ptr, nrows, rowstride, slotidx_ptr, weights_ptr, topk,
+                             recvcounts, rdispls, rowcount, dtype=ncclFloat, stream=0):
+        """mncclAllToAllvCombine: row t of the nrows x rowstride matrix at recv_ptr becomes the sum over
+        k < topk, in that order, of weights[t * topk + k] times row slotidx[t * topk + k] of the packed
+        sequence all_to_all_v would deliver from the dense send blocks (rows of `rowcount` elements), in
+        float, rounded once.  slotidx_ptr (int32) and weights_ptr (float32, or 0 / None: every weight
+        1) are DEVICE arrays read when the call runs; a slot outside every block contributes nothing.
+        Counts and displacements are in rows on both sides.  Returns the ncclResult_t."""
+        arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
+        return load().mncclAllToAllvCombine(send_ptr, arrays[0], arrays[1], recv_ptr, nrows, rowstride, slotidx_ptr,
+                                            weights_ptr, topk, arrays[2], arrays[3], rowcount, dtype, self.handle, stream)
 
     def all_gather_v(self, send_ptr, sendcount, recv_ptr, recvcounts, rdispls, dtype=ncclFloat, stream=0):
         """mncclAllGatherv: rank q's `sendcount` elements of send end up at elements [rdispls[q],

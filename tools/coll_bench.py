@@ -67,6 +67,11 @@ persistent form (mncclAlgoRead), fp32 Sum, stream-ordered (MINI_NCCL_BLOCKING=0)
     alltoallv_rows_composed   what a caller runs without it, on the same matrix and indices: the gather
                     as a kernel of its own (rows_pack, through a one-rank communicator) into a packed
                     buffer, then ncclAllToAllv.  Ratio alltoallv_rows_over_composed beside both spreads
+    alltoallv_combine  mncclAllToAllvCombine, the way back of the same layer: the rows kinds' matrix
+                    transposed, bf16 rows of --row-elems elements, every token's top-2 rows folded by weight
+    alltoallv_combine_composed   what a caller runs without it, on the same data: ncclAllToAllv into a
+                    packed buffer, then the fold as a kernel of its own (combine_local, through a one-rank
+                    communicator).  Ratio alltoallv_combine_over_composed beside both spreads
 
 (broadcast: every rank loads one chunk of the root's send and stores it into all n recvs; reduce:
 every rank loads its chunk from all n sends and stores it into the root's recv -- on the one-GPU
@@ -101,16 +106,19 @@ KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_pr
          "all_to_all", "all_to_all_v", "all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
          "p2p_neighbor_win", "p2p_all_pairs_win", "gather", "gather_p2p", "scatter", "scatter_p2p",
          "all_gather_v", "reduce_scatter_v", "all_gather_v_skew", "reduce_scatter_v_skew", "all_gather_padded",
-         "reduce_scatter_padded", "alltoallv_rows", "alltoallv_rows_composed")
+         "reduce_scatter_padded", "alltoallv_rows", "alltoallv_rows_composed", "alltoallv_combine",
+         "alltoallv_combine_composed")
 # mncclAllToAllvRows beside what a caller composes without it, on the same matrix and indices
 ROWS_KINDS = ("alltoallv_rows", "alltoallv_rows_composed")
+# mncclAllToAllvCombine beside ncclAllToAllv plus a fold of the caller's own, on the same data
+COMBINE_KINDS = ("alltoallv_combine", "alltoallv_combine_composed")
 # the kinds that need the padded buffers (n blocks of the skewed shape's largest block)
 PADDED_KINDS = ("all_gather_padded", "reduce_scatter_padded")
 VHALF_SKEW = ("all_gather_v_skew", "reduce_scatter_v_skew") + PADDED_KINDS
 # the kinds --dtype bf16 can time (the others' helpers are written for fp32 elements)
 # the kinds that run while big_b is a registered window, and the scratch form each is measured against
 WIN_KINDS = {"p2p_neighbor_win": "p2p_neighbor", "p2p_all_pairs_win": "p2p_all_pairs"}
-BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce") + ROWS_KINDS
+BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce") + ROWS_KINDS + COMBINE_KINDS
 
 
 def skew_matrix(n, chunk, seed):
@@ -159,6 +167,39 @@ def rows_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stre
                                    M.ncclBfloat16, stream)
         return r or comm.all_to_all_v(packed.ptr, e(sc), e(starts(sc)), recv.ptr, e(rc), e(starts(rc)), M.ncclBfloat16, stream)
     return fused, composed, [x, idx, packed, recv], solo
+
+
+def combine_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stream):
+    """(fused, composed, buffers, solo): the way back of rows_calls' layer on its matrix -- this rank's
+    experts return C[q][rank] rows to rank q and it gets C[rank][q] back from q, bf16 rows of `row_elems`
+    elements; half as many tokens as rows come back, each folding two of them (a seeded top-2 list over
+    the packed sequence) by seeded weights.  Fused: mncclAllToAllvCombine.  Composed: ncclAllToAllv into
+    a packed buffer, then the same fold out of it (mncclAllToAllvCombine on a one-rank communicator runs
+    combine_local alone)."""
+    import numpy as np
+    rb = 2 * row_elems
+    per = max(1, block_bytes // rb)
+    C = skew_matrix(n, per, skew_seed) if skew_seed >= 0 else np.full((n, n), per, dtype=np.int64)
+    sc, rc = [int(x) for x in C[:, rank]], [int(x) for x in C[rank, :]]
+    starts = lambda xs: [int(sum(xs[:q])) for q in range(n)]
+    back, tokens = max(1, sum(rc)), max(1, sum(rc) // 2)
+    send, packed = hip_rt.DeviceBuffer(max(1, sum(sc)) * rb, fresh=True), hip_rt.DeviceBuffer(back * rb, fresh=True)
+    y, idx, w = hip_rt.DeviceBuffer(tokens * rb, fresh=True), hip_rt.DeviceBuffer(8 * tokens, fresh=True), hip_rt.DeviceBuffer(8 * tokens, fresh=True)
+    for b in (send, packed, y):
+        b.fill_byte(0)
+    rng = np.random.default_rng([skew_seed + 1, rank, 7])
+    idx.upload(rng.integers(0, back, 2 * tokens).astype(np.int32))
+    w.upload(rng.random(2 * tokens).astype(np.float32))
+    solo = comm.split(rank)
+    e = lambda xs: [v * row_elems for v in xs]
+    fused = lambda: comm.all_to_all_v_combine(send.ptr, sc, starts(sc), y.ptr, tokens, row_elems, idx.ptr, w.ptr, 2, rc, starts(rc),
+                                              row_elems, M.ncclBfloat16, stream)
+
+    def composed():
+        r = comm.all_to_all_v(send.ptr, e(sc), e(starts(sc)), packed.ptr, e(rc), e(starts(rc)), M.ncclBfloat16, stream)
+        return r or solo.all_to_all_v_combine(packed.ptr, [back], [0], y.ptr, tokens, row_elems, idx.ptr, w.ptr, 2, [back], [0],
+                                              row_elems, M.ncclBfloat16, stream)
+    return fused, composed, [send, packed, y, idx, w], solo
 
 
 def half_skew_counts(n, chunk):
@@ -271,6 +312,11 @@ def rank_main(a):
         calls["alltoallv_rows"], calls["alltoallv_rows_composed"], more, solo = rows_calls(
             M, hip_rt, comm, n, a.rank, a.bytes // n, a.row_elems, a.skew_seed if a.rows_skew else -1, st.handle)
         pads += more
+    solo2 = None
+    if any(k in COMBINE_KINDS for k in kinds):
+        calls["alltoallv_combine"], calls["alltoallv_combine_composed"], more, solo2 = combine_calls(
+            M, hip_rt, comm, n, a.rank, a.bytes // n, a.row_elems, a.skew_seed if a.rows_skew else -1, st.handle)
+        pads += more
     window = [None]
 
     def set_window(k, on):
@@ -323,8 +369,9 @@ def rank_main(a):
     for b in [big_a, big_b, small] + pads:
         b.free()
     st.destroy()
-    if solo is not None:
-        solo.destroy()
+    for c in (solo, solo2):
+        if c is not None:
+            c.destroy()
     comm.destroy()
     print("COLL_BENCH_RANK " + json.dumps({"rank": a.rank, "device": dev, "ms": ms, "algos": algos, "async": err, "direct": direct,
                                            "ranks_on_device": info["ranks_on_device"]}), flush=True)
@@ -399,7 +446,7 @@ def main():
         "rounds_ms": {k: [round(x, 4) for x in v] for k, v in rounds.items()},
         "hbm_bytes": {k: (2 * n if k in ("all_reduce", "all_reduce_premul", "all_to_all", "all_to_all_v") else n + 1) * chunk_bytes
                       for k in kinds if k not in ("all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
-                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") + VHALF_SKEW + ROWS_KINDS
+                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") + VHALF_SKEW + ROWS_KINDS + COMBINE_KINDS
                       and k not in WIN_KINDS},
         "ratio": dict([(f"{k}_over_all_reduce", round(med[k] / med["all_reduce"], 4)) for k in kinds if k != "all_reduce"] +
                       [(f"{k}_over_{y}", round(med[k] / med[y], 4))
@@ -457,6 +504,11 @@ def main():
         res["rows"] = {"row_elems": a.row_elems, "row_bytes": 2 * a.row_elems, "matrix": "skew" if a.rows_skew else "balanced"}
         res["ratio"]["alltoallv_rows_over_composed"] = round(med["alltoallv_rows"] / med["alltoallv_rows_composed"], 4)
         for k in ROWS_KINDS:
+            res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
+    if all(k in med for k in COMBINE_KINDS):
+        res["combine"] = {"row_elems": a.row_elems, "row_bytes": 2 * a.row_elems, "topk": 2, "matrix": "skew" if a.rows_skew else "balanced"}
+        res["ratio"]["alltoallv_combine_over_composed"] = round(med["alltoallv_combine"] / med["alltoallv_combine_composed"], 4)
+        for k in COMBINE_KINDS:
             res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
     if "all_gather" in rounds:
         res["all_gather_spread"] = round((max(rounds["all_gather"]) - min(rounds["all_gather"])) / med["all_gather"], 4)
