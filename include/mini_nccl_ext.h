@@ -39,6 +39,8 @@
  *                        number of tokens, possibly none).
  *   mncclAllToAllvRows   ncclAllToAllv whose send blocks are rows of a matrix picked by a device-side
  *                        index list (a MoE router's output as it is: no permutation pass in front).
+ *   mncclAllToAllvRowsMxfp8  the same from a bf16 / fp16 matrix with every row quantised to MXFP8 on the
+ *                        way out: e4m3 elements and one E8M0 scale per 32, in one record per row.
  *   mncclAllToAllvCombine  the way back: the token owner pulls the top-k rows of each token out of the
  *                        experts' send buffers and folds them by gate weight (no packed recv, no atomics).
  *
@@ -105,7 +107,8 @@ extern "C" {
    lies in a registered window (no new symbol; mncclCommInfo_t grew, same prefix: p2p_direct_recvs,
    p2p_direct_sends -- mncclCommGetInfoV writes them to a caller whose struct has room); still 600:
    mncclAllGatherv and mncclReduceScatterv were added the same way (detected by symbol;
-   mncclCommInfo_t did not grow); still 600: mncclAllToAllvRows was added the same way */
+   mncclCommInfo_t did not grow); still 600: mncclAllToAllvRows was added the same way; still 600:
+   mncclAllToAllvRowsMxfp8 was added the same way */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -453,6 +456,49 @@ ncclResult_t mncclAllToAllvRows(const void* sendbuff, size_t nrows, size_t rowst
                                 const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                                 const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
                                 ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
+
+/* mncclAllToAllvRows of a bf16 / fp16 matrix whose rows are quantised to MXFP8 between the gather's
+ * load and the push's store: the MoE dispatch for experts whose grouped GEMMs take e4m3 elements with
+ * one E8M0 scale per 32 (gfx950's scaled MFMA forms), 1.03 bytes per element on the wire instead of 2
+ * and no quantise pass in front.  Detected by symbol (MNCCL_VERSION stays 600).
+ *
+ * The send side is mncclAllToAllvRows': the strided matrix, the device-side int32 index list read when
+ * the call runs (at replay, for a captured call), counts and displacements in rows, an index outside
+ * [0, nrows) standing for a row of zeros.  `datatype` is the matrix's: ncclBfloat16 or ncclFloat16.
+ *
+ * The receive side.  Each delivered row is one RECORD of P = rowcount + rowcount / 32 bytes: rowcount
+ * e4m3 bytes, then rowcount / 32 scale bytes, one per block of 32 consecutive elements.  recvcounts /
+ * rdispls are in records: rank r's block lands at bytes [rdispls[r] * P, (rdispls[r] + recvcounts[r]) *
+ * P) of rank q's recvbuff; bytes outside every block are never written.  A GEMM reads elements and
+ * scales out of the one buffer with row pitch P.
+ *
+ * Result, bit for bit on every schedule.  Per block of 32 elements, each widened exactly to f32: E is
+ * the largest biased exponent field of the 32 magnitudes.  E == 255 (a NaN or an infinity in the
+ * block): scale byte 0xFF, all 32 element bytes 0x7F.  Otherwise the scale byte is s = max(E - 8, 0)
+ * (OCP MX v1.0: floor(log2(amax)) - 8, clamped at the bottom) and each element byte is e4m3 of
+ * x * 2^(127 - s): the scaling exact (subnormal inputs are not flushed), one rounding to nearest even,
+ * finite overflow saturated to +-448, the sign of zero kept.  A block of zeros -- an out-of-range row
+ * -- gives scale 0x00 and element bytes 0x00 / 0x80.
+ *
+ * Checks, in mncclAllToAllvRows' order; what differs:
+ *  3. a datatype other than the two above: ncclInternalError;
+ *  4. also ncclInvalidArgument, each checked locally: rowcount % 128 != 0 or rowcount outside [128,
+ *     16384]; sendbuff, rowstride in bytes or recvbuff not dword-aligned; the receive side's overlap,
+ *     overflow and NULL checks count P bytes per row.
+ * Everything else -- the open group, the rendezvous' verdicts (ranks that differ in the collective,
+ * the datatype, rowcount or the schedule choice among them), all-zero counts, idle ranks with NULL
+ * buffers, one rank -- is mncclAllToAllvRows'.
+ *
+ * Schedules.  On the read schedule one persistent kernel gathers, quantises and pushes (a record
+ * travels whole with the slice that holds its first byte).  Otherwise a grid kernel gathers and
+ * quantises each peer's block into ncclAllToAllv's padded stage and the rest is its fallback by
+ * bytes, with its cost and its refusal under capture.  Not built: e5m2 or other block sizes, f32
+ * input, rows that are no multiple of 128, a separate scales buffer, an fp8 way back, registered
+ * windows. */
+ncclResult_t mncclAllToAllvRowsMxfp8(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                                     const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                                     const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
+                                     ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
 
 /* The way back of the same layer: ncclAllToAllv whose packed recv is never built, because the token
  * owner folds the up to top-k returned rows of each token, each times its gate weight, into one

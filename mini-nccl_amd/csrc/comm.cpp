@@ -1191,20 +1191,29 @@ bool Comm::gather_rows(const VarRow& mine, int dtype, VarRow* rows, int coll, in
 // alike.  On the read schedule: kernels.hip rows_push.  Else ONE rows_pack launch gathers the blocks
 // where the copies above pack them -- the peers' into the stage at q * Mpad, the own one straight into
 // recv -- and the exchange and the unpack are the ones above.  One rank: rows_pack alone.
+//
+// mncclAllToAllvRowsMxfp8 (rows->mx) is that call again with the row's MXFP8 record for the row on the
+// receive side and on the wire (mxblock.h: P = rowcount + rowcount / 32 bytes, its local rules on top
+// of rowblock.h's); the rendezvous row carries kVarRowsMx beside kVarRows.  On the read schedule:
+// kernels.hip rowsmx_push.  Else rowsmx_pack quantises into the stage where rows_pack gathers, unit P.
 ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
                                 const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream,
                                 const RowsCall* rows_call) {
   if (sticky_ != ncclSuccess) return sticky_;
   if (check_status() != ncclSuccess) return sticky_;
   const int n = nranks_, esz = dtype_size(dtype);
-  const char* const name = rows_call ? "mncclAllToAllvRows" : "ncclAllToAllv";
-  const int coll = rows_call ? kCollAllToAllVRows : kCollAllToAllV;
+  const bool mx = rows_call && rows_call->mx;
+  const char* const name = mx ? "mncclAllToAllvRowsMxfp8" : rows_call ? "mncclAllToAllvRows" : "ncclAllToAllv";
+  const int coll = mx ? kCollAllToAllVRowsMx : rows_call ? kCollAllToAllVRows : kCollAllToAllV;
   if (rows_call) {
-    const int local = rows_check_local(n, esz, send, rows_call->nrows, rows_call->rowstride, rows_call->rowidx, sendcounts,
-                                       sdispls, recv, recvcounts, rdispls, rows_call->rowcount);
+    const int local = (mx ? mx_check_local : rows_check_local)(n, esz, send, rows_call->nrows, rows_call->rowstride,
+                                                               rows_call->rowidx, sendcounts, sdispls, recv, recvcounts,
+                                                               rdispls, rows_call->rowcount);
     if (local != kRowsOk) {
       fprintf(stderr, "[Mini-NCCL] rank %d: %s: %s\n", rank_, name,
-              local == kRowsZeroRow       ? "rowcount is 0 with a non-zero count"
+              local == kMxRowcount        ? "rowcount is not a multiple of 128 in [128, 16384]"
+              : local == kMxAlign         ? "sendbuff, rowstride in bytes or recvbuff is not dword-aligned"
+              : local == kRowsZeroRow     ? "rowcount is 0 with a non-zero count"
               : local == kRowsStride      ? "rowstride is smaller than rowcount"
               : local == kRowsTooManyRows ? "nrows is beyond what an int32 index can name"
               : local == kRowsNullBuffer  ? "a NULL buffer or index list with a non-zero count"
@@ -1225,8 +1234,8 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
       return ncclInvalidArgument;
     }
   }
-  // a block's unit in bytes: the element, or the row
-  const size_t unit = rows_call ? rows_call->rowcount * (size_t)esz : (size_t)esz;
+  // a block's unit in bytes: the element, the row, or the row's MXFP8 record
+  const size_t unit = mx ? (size_t)mx_record_bytes(rows_call->rowcount) : rows_call ? rows_call->rowcount * (size_t)esz : (size_t)esz;
   bool sends = false;
   for (int q = 0; q < n; ++q) sends = sends || sendcounts[q] != 0;
   const int32_t* kidx = rows_call ? rows_call->rowidx : nullptr;  // the index list as the kernels address it
@@ -1261,6 +1270,24 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
     if (reach(send, &src, &l) == Reach::kStaged) {
       hip_check(hipMemcpyAsync(src_stage, send, src_extra, hipMemcpyDefault, stream), "stage in");
       src = src_stage;
+    }
+    if (mx) {
+      MxArgs m;
+      memset(&m, 0, sizeof m);
+      m.src = static_cast<const char*>(src);
+      m.rowidx = kidx;
+      m.stride_bytes = (uint64_t)rows_call->rowstride * (uint64_t)esz;
+      m.rowcount = (uint32_t)rows_call->rowcount;
+      m.nrows = (uint32_t)rows_call->nrows;
+      m.n = n;
+      for (int q = 0; q < n; ++q) {
+        if (!dst[q] || !sendcounts[q]) continue;
+        m.dst[q] = dst[q];
+        m.idx_off[q] = sdispls[q];
+        m.count[q] = sendcounts[q];
+      }
+      hip_check(launch_rowsmx_pack(dtype, m, stream), "kernel launch");
+      return;
     }
     RowsPackArgs a;
     memset(&a, 0, sizeof a);
@@ -1312,7 +1339,8 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
     mine.recvcounts[q] = recvcounts[q];
     mine.rdispls[q] = rdispls[q];
   }
-  mine.flags = (scope.capturing() ? (uint32_t)kVarCapturing : 0u) | (rows_call ? (uint32_t)kVarRows : 0u);
+  mine.flags = (scope.capturing() ? (uint32_t)kVarCapturing : 0u) | (rows_call ? (uint32_t)kVarRows : 0u) |
+               (mx ? (uint32_t)kVarRowsMx : 0u);
   mine.pad = rows_call ? (uint32_t)rows_call->rowcount : 0u;  // (below 2^31: rows_check_local)
 
   PeerBuffers::Decision d = PeerBuffers::kFallback;
@@ -1381,7 +1409,25 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
   if (seq == 0) seq = ++call_seq_;
   const char* s0 = static_cast<const char*>(send);
   char* r0 = static_cast<char*>(recv);
-  if (d == PeerBuffers::kRead && rows_call) {
+  if (d == PeerBuffers::kRead && mx) {
+    MxArgs m;
+    memset(&m, 0, sizeof m);
+    // (an idle rank's stand-in matrix and list are never read: its counts are all zero)
+    m.rowidx = kidx ? kidx : (const int32_t*)rsend;
+    m.stride_bytes = (uint64_t)rows_call->rowstride * (uint64_t)esz;
+    m.rowcount = (uint32_t)rows_call->rowcount;
+    m.nrows = (uint32_t)rows_call->nrows;
+    m.n = n;
+    for (int q = 0; q < n; ++q) {
+      m.idx_off[q] = sdispls[q];
+      m.count[q] = sendcounts[q];
+      m.dst[q] = const_cast<char*>(q == rank_ ? (const char*)rrecv : precv[q]) + rows[q].rdispls[rank_] * unit;
+    }
+    int A = 0;
+    const CollParams p = make_params(2, rsend, rrecv, M, seq, psend, precv, 0, 0, coll, 0, 0, &A);
+    hip_check(launch_rowsmx(dtype, A / geo_.waves, cfg_.threads, p, m, stream), "kernel launch");
+    last_algo_ = 2;
+  } else if (d == PeerBuffers::kRead && rows_call) {
     const void* recv_of[kMaxRanks];
     uint64_t peer_rdispl[kMaxRanks];
     for (int q = 0; q < n; ++q) {

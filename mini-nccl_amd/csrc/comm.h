@@ -142,6 +142,17 @@ class Comm {
     return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
   }
 
+  // The same again with every row quantised to an MXFP8 record on the way out (mncclAllToAllvRowsMxfp8,
+  // mini_nccl_ext.h; dtype is the matrix's, kBF16 or kF16; the receive side counts records of
+  // rowcount + rowcount / 32 bytes).  The rules of mxblock.h: kernels.hip rowsmx_push on the read
+  // schedule; else rowsmx_pack quantises into the padded ring's stage.
+  ncclResult_t all_to_all_v_rows_mx(const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                                    const size_t* sendcounts, const size_t* sdispls, void* recv, const size_t* recvcounts,
+                                    const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream) {
+    const RowsCall rows{nrows, rowstride, rowcount, rowidx, true};
+    return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
+  }
+
   // The way back (mncclAllToAllvCombine, mini_nccl_ext.h; counts and displacements in rows): the dense
   // send blocks are what ncclAllToAllv would deliver into a packed recv, which is never built -- row t
   // of the nrows x rowstride matrix at `recv` becomes the sum over k < topk of weights[t * topk + k]
@@ -280,6 +291,7 @@ class Comm {
   struct RowsCall {
     size_t nrows, rowstride, rowcount;
     const int32_t* rowidx;
+    bool mx = false;  // mncclAllToAllvRowsMxfp8: the rows leave as MXFP8 records (mxblock.h)
   };
   ncclResult_t var_exchange(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
                             const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream,

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "combine.h"
+#include "mxblock.h"
 #include "p2p.h"
 #include "rowblock.h"
 
@@ -149,6 +150,15 @@ struct RowsPackArgs {
   uint32_t lanes_log2_vec, lanes_log2_elem;  // set by the launcher: lanes per row on either path
 };
 hipError_t launch_rows_pack(int dtype, RowsPackArgs a, hipStream_t stream);
+// mncclAllToAllvRowsMxfp8 on the read schedule (kernels.hip rowsmx_push): MxArgs (mxblock.h), a second
+// by-value kernel argument, dst[q] the block's place in rank q's recv.  p: p.coll kCollAllToAllVRowsMx;
+// the all-to-all's geometry for chunk_bytes = the largest block of the whole matrix in bytes of
+// records, p.send the matrix.  dtype: kBF16 or kF16, the matrix's.  Refuses a rowcount or an alignment
+// mx_check_local would, and a block longer than the geometry's.
+hipError_t launch_rowsmx(int dtype, int channels, int threads, const CollParams& p, const MxArgs& v, hipStream_t stream);
+// The same gather and quantise into local memory as a plain grid launch (kernels.hip rowsmx_pack):
+// block q's records packed at v.dst[q] out of the matrix at v.src, for every q < v.n.
+hipError_t launch_rowsmx_pack(int dtype, const MxArgs& v, hipStream_t stream);
 // mncclAllToAllvCombine on the read schedule (kernels.hip combine_fold): CombineArgs (combine.h), a
 // second by-value kernel argument.  p: p.coll kCollAllToAllVCombine; the geometry for chunk_bytes = the
 // longest output matrix of any rank in bytes of packed rows, p.recv this rank's matrix, p.peer_send

@@ -35,6 +35,9 @@
 //                 device-side index list (mncclAllToAllvRows): varblock_push's protocol and geometry,
 //                 the gather fused into the push's loads; rows_pack is the same gather as a grid
 //                 kernel into local memory (one rank, and the padded ring's stage).
+//  rowsmx_push / rowsmx_pack   the same from a bf16 / fp16 matrix with every row quantised to an MXFP8
+//                 record on the way out (mncclAllToAllvRowsMxfp8): e4m3 elements, one E8M0 scale byte
+//                 per 32; a lane pair per block, the scale bytes through a per-wave LDS strip.
 //  combine_fold / combine_local   the way back of that layer (mncclAllToAllvCombine): the token owner
 //                 pulls the top-k rows of each of its tokens out of the peers' send, folds them by gate
 //                 weight in float in slot order and stores one row; vhalf_fold's protocol, the geometry
@@ -2081,6 +2084,214 @@ __global__ void __launch_bounds__(256) rows_pack(RowsPackArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- the variable all-to-all by rows, to MXFP8
+// mncclAllToAllvRowsMxfp8 (rowsmx_push): rows_push whose rows are quantised between the gather's load
+// and the push's store -- bf16 / fp16 in, one RECORD per row out: rowcount e4m3 bytes, then one E8M0
+// scale byte per 32 elements (mxblock.h has the rule and the record's layout).  read_half's protocol
+// and rows_push's geometry; the blocks are virtual sequences of records of P bytes and a record travels
+// whole with the slice that holds its first byte (mx_slice_records): pushes go straight into the peer's
+// recv, so the overhang past a slice's end is harmless, no row is quantised twice and no amax is taken
+// from a partial row.
+//
+// A lane loads 16 consecutive elements (two 16-byte non-temporal loads), so a block of 32 is a lane
+// pair: each lane takes the unsigned maximum of its 16 magnitudes' f32 bits, one quad_perm DPP move
+// brings the neighbour's, and both lanes of the pair hold the block's exponent field E.  The scaling is
+// v_ldexp_f32 by 127 - s -- exact, subnormal inputs included: these kernels run with f32 denormals on
+// -- then fp8_sat's clamp and v_cvt_pk_fp8_f32, the encoder every fp8 fold here already uses; a block
+// with E == 255 becomes 0x7f bytes by a select, no branch.  Each lane stores its 16 e4m3 bytes as one
+// vector with the pushes' sc0 sc1 stores; the even lane of a pair writes the scale byte into the wave's
+// LDS strip (512 B: the 16384-element row's), and after the row's last pass the strip leaves behind the
+// row's elements as 16-byte vectors plus a dword tail.
+//
+// mx_lanes: rows of 1024 elements and more take the wave whole, one pass per 1024 elements (the last
+// one partial: its idle lanes load nothing and their stores fall outside the descriptor); narrower rows
+// share a pass, rowcount / 16 lanes per row, 1024 / rowcount rows at once, each with its own index and
+// its own part of the strip.  The walk is rows_wide's: two register sets, the next pass's loads -- of
+// the next row or the next destination as it may be -- leave before this pass is converted and stored;
+// indices arrive 64 per coalesced load a batch ahead, a lane picks its row's with ds_bpermute and
+// range-checks it once per pass.  The walk is shared with rowsmx_pack, the same gather and quantise as
+// a plain grid kernel into local memory: `open` names the destinations and their record ranges.
+template <bool F16>
+__device__ __forceinline__ v4u mx_quant16(const v4u& a, const v4u& b, uint32_t* scale) {
+  float f[16];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t w = i < 4 ? a[i] : b[i - 4];
+    if constexpr (F16) {
+      f[2 * i] = (float)__builtin_bit_cast(_Float16, (uint16_t)w);
+      f[2 * i + 1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
+    } else {
+      f[2 * i] = __uint_as_float(w << 16);
+      f[2 * i + 1] = __uint_as_float(w & 0xffff0000u);
+    }
+  }
+  uint32_t am = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const uint32_t m = __float_as_uint(f[i]) & 0x7fffffffu;
+    am = m > am ? m : am;
+  }
+  // the other lane of the pair: quad_perm [1, 0, 3, 2]; every lane of the wave is active here
+  const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)am, 0xB1, 0xf, 0xf, true);
+  am = nb > am ? nb : am;
+  const uint32_t s = mx_scale_byte(am >> 23);
+  *scale = s;
+  const int sh = 127 - (int)s;
+  v4u r;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    float y[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) y[e] = fp8_sat<e4m3_t>(__builtin_ldexpf(f[4 * d + e], sh));
+    const uint32_t w = Fp8<e4m3_t>::enc2<true>(y[2], y[3], Fp8<e4m3_t>::enc2<false>(y[0], y[1], 0u));
+    r[d] = s == 255u ? 0x7f7f7f7fu : w;
+  }
+  return r;
+}
+
+// an offset beyond every pass's descriptor (at most 8 records of 16896 bytes) that no 32-bit sum wraps
+constexpr uint32_t kMxNowhere = 0x40000000u;
+
+// One pass: a wave's 64 x 16 elements, of one row (wide) or of up to g.rows rows (narrow)
+struct MxPass {
+  rsrc_t dst;        // the pass's records, from the first one's first byte
+  const char* from;  // this lane's 32 source bytes
+  uint32_t off;      // where this lane's 16 element bytes go in dst (kMxNowhere: an idle lane)
+  uint32_t sc;       // where this lane's scale byte goes in the strip (~0u: not this lane's to write)
+  uint32_t nrec;     // records of the pass
+  bool ld;           // the lane has a row, and its index is in range
+  bool last;         // the records' last pass: the strip leaves after it
+};
+
+// open(k, j0, j1, dbase, ioff): destination k < K's records [j0, j1) of its block, the block's first
+// byte at the destination and its first entry of rowidx; false: nothing for k
+template <bool F16, typename Open>
+__device__ __forceinline__ void mx_walk(const MxArgs& v, const char* send, int K, const Open& open, uint32_t* strip,
+                                        int lane) {
+  const uint32_t rc = v.rowcount, sb = rc / kMxBlock, P = rc + sb;
+  const MxLanes g = mx_lanes(rc);
+  const uint32_t lr = (uint32_t)lane / g.lanes, lc = (uint32_t)lane % g.lanes;
+  int k = -1;
+  u64 j = 0, j1 = 0, jb = 0, ioff = 0;
+  uint32_t i = 0;
+  char* dbase = nullptr;
+  int32_t ic = -1, in = -1;  // lane l: the index of record jb + l, and of record jb + 64 + l
+  auto fetch = [&](u64 base) -> int32_t {
+    const u64 row = base + (u64)lane;
+    return row < j1 ? v.rowidx[ioff + row] : -1;
+  };
+  auto next = [&](MxPass& t) {
+    for (;;) {
+      if (k >= 0 && i < g.passes) {
+        const u64 left = j1 - j;
+        t.nrec = left < g.rows ? (uint32_t)left : g.rows;
+        const uint32_t e = i * kMxPassElems + lc * 16u;  // this lane's first element of its row
+        const bool live = lr < t.nrec && e < rc;
+        const int32_t idx = __builtin_amdgcn_ds_bpermute((int)((((uint32_t)(j - jb) + lr) & 63u) << 2), ic);
+        t.ld = live && (uint32_t)idx < v.nrows;  // (negative indices are large as unsigned)
+        t.from = send + (u64)(uint32_t)idx * v.stride_bytes + (u64)e * 2;
+        t.dst = make_rsrc(dbase + j * P, t.nrec * P);
+        t.off = live ? lr * P + e : kMxNowhere;
+        t.sc = live && !(lc & 1u) ? i * (kMxPassElems / kMxBlock) + lr * sb + (lc >> 1) : ~0u;
+        t.last = ++i == g.passes;
+        return true;
+      }
+      if (k >= 0 && j + g.rows < j1) {
+        j += g.rows;
+        if (j - jb >= 64) {
+          jb += 64;
+          ic = in;
+          in = fetch(jb + 64);
+        }
+      } else {
+        u64 j0 = 0;
+        do {
+          if (++k >= K) return false;
+        } while (!open(k, j0, j1, dbase, ioff) || j0 >= j1);
+        j = jb = j0;
+        ic = fetch(jb);
+        in = fetch(jb + 64);
+      }
+      i = 0;
+    }
+  };
+  auto load = [&](const MxPass& t, v4u& x0, v4u& x1) {
+    x0 = x1 = v4u{0u, 0u, 0u, 0u};
+    if (t.ld) {
+      x0 = __builtin_nontemporal_load(reinterpret_cast<const v4u_dw*>(t.from));
+      x1 = __builtin_nontemporal_load(reinterpret_cast<const v4u_dw*>(t.from + 16));
+    }
+  };
+  auto store = [&](const MxPass& t, const v4u& x0, const v4u& x1) {
+    uint32_t s;
+    const v4u y = mx_quant16<F16>(x0, x1, &s);
+    st_slot16(t.dst, t.off, y);
+    if (t.sc != ~0u) reinterpret_cast<uint8_t*>(strip)[t.sc] = (uint8_t)s;
+    if (!t.last) return;
+    // the strip: the scale bytes of the pass's records, record after record, sb bytes each
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t nv = g.rows == 1 ? sb >> 4 : 0u, dw = sb >> 2, at = nv * 4 + (uint32_t)lane;
+    if ((uint32_t)lane < nv) st_slot16(t.dst, rc + (uint32_t)lane * 16u, *reinterpret_cast<const v4u*>(strip + lane * 4));
+    if (at < t.nrec * dw) Scal<4>::st(t.dst, (at / dw) * P + rc + (at % dw) * 4u, strip[at]);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+  };
+  MxPass ta, tb;
+  v4u a0, a1, b0, b1;
+  if (!next(ta)) return;
+  load(ta, a0, a1);
+  for (;;) {
+    bool more = next(tb);
+    if (more) load(tb, b0, b1);
+    store(ta, a0, a1);
+    if (!more) break;
+    more = next(ta);
+    if (more) load(ta, a0, a1);
+    store(tb, b0, b1);
+    if (!more) break;
+  }
+}
+
+template <bool F16>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) rowsmx_push(CollParams p, MxArgs v) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  __shared__ __attribute__((aligned(16))) uint32_t s_strip[kMaxWaves][128];
+  uint32_t* const strip = s_strip[wave_id().wv];
+  read_half(p, s_tx, s_rx, [&p, &v, strip](u64 coff, uint32_t, int lane) {
+    const u64 soff = coff - (u64)p.rank * p.chunk_bytes, P = mx_record_bytes(v.rowcount);
+    const int n = p.n, r = p.rank, first = wave_id().w % (n - 1);
+    mx_walk<F16>(v, p.send, n, [&](int k, u64& j0, u64& j1, char*& dbase, u64& ioff) {
+      const int q = k < n - 1 ? direct_peer(n, r, 1 + (first + k) % (n - 1)) : r;  // the peers first, spread over the links
+      const u64 len = varblock_len_at(v.count[q] * P, p.slice_bytes, soff);
+      if (len == 0) return false;
+      mx_slice_records(soff, soff + len, P, &j0, &j1);
+      dbase = v.dst[q];
+      ioff = v.idx_off[q];
+      return true;
+    }, strip, lane);
+  });
+}
+
+// The same as a plain grid kernel into local memory: the whole call at one rank, and the pack of the
+// padded ring (block q into the stage at q * Mpad, the own block into recv).  blockIdx.y is the
+// destination; its records are dealt to the grid's waves in runs of whole passes.
+template <bool F16>
+__global__ void __launch_bounds__(256) rowsmx_pack(MxArgs v) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_strip[4][128];
+  const int q = blockIdx.y, lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const u64 count = v.count[q], waves = (u64)gridDim.x * 4, w = (u64)blockIdx.x * 4 + (u64)wv;
+  const uint32_t rows = mx_lanes(v.rowcount).rows;
+  const u64 run = ((count + waves - 1) / waves + rows - 1) / rows * rows;  // records per wave: whole passes
+  mx_walk<F16>(v, v.src, 1, [&](int, u64& j0, u64& j1, char*& dbase, u64& ioff) {
+    j0 = w * run < count ? w * run : count;
+    j1 = j0 + run < count ? j0 + run : count;
+    dbase = v.dst[q];
+    ioff = v.idx_off[q];
+    return true;
+  }, s_strip[wv], lane);
+}
+
 // ---------------------------------------------------------------- the combine
 // mncclAllToAllvCombine (combine_fold): rows_push transposed.  The token owner PULLS the up to topk
 // rows of each of its tokens out of the peers' dense send buffers (sc0 sc1 loads over the links,
@@ -3252,6 +3463,41 @@ hipError_t launch_rows_pack(int dtype, RowsPackArgs a, hipStream_t st) {
     hipLaunchKernelGGL(rows_pack<decltype(e)::value>, dim3(blocks, (unsigned)a.n), dim3(256), 0, st, a);
     return hipGetLastError();
   });
+}
+
+// what both MXFP8 kernels assume of their argument, checked before anything is launched: every access
+// they form is a dword-aligned 16-byte vector inside a row, a record or the wave's strip
+static bool mx_args_ok(int dtype, const MxArgs& v, const char* src, int n) {
+  if ((dtype != kBF16 && dtype != kF16) || n < 1 || n > kMaxRanks || !v.rowidx || !src) return false;
+  if (v.rowcount % kMxRowMultiple || v.rowcount < kMxRowMultiple || v.rowcount > kMxMaxRowcount) return false;
+  if (((u64)(uintptr_t)src | v.stride_bytes) % 4 || v.stride_bytes < (u64)v.rowcount * 2) return false;
+  for (int q = 0; q < n; ++q)
+    if (v.count[q] && (!v.dst[q] || (u64)(uintptr_t)v.dst[q] % 4)) return false;
+  return true;
+}
+
+hipError_t launch_rowsmx(int dtype, int C, int nt, const CollParams& p, const MxArgs& v, hipStream_t st) {
+  // (a rank whose counts are all zero passes a stand-in matrix and list, Comm::var_exchange: never read, but not NULL)
+  if (p.coll != kCollAllToAllVRowsMx || p.n < 2 || !mx_args_ok(dtype, v, p.send, p.n)) return hipErrorInvalidValue;
+  for (int q = 0; q < p.n; ++q)
+    if (v.count[q] * mx_record_bytes(v.rowcount) > p.chunk_bytes) return hipErrorInvalidValue;
+  if (dtype == kF16) hipLaunchKernelGGL(rowsmx_push<true>, dim3(C), dim3(nt), 0, st, p, v);
+  else hipLaunchKernelGGL(rowsmx_push<false>, dim3(C), dim3(nt), 0, st, p, v);
+  return hipGetLastError();
+}
+
+hipError_t launch_rowsmx_pack(int dtype, const MxArgs& v, hipStream_t st) {
+  if (!mx_args_ok(dtype, v, v.src, v.n)) return hipErrorInvalidValue;
+  u64 most = 0;
+  for (int q = 0; q < v.n; ++q) most = v.count[q] > most ? v.count[q] : most;
+  if (most == 0) return hipSuccess;
+  // a wave per pass of the longest block, four to a workgroup; the rest by the waves' runs
+  const MxLanes g = mx_lanes(v.rowcount);
+  const u64 want = ((most + g.rows - 1) / g.rows + 3) / 4;
+  const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);
+  if (dtype == kF16) hipLaunchKernelGGL(rowsmx_pack<true>, dim3(blocks, (unsigned)v.n), dim3(256), 0, st, v);
+  else hipLaunchKernelGGL(rowsmx_pack<false>, dim3(blocks, (unsigned)v.n), dim3(256), 0, st, v);
+  return hipGetLastError();
 }
 
 // the combine's datatypes: the ones with a float to fold in

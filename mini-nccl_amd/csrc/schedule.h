@@ -170,7 +170,10 @@ enum Coll : int {
   kCollAllToAllVRows = 11,
   // mncclAllToAllvCombine: the way back -- the owner pulls its tokens' rows out of the peers' send and
   // folds them by weight (combine.h); its fallback is kCollAllToAllV's padded ring in front of a local fold
-  kCollAllToAllVCombine = 12
+  kCollAllToAllVCombine = 12,
+  // mncclAllToAllvRowsMxfp8: kCollAllToAllVRows whose rows are quantised to MXFP8 records on the way
+  // out (mxblock.h); its fallback is kCollAllToAllV's padded ring behind a gather-and-quantise kernel
+  kCollAllToAllVRowsMx = 13
 };
 
 // r, root: gather and scatter only (their op count depends on the rank's place in the chain; the

@@ -1590,6 +1590,42 @@ int mnccl_sim_rows_exchange(int n, int esz, uint64_t slice_bytes, const uint8_t*
   return 0;
 }
 
+// csrc/mxblock.h, the rules of mncclAllToAllvRowsMxfp8, for the CPU suite: one rank's local checks (an
+// MxLocal or RowsLocal verdict; the buffers are only compared, never dereferenced), the record's size
+// and a slice's records, the host quantiser over `nrows` dense rows, and kernels.hip rowsmx_push's
+// walk over one block of `count` records in a geometry cut for `max_count`: owners[j] becomes the
+// number of slices that take record j (the rule wants exactly 1).
+int mnccl_sim_mx_check_local(int n, int esz, const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                             const size_t* sendcounts, const size_t* sdispls, const void* recv, const size_t* recvcounts,
+                             const size_t* rdispls, size_t rowcount) {
+  if (n < 1 || n > mnccl::kVarMaxRanks || esz < 1) return -2;
+  return mnccl::mx_check_local(n, esz, send, nrows, rowstride, rowidx, sendcounts, sdispls, recv, recvcounts, rdispls,
+                               rowcount);
+}
+uint64_t mnccl_sim_mx_record_bytes(uint64_t rowcount) { return mnccl::mx_record_bytes(rowcount); }
+void mnccl_sim_mx_slice_records(uint64_t a, uint64_t b, uint64_t P, uint64_t* out) {
+  mnccl::mx_slice_records(a, b, P, &out[0], &out[1]);
+}
+int mnccl_sim_mx_quantise(const uint16_t* rows, int f16, uint32_t rowcount, uint64_t nrows, uint8_t* out) {
+  if (rowcount % mnccl::kMxBlock) return -2;
+  for (uint64_t t = 0; t < nrows; ++t)
+    mnccl::mx_quantise_row(rows + t * rowcount, f16 != 0, rowcount, out + t * mnccl::mx_record_bytes(rowcount));
+  return 0;
+}
+int mnccl_sim_mx_owners(uint64_t count, uint64_t max_count, uint64_t rowcount, uint64_t slice_bytes, uint32_t* owners) {
+  if (slice_bytes == 0 || count > max_count) return -2;
+  const uint64_t P = mnccl::mx_record_bytes(rowcount);
+  for (uint64_t a = 0; a < max_count * P; a += slice_bytes) {
+    const uint64_t len = mnccl::varblock_len_at(count * P, slice_bytes, a);
+    if (len == 0) continue;
+    uint64_t j0, j1;
+    mnccl::mx_slice_records(a, a + len, P, &j0, &j1);
+    if (j1 > count) return -3;
+    for (uint64_t j = j0; j < j1; ++j) ++owners[j];
+  }
+  return 0;
+}
+
 // csrc/combine.h, the host-side rules of mncclAllToAllvCombine, for the CPU suite: one rank's local
 // checks (a CombineLocal verdict; the buffers are only compared, never dereferenced), and the kernels'
 // argument block (out: n lo[], n cnt[], n src_off[], then vec) with the owner of each of `nj`

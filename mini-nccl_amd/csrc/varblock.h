@@ -36,7 +36,10 @@ enum : uint32_t {
   // above; the puller needs what ncclAllToAllv keeps private, so `rdispls` carries the rank's SEND
   // displacements (its recv displacements name positions of a virtual sequence: nobody else's business),
   // and `nrows` its output rows -- the call's geometry follows the longest output (combine_max_rows)
-  kVarCombine = 8u
+  kVarCombine = 8u,
+  // the row of an mncclAllToAllvRowsMxfp8 call (mxblock.h), set beside kVarRows: the counts are MXFP8
+  // records of `pad` elements
+  kVarRowsMx = 16u
 };
 
 // The local checks' verdicts, in the order they are made
