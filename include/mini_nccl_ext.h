@@ -41,6 +41,7 @@
  *                        index list (a MoE router's output as it is: no permutation pass in front).
  *   mncclAllToAllvRowsMxfp8  the same from a bf16 / fp16 matrix with every row quantised to MXFP8 on the
  *                        way out: e4m3 elements and one E8M0 scale per 32, in one record per row.
+ *   mncclAllToAllvRowsMxfp4  the same with e2m1 elements, two to a byte: MXFP4 records.
  *   mncclAllToAllvCombine  the way back: the token owner pulls the top-k rows of each token out of the
  *                        experts' send buffers and folds them by gate weight (no packed recv, no atomics).
  *
@@ -108,7 +109,8 @@ extern "C" {
    p2p_direct_sends -- mncclCommGetInfoV writes them to a caller whose struct has room); still 600:
    mncclAllGatherv and mncclReduceScatterv were added the same way (detected by symbol;
    mncclCommInfo_t did not grow); still 600: mncclAllToAllvRows was added the same way; still 600:
-   mncclAllToAllvRowsMxfp8 was added the same way */
+   mncclAllToAllvRowsMxfp8 was added the same way; still 600: mncclAllToAllvRowsMxfp4 was added the
+   same way */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -496,6 +498,45 @@ ncclResult_t mncclAllToAllvRows(const void* sendbuff, size_t nrows, size_t rowst
  * input, rows that are no multiple of 128, a separate scales buffer, an fp8 way back, registered
  * windows. */
 ncclResult_t mncclAllToAllvRowsMxfp8(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                                     const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                                     const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
+                                     ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
+
+/* mncclAllToAllvRowsMxfp8 with MXFP4 records: e2m1 elements, two to a byte, with one E8M0 scale per 32
+ * -- the narrowest operands of gfx950's scaled MFMA forms, 0.53 bytes per element on the wire instead
+ * of 1.03 (MXFP8) or 2 (bf16); both figures are counts from the layout.  Detected by symbol
+ * (MNCCL_VERSION stays 600).
+ *
+ * The send side is mncclAllToAllvRowsMxfp8's: the strided bf16 / fp16 matrix, the device-side int32
+ * index list read when the call runs (at replay, for a captured call), counts and displacements in
+ * rows, an index outside [0, nrows) standing for a row of zeros and causing no access.
+ *
+ * The receive side.  Each delivered row is one RECORD of P4 = rowcount / 2 + rowcount / 32 bytes: first
+ * rowcount / 2 element bytes, element 2i in the low nibble of byte i and element 2i + 1 in the high
+ * one, then rowcount / 32 scale bytes, one per block of 32 consecutive elements.  recvcounts / rdispls
+ * are in records; bytes outside every block are never written.
+ *
+ * Result, bit for bit on every schedule.  Per block of 32 elements, each widened exactly to f32: E is
+ * the largest biased exponent field of the 32 magnitudes.  E == 255 (a NaN or an infinity in the
+ * block): scale byte 0xFF and all 16 element bytes 0x77 -- the largest magnitude, so that a consumer
+ * which reads 0xFF as a large finite scale still sees a non-finite product.  Otherwise the scale byte
+ * is s = max(E - 2, 0) (OCP MX v1.0: floor(log2(amax)) - emax(e2m1), clamped at the bottom) and each
+ * element is e2m1 of x * 2^(127 - s): the scaling exact (subnormal inputs are not flushed), one
+ * rounding to nearest, ties to the even code, on the grid {0, 0.5, 1, 1.5, 2, 3, 4, 6}; magnitudes
+ * above 6 saturate to 6 (the block's largest element lands in [4, 8)); the sign is kept, on zero too
+ * (code 0x8 is -0).  With a = |x * 2^(127 - s)| the magnitude code is (a > 0.25) + (a >= 0.75) +
+ * (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5).  A block of zeros gives scale 0x00 and
+ * nibbles 0x0 / 0x8.
+ *
+ * Checks: mncclAllToAllvRowsMxfp8's, in its order and with its verdicts; the receive side's overlap,
+ * overflow and NULL checks count P4 bytes per row.  The call has a collective id of its own: ranks
+ * that mix it with mncclAllToAllvRowsMxfp8, or that differ in rowcount, get ncclInvalidUsage on every
+ * rank with nothing launched.
+ *
+ * Schedules: mncclAllToAllvRowsMxfp8's, a kernel pair of its own (a lane quantises a whole block of 32).
+ * Not built: FP6 and e5m2, block sizes other than 32, f32 input, a separate or pre-shuffled scales
+ * buffer, rows that are no multiple of 128, registered windows, an FP4 way back. */
+ncclResult_t mncclAllToAllvRowsMxfp4(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
                                      const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                                      const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
                                      ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);

@@ -149,7 +149,15 @@ class Comm {
   ncclResult_t all_to_all_v_rows_mx(const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
                                     const size_t* sendcounts, const size_t* sdispls, void* recv, const size_t* recvcounts,
                                     const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream) {
-    const RowsCall rows{nrows, rowstride, rowcount, rowidx, true};
+    const RowsCall rows{nrows, rowstride, rowcount, rowidx, kRowsMxfp8};
+    return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
+  }
+  // And with MXFP4 records (mncclAllToAllvRowsMxfp4: rowcount / 2 + rowcount / 32 bytes, mxblock.h's mx4_
+  // rules): kernels.hip rowsmx4_push on the read schedule; else rowsmx4_pack into the padded ring's stage.
+  ncclResult_t all_to_all_v_rows_mx4(const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                                     const size_t* sendcounts, const size_t* sdispls, void* recv, const size_t* recvcounts,
+                                     const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream) {
+    const RowsCall rows{nrows, rowstride, rowcount, rowidx, kRowsMxfp4};
     return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
   }
 
@@ -288,10 +296,12 @@ class Comm {
                    uint64_t scalar = 0);
   // the one call path of ncclAllToAllv (rows == nullptr: counts and displacements in elements of
   // `send`) and mncclAllToAllvRows (in rows of the matrix `rows` describes at `send`)
+  // what a delivered row is: the row itself, or its MXFP8 / MXFP4 record (mxblock.h)
+  enum RowsFormat { kRowsPlain, kRowsMxfp8, kRowsMxfp4 };
   struct RowsCall {
     size_t nrows, rowstride, rowcount;
     const int32_t* rowidx;
-    bool mx = false;  // mncclAllToAllvRowsMxfp8: the rows leave as MXFP8 records (mxblock.h)
+    RowsFormat fmt = kRowsPlain;
   };
   ncclResult_t var_exchange(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
                             const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream,

@@ -159,6 +159,10 @@ hipError_t launch_rowsmx(int dtype, int channels, int threads, const CollParams&
 // The same gather and quantise into local memory as a plain grid launch (kernels.hip rowsmx_pack):
 // block q's records packed at v.dst[q] out of the matrix at v.src, for every q < v.n.
 hipError_t launch_rowsmx_pack(int dtype, const MxArgs& v, hipStream_t stream);
+// mncclAllToAllvRowsMxfp4 (kernels.hip rowsmx4_push, rowsmx4_pack): the two launches above with records
+// of mx4_record_bytes(rowcount) bytes, p.coll kCollAllToAllVRowsMx4 and the same argument checks.
+hipError_t launch_rowsmx4(int dtype, int channels, int threads, const CollParams& p, const MxArgs& v, hipStream_t stream);
+hipError_t launch_rowsmx4_pack(int dtype, const MxArgs& v, hipStream_t stream);
 // mncclAllToAllvCombine on the read schedule (kernels.hip combine_fold): CombineArgs (combine.h), a
 // second by-value kernel argument.  p: p.coll kCollAllToAllVCombine; the geometry for chunk_bytes = the
 // longest output matrix of any rank in bytes of packed rows, p.recv this rank's matrix, p.peer_send

@@ -38,6 +38,8 @@
 //  rowsmx_push / rowsmx_pack   the same from a bf16 / fp16 matrix with every row quantised to an MXFP8
 //                 record on the way out (mncclAllToAllvRowsMxfp8): e4m3 elements, one E8M0 scale byte
 //                 per 32; a lane pair per block, the scale bytes through a per-wave LDS strip.
+//  rowsmx4_push / rowsmx4_pack   the same walk for MXFP4 records (mncclAllToAllvRowsMxfp4): e2m1 nibbles,
+//                 a lane per block -- four vector loads, a lane-local amax, one vector store.
 //  combine_fold / combine_local   the way back of that layer (mncclAllToAllvCombine): the token owner
 //                 pulls the top-k rows of each of its tokens out of the peers' send, folds them by gate
 //                 weight in float in slot order and stores one row; vhalf_fold's protocol, the geometry
@@ -2149,13 +2151,85 @@ __device__ __forceinline__ v4u mx_quant16(const v4u& a, const v4u& b, uint32_t* 
   return r;
 }
 
-// an offset beyond every pass's descriptor (at most 8 records of 16896 bytes) that no 32-bit sum wraps
+// mncclAllToAllvRowsMxfp4 (rowsmx4_push, rowsmx4_pack): the same walk with a lane layout of its own.
+// An e2m1 block is 16 bytes of output, one lane's vector store, so a lane owns a WHOLE block: four
+// 16-byte non-temporal loads bring its 32 consecutive elements, the amax is lane-local -- no DPP, no
+// partner lane -- and every live lane writes a scale byte into the strip.  A pass is 64 x 32 = 2048
+// elements (mx4_lanes).  The amax is taken on the 16-bit patterns, two per v_pk_max_u16: bf16 and fp16
+// magnitudes both order as their bits do, so only the block's largest pattern is widened for E.
+// Then per element: widen, v_ldexp_f32 by 127 - s (exact, f32 denormals on), and the e2m1 code from
+// the seven comparisons of the rule (mxblock.h) -- ties to the even code and saturation to 6 fall out
+// of which of them are strict -- with the sign bit moved to bit 3.  Source vector d (elements 8d ..
+// 8d + 7) becomes dword d of the output vector, element 2i in the low nibble of byte i.  A block with
+// E == 255 becomes 0x77 bytes by a select.
+__device__ __forceinline__ uint32_t e2m1_code(float y) {
+  const float a = __builtin_fabsf(y);
+  return ((__float_as_uint(y) >> 28) & 8u) | (uint32_t)((a > 0.25f) + (a >= 0.75f) + (a > 1.25f) + (a >= 1.75f) +
+                                                        (a > 2.5f) + (a >= 3.5f) + (a > 5.0f));
+}
+
+template <bool F16>
+__device__ __forceinline__ v4u mx4_quant32(const v4u (&x)[4], uint32_t* scale) {
+  typedef uint16_t v2h __attribute__((ext_vector_type(2)));
+  v2h m2 = {0, 0};
+#pragma unroll
+  for (int d = 0; d < 16; ++d)
+    m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(v2h, x[d >> 2][d & 3] & 0x7fff7fffu));
+  const uint16_t am = m2[0] > m2[1] ? m2[0] : m2[1];
+  uint32_t E;
+  if constexpr (F16) E = __float_as_uint((float)__builtin_bit_cast(_Float16, am)) >> 23;
+  else E = (uint32_t)am >> 7;
+  const uint32_t s = mx4_scale_byte(E);
+  *scale = s;
+  const int sh = 127 - (int)s;
+  v4u r;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const uint32_t u = x[d][e];
+      float lo, hi;
+      if constexpr (F16) {
+        lo = (float)__builtin_bit_cast(_Float16, (uint16_t)u);
+        hi = (float)__builtin_bit_cast(_Float16, (uint16_t)(u >> 16));
+      } else {
+        lo = __uint_as_float(u << 16);
+        hi = __uint_as_float(u & 0xffff0000u);
+      }
+      w |= (e2m1_code(__builtin_ldexpf(lo, sh)) | e2m1_code(__builtin_ldexpf(hi, sh)) << 4) << (8 * e);
+    }
+    r[d] = s == 255u ? 0x77777777u : w;
+  }
+  return r;
+}
+
+// What the walk needs to know of a format: a lane's elements per pass (64 source bytes at most), the
+// element bytes of a record, the lane split, and the quantiser of a lane's elements into one vector
+struct MxFp8 {
+  static constexpr uint32_t kLaneElems = 16;
+  static __device__ __forceinline__ uint32_t elem_bytes(uint32_t rc) { return rc; }
+  static __device__ __forceinline__ MxLanes lanes(uint32_t rc) { return mx_lanes(rc); }
+  template <bool F16>
+  static __device__ __forceinline__ v4u quant(const v4u (&x)[2], uint32_t* s) { return mx_quant16<F16>(x[0], x[1], s); }
+};
+struct MxFp4 {
+  static constexpr uint32_t kLaneElems = 32;
+  static __device__ __forceinline__ uint32_t elem_bytes(uint32_t rc) { return rc / 2; }
+  static __device__ __forceinline__ MxLanes lanes(uint32_t rc) { return mx4_lanes(rc); }
+  template <bool F16>
+  static __device__ __forceinline__ v4u quant(const v4u (&x)[4], uint32_t* s) { return mx4_quant32<F16>(x, s); }
+};
+
+// an offset beyond every pass's descriptor (a pass's records hold one output vector per lane: under
+// 2 KiB with their scale bytes when rows share it, one record of at most 16896 bytes else) that no
+// 32-bit sum wraps
 constexpr uint32_t kMxNowhere = 0x40000000u;
 
-// One pass: a wave's 64 x 16 elements, of one row (wide) or of up to g.rows rows (narrow)
+// One pass: a wave's 64 x 16 (MXFP4: 64 x 32) elements, of one row (wide) or of up to g.rows rows (narrow)
 struct MxPass {
   rsrc_t dst;        // the pass's records, from the first one's first byte
-  const char* from;  // this lane's 32 source bytes
+  const char* from;  // this lane's 32 (64) source bytes
   uint32_t off;      // where this lane's 16 element bytes go in dst (kMxNowhere: an idle lane)
   uint32_t sc;       // where this lane's scale byte goes in the strip (~0u: not this lane's to write)
   uint32_t nrec;     // records of the pass
@@ -2165,11 +2239,13 @@ struct MxPass {
 
 // open(k, j0, j1, dbase, ioff): destination k < K's records [j0, j1) of its block, the block's first
 // byte at the destination and its first entry of rowidx; false: nothing for k
-template <bool F16, typename Open>
+template <typename Fmt, bool F16, typename Open>
 __device__ __forceinline__ void mx_walk(const MxArgs& v, const char* send, int K, const Open& open, uint32_t* strip,
                                         int lane) {
-  const uint32_t rc = v.rowcount, sb = rc / kMxBlock, P = rc + sb;
-  const MxLanes g = mx_lanes(rc);
+  constexpr uint32_t kLane = Fmt::kLaneElems, kPass = 64u * kLane, kVecs = kLane / 8u;  // (a vector: 8 source elements)
+  constexpr uint32_t kPerBlock = kMxBlock / kLane;                                      // lanes per scale byte
+  const uint32_t rc = v.rowcount, sb = rc / kMxBlock, eb = Fmt::elem_bytes(rc), P = eb + sb;
+  const MxLanes g = Fmt::lanes(rc);
   const uint32_t lr = (uint32_t)lane / g.lanes, lc = (uint32_t)lane % g.lanes;
   int k = -1;
   u64 j = 0, j1 = 0, jb = 0, ioff = 0;
@@ -2185,14 +2261,15 @@ __device__ __forceinline__ void mx_walk(const MxArgs& v, const char* send, int K
       if (k >= 0 && i < g.passes) {
         const u64 left = j1 - j;
         t.nrec = left < g.rows ? (uint32_t)left : g.rows;
-        const uint32_t e = i * kMxPassElems + lc * 16u;  // this lane's first element of its row
+        const uint32_t e = i * kPass + lc * kLane;  // this lane's first element of its row
         const bool live = lr < t.nrec && e < rc;
+        // (j - jb is a multiple of g.rows below 64 and g.rows divides 64, MxLanes: a live lane's record is in ic)
         const int32_t idx = __builtin_amdgcn_ds_bpermute((int)((((uint32_t)(j - jb) + lr) & 63u) << 2), ic);
         t.ld = live && (uint32_t)idx < v.nrows;  // (negative indices are large as unsigned)
         t.from = send + (u64)(uint32_t)idx * v.stride_bytes + (u64)e * 2;
         t.dst = make_rsrc(dbase + j * P, t.nrec * P);
-        t.off = live ? lr * P + e : kMxNowhere;
-        t.sc = live && !(lc & 1u) ? i * (kMxPassElems / kMxBlock) + lr * sb + (lc >> 1) : ~0u;
+        t.off = live ? lr * P + e / kLane * 16u : kMxNowhere;
+        t.sc = live && lc % kPerBlock == 0 ? i * (kPass / kMxBlock) + lr * sb + lc / kPerBlock : ~0u;
         t.last = ++i == g.passes;
         return true;
       }
@@ -2215,16 +2292,17 @@ __device__ __forceinline__ void mx_walk(const MxArgs& v, const char* send, int K
       i = 0;
     }
   };
-  auto load = [&](const MxPass& t, v4u& x0, v4u& x1) {
-    x0 = x1 = v4u{0u, 0u, 0u, 0u};
+  auto load = [&](const MxPass& t, v4u (&x)[kVecs]) {
+#pragma unroll
+    for (uint32_t d = 0; d < kVecs; ++d) x[d] = v4u{0u, 0u, 0u, 0u};
     if (t.ld) {
-      x0 = __builtin_nontemporal_load(reinterpret_cast<const v4u_dw*>(t.from));
-      x1 = __builtin_nontemporal_load(reinterpret_cast<const v4u_dw*>(t.from + 16));
+#pragma unroll
+      for (uint32_t d = 0; d < kVecs; ++d) x[d] = __builtin_nontemporal_load(reinterpret_cast<const v4u_dw*>(t.from + 16 * d));
     }
   };
-  auto store = [&](const MxPass& t, const v4u& x0, const v4u& x1) {
+  auto store = [&](const MxPass& t, const v4u (&x)[kVecs]) {
     uint32_t s;
-    const v4u y = mx_quant16<F16>(x0, x1, &s);
+    const v4u y = Fmt::template quant<F16>(x, &s);
     st_slot16(t.dst, t.off, y);
     if (t.sc != ~0u) reinterpret_cast<uint8_t*>(strip)[t.sc] = (uint8_t)s;
     if (!t.last) return;
@@ -2232,36 +2310,36 @@ __device__ __forceinline__ void mx_walk(const MxArgs& v, const char* send, int K
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
     const uint32_t nv = g.rows == 1 ? sb >> 4 : 0u, dw = sb >> 2, at = nv * 4 + (uint32_t)lane;
-    if ((uint32_t)lane < nv) st_slot16(t.dst, rc + (uint32_t)lane * 16u, *reinterpret_cast<const v4u*>(strip + lane * 4));
-    if (at < t.nrec * dw) Scal<4>::st(t.dst, (at / dw) * P + rc + (at % dw) * 4u, strip[at]);
+    if ((uint32_t)lane < nv) st_slot16(t.dst, eb + (uint32_t)lane * 16u, *reinterpret_cast<const v4u*>(strip + lane * 4));
+    if (at < t.nrec * dw) Scal<4>::st(t.dst, (at / dw) * P + eb + (at % dw) * 4u, strip[at]);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
   };
   MxPass ta, tb;
-  v4u a0, a1, b0, b1;
+  v4u xa[kVecs], xb[kVecs];
   if (!next(ta)) return;
-  load(ta, a0, a1);
+  load(ta, xa);
   for (;;) {
     bool more = next(tb);
-    if (more) load(tb, b0, b1);
-    store(ta, a0, a1);
+    if (more) load(tb, xb);
+    store(ta, xa);
     if (!more) break;
     more = next(ta);
-    if (more) load(ta, a0, a1);
-    store(tb, b0, b1);
+    if (more) load(ta, xa);
+    store(tb, xb);
     if (!more) break;
   }
 }
 
-template <bool F16>
-__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) rowsmx_push(CollParams p, MxArgs v) {
+template <typename Fmt, bool F16>
+__device__ __forceinline__ void mx_push(const CollParams& p, const MxArgs& v) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   __shared__ __attribute__((aligned(16))) uint32_t s_strip[kMaxWaves][128];
   uint32_t* const strip = s_strip[wave_id().wv];
   read_half(p, s_tx, s_rx, [&p, &v, strip](u64 coff, uint32_t, int lane) {
-    const u64 soff = coff - (u64)p.rank * p.chunk_bytes, P = mx_record_bytes(v.rowcount);
+    const u64 soff = coff - (u64)p.rank * p.chunk_bytes, P = (u64)Fmt::elem_bytes(v.rowcount) + v.rowcount / kMxBlock;
     const int n = p.n, r = p.rank, first = wave_id().w % (n - 1);
-    mx_walk<F16>(v, p.send, n, [&](int k, u64& j0, u64& j1, char*& dbase, u64& ioff) {
+    mx_walk<Fmt, F16>(v, p.send, n, [&](int k, u64& j0, u64& j1, char*& dbase, u64& ioff) {
       const int q = k < n - 1 ? direct_peer(n, r, 1 + (first + k) % (n - 1)) : r;  // the peers first, spread over the links
       const u64 len = varblock_len_at(v.count[q] * P, p.slice_bytes, soff);
       if (len == 0) return false;
@@ -2272,24 +2350,40 @@ __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) rowsmx_push(Col
     }, strip, lane);
   });
 }
+template <bool F16>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) rowsmx_push(CollParams p, MxArgs v) {
+  mx_push<MxFp8, F16>(p, v);
+}
+template <bool F16>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) rowsmx4_push(CollParams p, MxArgs v) {
+  mx_push<MxFp4, F16>(p, v);
+}
 
 // The same as a plain grid kernel into local memory: the whole call at one rank, and the pack of the
 // padded ring (block q into the stage at q * Mpad, the own block into recv).  blockIdx.y is the
 // destination; its records are dealt to the grid's waves in runs of whole passes.
-template <bool F16>
-__global__ void __launch_bounds__(256) rowsmx_pack(MxArgs v) {
+template <typename Fmt, bool F16>
+__device__ __forceinline__ void mx_pack(const MxArgs& v) {
   __shared__ __attribute__((aligned(16))) uint32_t s_strip[4][128];
   const int q = blockIdx.y, lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const u64 count = v.count[q], waves = (u64)gridDim.x * 4, w = (u64)blockIdx.x * 4 + (u64)wv;
-  const uint32_t rows = mx_lanes(v.rowcount).rows;
+  const uint32_t rows = Fmt::lanes(v.rowcount).rows;
   const u64 run = ((count + waves - 1) / waves + rows - 1) / rows * rows;  // records per wave: whole passes
-  mx_walk<F16>(v, v.src, 1, [&](int, u64& j0, u64& j1, char*& dbase, u64& ioff) {
+  mx_walk<Fmt, F16>(v, v.src, 1, [&](int, u64& j0, u64& j1, char*& dbase, u64& ioff) {
     j0 = w * run < count ? w * run : count;
     j1 = j0 + run < count ? j0 + run : count;
     dbase = v.dst[q];
     ioff = v.idx_off[q];
     return true;
   }, s_strip[wv], lane);
+}
+template <bool F16>
+__global__ void __launch_bounds__(256) rowsmx_pack(MxArgs v) {
+  mx_pack<MxFp8, F16>(v);
+}
+template <bool F16>
+__global__ void __launch_bounds__(256) rowsmx4_pack(MxArgs v) {
+  mx_pack<MxFp4, F16>(v);
 }
 
 // ---------------------------------------------------------------- the combine
@@ -3465,7 +3559,7 @@ hipError_t launch_rows_pack(int dtype, RowsPackArgs a, hipStream_t st) {
   });
 }
 
-// what both MXFP8 kernels assume of their argument, checked before anything is launched: every access
+// what the MXFP8 and MXFP4 kernels assume of their argument, checked before anything is launched: every access
 // they form is a dword-aligned 16-byte vector inside a row, a record or the wave's strip
 static bool mx_args_ok(int dtype, const MxArgs& v, const char* src, int n) {
   if ((dtype != kBF16 && dtype != kF16) || n < 1 || n > kMaxRanks || !v.rowidx || !src) return false;
@@ -3476,29 +3570,42 @@ static bool mx_args_ok(int dtype, const MxArgs& v, const char* src, int n) {
   return true;
 }
 
-hipError_t launch_rowsmx(int dtype, int C, int nt, const CollParams& p, const MxArgs& v, hipStream_t st) {
+// fp4: the MXFP4 kernels and their record (launch_rowsmx4, launch_rowsmx4_pack)
+static hipError_t launch_mx_push(bool fp4, int dtype, int C, int nt, const CollParams& p, const MxArgs& v, hipStream_t st) {
   // (a rank whose counts are all zero passes a stand-in matrix and list, Comm::var_exchange: never read, but not NULL)
-  if (p.coll != kCollAllToAllVRowsMx || p.n < 2 || !mx_args_ok(dtype, v, p.send, p.n)) return hipErrorInvalidValue;
+  if (p.coll != (fp4 ? kCollAllToAllVRowsMx4 : kCollAllToAllVRowsMx) || p.n < 2 || !mx_args_ok(dtype, v, p.send, p.n))
+    return hipErrorInvalidValue;
+  const u64 P = fp4 ? mx4_record_bytes(v.rowcount) : mx_record_bytes(v.rowcount);
   for (int q = 0; q < p.n; ++q)
-    if (v.count[q] * mx_record_bytes(v.rowcount) > p.chunk_bytes) return hipErrorInvalidValue;
-  if (dtype == kF16) hipLaunchKernelGGL(rowsmx_push<true>, dim3(C), dim3(nt), 0, st, p, v);
-  else hipLaunchKernelGGL(rowsmx_push<false>, dim3(C), dim3(nt), 0, st, p, v);
+    if (v.count[q] * P > p.chunk_bytes) return hipErrorInvalidValue;
+  auto* const k = fp4 ? (dtype == kF16 ? rowsmx4_push<true> : rowsmx4_push<false>)
+                      : (dtype == kF16 ? rowsmx_push<true> : rowsmx_push<false>);
+  hipLaunchKernelGGL(k, dim3(C), dim3(nt), 0, st, p, v);
   return hipGetLastError();
 }
+hipError_t launch_rowsmx(int dtype, int C, int nt, const CollParams& p, const MxArgs& v, hipStream_t st) {
+  return launch_mx_push(false, dtype, C, nt, p, v, st);
+}
+hipError_t launch_rowsmx4(int dtype, int C, int nt, const CollParams& p, const MxArgs& v, hipStream_t st) {
+  return launch_mx_push(true, dtype, C, nt, p, v, st);
+}
 
-hipError_t launch_rowsmx_pack(int dtype, const MxArgs& v, hipStream_t st) {
+static hipError_t launch_mx_pack(bool fp4, int dtype, const MxArgs& v, hipStream_t st) {
   if (!mx_args_ok(dtype, v, v.src, v.n)) return hipErrorInvalidValue;
   u64 most = 0;
   for (int q = 0; q < v.n; ++q) most = v.count[q] > most ? v.count[q] : most;
   if (most == 0) return hipSuccess;
   // a wave per pass of the longest block, four to a workgroup; the rest by the waves' runs
-  const MxLanes g = mx_lanes(v.rowcount);
+  const MxLanes g = fp4 ? mx4_lanes(v.rowcount) : mx_lanes(v.rowcount);
   const u64 want = ((most + g.rows - 1) / g.rows + 3) / 4;
   const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);
-  if (dtype == kF16) hipLaunchKernelGGL(rowsmx_pack<true>, dim3(blocks, (unsigned)v.n), dim3(256), 0, st, v);
-  else hipLaunchKernelGGL(rowsmx_pack<false>, dim3(blocks, (unsigned)v.n), dim3(256), 0, st, v);
+  auto* const k = fp4 ? (dtype == kF16 ? rowsmx4_pack<true> : rowsmx4_pack<false>)
+                      : (dtype == kF16 ? rowsmx_pack<true> : rowsmx_pack<false>);
+  hipLaunchKernelGGL(k, dim3(blocks, (unsigned)v.n), dim3(256), 0, st, v);
   return hipGetLastError();
 }
+hipError_t launch_rowsmx_pack(int dtype, const MxArgs& v, hipStream_t st) { return launch_mx_pack(false, dtype, v, st); }
+hipError_t launch_rowsmx4_pack(int dtype, const MxArgs& v, hipStream_t st) { return launch_mx_pack(true, dtype, v, st); }
 
 // the combine's datatypes: the ones with a float to fold in
 template <typename F>

@@ -12,6 +12,14 @@
 // of the 32 magnitudes.  E == 255 (a NaN or an infinity): scale 0xFF, every element 0x7F.  Else the
 // scale byte is s = max(E - 8, 0) and element x becomes encode_e4m3(x * 2^(127 - s)): exact scaling,
 // one rounding to nearest even, finite overflow saturated to +-448, the sign of zero kept.
+//
+// mncclAllToAllvRowsMxfp4 (the mx4_ names; kernels.hip rowsmx4_push, rowsmx4_pack) is the same call with
+// e2m1 elements, two to a byte: a record is P4 = rowcount / 2 + rowcount / 32 bytes, element 2i in the
+// low nibble of byte i and element 2i + 1 in the high one, then the scale bytes.  E == 255: scale 0xFF,
+// every element byte 0x77 (+6, +6).  Else s = max(E - 2, 0) and element x becomes the code of
+// x * 2^(127 - s) on the grid {0, 0.5, 1, 1.5, 2, 3, 4, 6}: exact scaling, one rounding to nearest, ties
+// to the even code, magnitudes above 6 saturated to 6, the sign kept (0x8 is -0).  The slice rule, the
+// local checks and the kernels' argument block are the ones below, with P4 for P.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -28,11 +36,15 @@ constexpr uint32_t kMxRowMultiple = 128;    // records and their scale parts are
 constexpr uint32_t kMxMaxRowcount = 16384;  // 512 scale bytes: the kernels' per-wave LDS strip
 constexpr uint32_t kMxPassElems = 1024;     // elements a wave quantises per pass: 16 per lane
 
+constexpr uint32_t kMx4PassElems = 2048;    // the same for MXFP4: 32 per lane, a block per lane
+
 // bytes of one record
 MNCCL_HD uint64_t mx_record_bytes(uint64_t rowcount) { return rowcount + rowcount / kMxBlock; }
+MNCCL_HD uint64_t mx4_record_bytes(uint64_t rowcount) { return rowcount / 2 + rowcount / kMxBlock; }
 
 // the E8M0 scale byte of a block whose largest magnitude has f32 exponent field E
 MNCCL_HD uint32_t mx_scale_byte(uint32_t E) { return E == 255u ? 255u : E > 8u ? E - 8u : 0u; }
+MNCCL_HD uint32_t mx4_scale_byte(uint32_t E) { return E == 255u ? 255u : E > 2u ? E - 2u : 0u; }
 
 // The slice rule.  A block is the virtual packed sequence of its records and the call's slices are
 // cut for the largest block (varblock_len_at), so slice [a, b) may begin and end inside a record.  A
@@ -50,11 +62,12 @@ enum MxLocal : int {
   kMxAlign = 17      // sendbuff, rowstride in bytes, or recvbuff not dword-aligned
 };
 
-// One rank's arguments; esz: the SEND element size (2).  The receive side gets rows_check_local's
-// overlap, overflow and NULL checks with P for the row's bytes: the check is made twice, once per side.
+// One rank's arguments; esz: the SEND element size (2); P: the record's bytes (mx_record_bytes or
+// mx4_record_bytes of rowcount).  The receive side gets rows_check_local's overlap, overflow and NULL
+// checks with P for the row's bytes: the check is made twice, once per side.
 inline int mx_check_local(int n, int esz, const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
                           const size_t* sendcounts, const size_t* sdispls, const void* recv, const size_t* recvcounts,
-                          const size_t* rdispls, size_t rowcount) {
+                          const size_t* rdispls, size_t rowcount, uint64_t P) {
   if (rowcount % kMxRowMultiple || rowcount < kMxRowMultiple || rowcount > kMxMaxRowcount) return kMxRowcount;
   if (((uint64_t)(uintptr_t)send | (uint64_t)(uintptr_t)recv | (uint64_t)rowstride * (uint64_t)esz) % 4) return kMxAlign;
   if (rowstride < rowcount) return kRowsStride;
@@ -67,7 +80,6 @@ inline int mx_check_local(int n, int esz, const void* send, size_t nrows, size_t
   bool any_s = false;
   for (int q = 0; q < n; ++q) any_s = any_s || sendcounts[q] != 0;
   const uint64_t top = ~(uint64_t)0;
-  const uint64_t P = mx_record_bytes(rowcount);
   rc = rows_check_local(n, 1, nullptr, 0, (size_t)P, nullptr, none, none, recv, recvcounts, rdispls, (size_t)P);
   if (rc != kRowsOk || !any_s) return rc;
   const uint64_t ext = rows_extent_bytes(nrows, rowstride, rowcount, esz);
@@ -89,7 +101,7 @@ inline int mx_check_local(int n, int esz, const void* send, size_t nrows, size_t
 
 // ---------------------------------------------------------------- the kernels' view
 // The per-destination blocks of this rank (rowsmx_push's second by-value argument; rowsmx_pack takes
-// the same with dst the local addresses).  Indexed by destination rank q.
+// the same with dst the local addresses; rowsmx4_push and rowsmx4_pack alike).  Indexed by destination rank q.
 struct MxArgs {
   const char* src;        // the matrix (rowsmx_pack; rowsmx_push reads p.send)
   const int32_t* rowidx;  // device-readable; read when the kernel runs
@@ -106,9 +118,13 @@ struct MxArgs {
 // How a wave shares its lanes among rows: a lane quantises 16 consecutive elements, so a block of 32
 // is a lane pair.  Rows of 1024 elements and more take the wave whole, one pass per 1024 elements;
 // narrower rows share a pass, rowcount / 16 lanes per row and 1024 / rowcount rows at once.
+//
+// `rows` must be a power of two (so it divides 64): the walk (kernels.hip mx_walk) holds the indices of
+// 64 records, advances by `rows` records a pass and picks a record's index out of that batch alone, so
+// a pass must never straddle two batches.  Lanes at and beyond lanes * rows are idle.
 struct MxLanes {
-  uint32_t lanes;   // lanes per row (a multiple of 8, at most 64)
-  uint32_t rows;    // rows per pass
+  uint32_t lanes;   // lanes per row (MXFP8: a multiple of 8, MXFP4: of 4; at most 64)
+  uint32_t rows;    // rows per pass: a power of two, rows * lanes <= 64
   uint32_t passes;  // passes per row
 };
 MNCCL_HD MxLanes mx_lanes(uint32_t rowcount) {
@@ -116,6 +132,20 @@ MNCCL_HD MxLanes mx_lanes(uint32_t rowcount) {
   g.lanes = rowcount >= kMxPassElems ? 64u : rowcount / 16u;
   g.rows = 64u / g.lanes;
   g.passes = (rowcount + kMxPassElems - 1) / kMxPassElems;
+  return g;
+}
+
+// The same for MXFP4: a lane quantises a whole block of 32 consecutive elements into one 16-byte
+// vector of nibbles.  Rows of 2048 elements and more take the wave whole, one pass per 2048 elements;
+// narrower rows share a pass, rowcount / 32 lanes per row and the largest power of two of rows that
+// fits 64 lanes at once (1152 elements: 36 lanes, one row, 28 lanes idle; 384 elements: 12 lanes,
+// 4 rows and not 5, 16 lanes idle; 640 elements: 20 lanes, 2 rows and not 3, 24 lanes idle).  Unlike
+// MXFP8's lane counts (8, 16, 32, 64), these do not all divide 64: see MxLanes for why rows must.
+MNCCL_HD MxLanes mx4_lanes(uint32_t rowcount) {
+  MxLanes g;
+  g.lanes = rowcount >= kMx4PassElems ? 64u : rowcount / kMxBlock;
+  g.rows = 1u << (31 - __builtin_clz(64u / g.lanes));  // (lanes >= 4 for every legal rowcount; 64 / lanes >= 1)
+  g.passes = (rowcount + kMx4PassElems - 1) / kMx4PassElems;
   return g;
 }
 
@@ -170,6 +200,37 @@ inline void mx_quantise_row(const uint16_t* row, bool f16, uint32_t rowcount, ui
     rec[rowcount + b] = (uint8_t)s;
     for (uint32_t i = 0; i < kMxBlock; ++i)
       rec[b * kMxBlock + i] = s == 255u ? 0x7f : mx_encode_e4m3(ldexpf(x[i], 127 - (int)s));
+  }
+}
+
+// a finite float onto e2m1's grid {0, 0.5, 1, 1.5, 2, 3, 4, 6}: nearest, ties to the even code, saturated to +-6
+inline uint8_t mx4_encode_e2m1(float v) {
+  uint32_t u;
+  memcpy(&u, &v, 4);
+  const float a = fabsf(v);
+  return (uint8_t)(((u >> 28) & 8u) | (uint32_t)((a > 0.25f) + (a >= 0.75f) + (a > 1.25f) + (a >= 1.75f) + (a > 2.5f) +
+                                                 (a >= 3.5f) + (a > 5.0f)));
+}
+
+// one row of `rowcount` bf16 / fp16 elements into its MXFP4 record
+inline void mx4_quantise_row(const uint16_t* row, bool f16, uint32_t rowcount, uint8_t* rec) {
+  for (uint32_t b = 0; b < rowcount / kMxBlock; ++b) {
+    float x[kMxBlock];
+    uint32_t amax = 0;
+    for (uint32_t i = 0; i < kMxBlock; ++i) {
+      x[i] = mx_widen(row[b * kMxBlock + i], f16);
+      uint32_t u;
+      memcpy(&u, &x[i], 4);
+      u &= 0x7fffffffu;
+      amax = u > amax ? u : amax;
+    }
+    const uint32_t s = mx4_scale_byte(amax >> 23);
+    rec[rowcount / 2 + b] = (uint8_t)s;
+    for (uint32_t i = 0; i < kMxBlock; i += 2) {
+      // (an underflow of the scaling ends below 0.25 either way: code 0)
+      const uint8_t lo = mx4_encode_e2m1(ldexpf(x[i], 127 - (int)s)), hi = mx4_encode_e2m1(ldexpf(x[i + 1], 127 - (int)s));
+      rec[(b * kMxBlock + i) / 2] = s == 255u ? 0x77 : (uint8_t)(lo | hi << 4);
+    }
   }
 }
 

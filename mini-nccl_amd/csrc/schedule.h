@@ -173,7 +173,9 @@ enum Coll : int {
   kCollAllToAllVCombine = 12,
   // mncclAllToAllvRowsMxfp8: kCollAllToAllVRows whose rows are quantised to MXFP8 records on the way
   // out (mxblock.h); its fallback is kCollAllToAllV's padded ring behind a gather-and-quantise kernel
-  kCollAllToAllVRowsMx = 13
+  kCollAllToAllVRowsMx = 13,
+  // mncclAllToAllvRowsMxfp4: the same with MXFP4 records (mxblock.h's mx4_ rules)
+  kCollAllToAllVRowsMx4 = 14
 };
 
 // r, root: gather and scatter only (their op count depends on the rank's place in the chain; the

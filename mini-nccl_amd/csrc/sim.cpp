@@ -1600,7 +1600,7 @@ int mnccl_sim_mx_check_local(int n, int esz, const void* send, size_t nrows, siz
                              const size_t* rdispls, size_t rowcount) {
   if (n < 1 || n > mnccl::kVarMaxRanks || esz < 1) return -2;
   return mnccl::mx_check_local(n, esz, send, nrows, rowstride, rowidx, sendcounts, sdispls, recv, recvcounts, rdispls,
-                               rowcount);
+                               rowcount, mnccl::mx_record_bytes(rowcount));
 }
 uint64_t mnccl_sim_mx_record_bytes(uint64_t rowcount) { return mnccl::mx_record_bytes(rowcount); }
 void mnccl_sim_mx_slice_records(uint64_t a, uint64_t b, uint64_t P, uint64_t* out) {
@@ -1612,9 +1612,8 @@ int mnccl_sim_mx_quantise(const uint16_t* rows, int f16, uint32_t rowcount, uint
     mnccl::mx_quantise_row(rows + t * rowcount, f16 != 0, rowcount, out + t * mnccl::mx_record_bytes(rowcount));
   return 0;
 }
-int mnccl_sim_mx_owners(uint64_t count, uint64_t max_count, uint64_t rowcount, uint64_t slice_bytes, uint32_t* owners) {
+static int mx_owners(uint64_t count, uint64_t max_count, uint64_t P, uint64_t slice_bytes, uint32_t* owners) {
   if (slice_bytes == 0 || count > max_count) return -2;
-  const uint64_t P = mnccl::mx_record_bytes(rowcount);
   for (uint64_t a = 0; a < max_count * P; a += slice_bytes) {
     const uint64_t len = mnccl::varblock_len_at(count * P, slice_bytes, a);
     if (len == 0) continue;
@@ -1624,6 +1623,34 @@ int mnccl_sim_mx_owners(uint64_t count, uint64_t max_count, uint64_t rowcount, u
     for (uint64_t j = j0; j < j1; ++j) ++owners[j];
   }
   return 0;
+}
+int mnccl_sim_mx_owners(uint64_t count, uint64_t max_count, uint64_t rowcount, uint64_t slice_bytes, uint32_t* owners) {
+  return mx_owners(count, max_count, mnccl::mx_record_bytes(rowcount), slice_bytes, owners);
+}
+
+// The same for mncclAllToAllvRowsMxfp4 (the mx4_ rules of csrc/mxblock.h): records of rowcount / 2 +
+// rowcount / 32 bytes; lanes: {lanes per row, rows per pass, passes per row} of kernels.hip's walk.
+int mnccl_sim_mx4_check_local(int n, int esz, const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                              const size_t* sendcounts, const size_t* sdispls, const void* recv, const size_t* recvcounts,
+                              const size_t* rdispls, size_t rowcount) {
+  if (n < 1 || n > mnccl::kVarMaxRanks || esz < 1) return -2;
+  return mnccl::mx_check_local(n, esz, send, nrows, rowstride, rowidx, sendcounts, sdispls, recv, recvcounts, rdispls,
+                               rowcount, mnccl::mx4_record_bytes(rowcount));
+}
+uint64_t mnccl_sim_mx4_record_bytes(uint64_t rowcount) { return mnccl::mx4_record_bytes(rowcount); }
+uint32_t mnccl_sim_mx4_scale_byte(uint32_t E) { return mnccl::mx4_scale_byte(E); }
+void mnccl_sim_mx4_lanes(uint32_t rowcount, uint32_t* out) {
+  const mnccl::MxLanes g = mnccl::mx4_lanes(rowcount);
+  out[0] = g.lanes, out[1] = g.rows, out[2] = g.passes;
+}
+int mnccl_sim_mx4_quantise(const uint16_t* rows, int f16, uint32_t rowcount, uint64_t nrows, uint8_t* out) {
+  if (rowcount % mnccl::kMxBlock) return -2;
+  for (uint64_t t = 0; t < nrows; ++t)
+    mnccl::mx4_quantise_row(rows + t * rowcount, f16 != 0, rowcount, out + t * mnccl::mx4_record_bytes(rowcount));
+  return 0;
+}
+int mnccl_sim_mx4_owners(uint64_t count, uint64_t max_count, uint64_t rowcount, uint64_t slice_bytes, uint32_t* owners) {
+  return mx_owners(count, max_count, mnccl::mx4_record_bytes(rowcount), slice_bytes, owners);
 }
 
 // csrc/combine.h, the host-side rules of mncclAllToAllvCombine, for the CPU suite: one rank's local

@@ -39,7 +39,9 @@ enum : uint32_t {
   kVarCombine = 8u,
   // the row of an mncclAllToAllvRowsMxfp8 call (mxblock.h), set beside kVarRows: the counts are MXFP8
   // records of `pad` elements
-  kVarRowsMx = 16u
+  kVarRowsMx = 16u,
+  // the row of an mncclAllToAllvRowsMxfp4 call, set beside kVarRows: MXFP4 records of `pad` elements
+  kVarRowsMx4 = 32u
 };
 
 // The local checks' verdicts, in the order they are made

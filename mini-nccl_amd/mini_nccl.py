@@ -101,6 +101,8 @@ SIGNATURES = {
                                 ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllToAllvRowsMxfp8": (_I, [_VP, _SZ, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, ctypes.POINTER(_SZ),
                                      ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
+    "mncclAllToAllvRowsMxfp4": (_I, [_VP, _SZ, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, ctypes.POINTER(_SZ),
+                                     ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllToAllvCombine": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _SZ, _VP, _VP, _I,
                                    ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllGatherv": (_I, [_VP, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _I, _VP, _VP]),
@@ -317,6 +319,15 @@ class Comm:
         count records; rowcount is a multiple of 128 in [128, 16384].  Returns the ncclResult_t."""
         arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
         return load().mncclAllToAllvRowsMxfp8(send_ptr, nrows, rowstride, rowidx_ptr, arrays[0], arrays[1], recv_ptr,
+                                              arrays[2], arrays[3], rowcount, dtype, self.handle, stream)
+
+    def all_to_all_v_rows_mxfp4(self, send_ptr, nrows, rowstride, rowidx_ptr, sendcounts, sdispls, recv_ptr, recvcounts,
+                                rdispls, rowcount, dtype=ncclBfloat16, stream=0):
+        """mncclAllToAllvRowsMxfp4: all_to_all_v_rows_mxfp8 with MXFP4 records of rowcount // 2 + rowcount // 32
+        bytes: rowcount // 2 bytes of e2m1 nibbles (element 2i low, 2i + 1 high), then one E8M0 scale byte
+        per 32 elements.  Returns the ncclResult_t."""
+        arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
+        return load().mncclAllToAllvRowsMxfp4(send_ptr, nrows, rowstride, rowidx_ptr, arrays[0], arrays[1], recv_ptr,
                                               arrays[2], arrays[3], rowcount, dtype, self.handle, stream)
 
     def all_to_all_v_combine(self, send_ptr, sendcounts, sdispls, recv_ptr, nrows, rowstride, slotidx_ptr, weights_ptr, topk,

@@ -68,6 +68,9 @@ persistent form (mncclAlgoRead), fp32 Sum, stream-ordered (MINI_NCCL_BLOCKING=0)
                     indices (--row-elems a multiple of 128), beside the quantise kernel into a packed buffer
                     followed by ncclAllToAllv of the records' bytes.  Ratios alltoallv_rows_mxfp8_over_composed
                     and, when alltoallv_rows is timed too, alltoallv_rows_mxfp8_over_alltoallv_rows
+    alltoallv_rows_mxfp4 / alltoallv_rows_mxfp4_composed   the same pair for mncclAllToAllvRowsMxfp4.  Ratios
+                    alltoallv_rows_mxfp4_over_composed and, when those kinds are timed too,
+                    alltoallv_rows_mxfp4_over_alltoallv_rows_mxfp8 and alltoallv_rows_mxfp4_over_alltoallv_rows
     alltoallv_rows_composed   what a caller runs without it, on the same matrix and indices: the gather
                     as a kernel of its own (rows_pack, through a one-rank communicator) into a packed
                     buffer, then ncclAllToAllv.  Ratio alltoallv_rows_over_composed beside both spreads
@@ -111,11 +114,14 @@ KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_pr
          "p2p_neighbor_win", "p2p_all_pairs_win", "gather", "gather_p2p", "scatter", "scatter_p2p",
          "all_gather_v", "reduce_scatter_v", "all_gather_v_skew", "reduce_scatter_v_skew", "all_gather_padded",
          "reduce_scatter_padded", "alltoallv_rows", "alltoallv_rows_composed", "alltoallv_combine",
-         "alltoallv_combine_composed", "alltoallv_rows_mxfp8", "alltoallv_rows_mxfp8_composed")
+         "alltoallv_combine_composed", "alltoallv_rows_mxfp8", "alltoallv_rows_mxfp8_composed", "alltoallv_rows_mxfp4",
+         "alltoallv_rows_mxfp4_composed")
 # mncclAllToAllvRows beside what a caller composes without it, on the same matrix and indices
 ROWS_KINDS = ("alltoallv_rows", "alltoallv_rows_composed")
 # mncclAllToAllvRowsMxfp8 beside the quantise kernel followed by ncclAllToAllv of bytes, same matrix and indices
 MX_KINDS = ("alltoallv_rows_mxfp8", "alltoallv_rows_mxfp8_composed")
+# mncclAllToAllvRowsMxfp4 beside its composed form, built the same way
+MX4_KINDS = ("alltoallv_rows_mxfp4", "alltoallv_rows_mxfp4_composed")
 # mncclAllToAllvCombine beside ncclAllToAllv plus a fold of the caller's own, on the same data
 COMBINE_KINDS = ("alltoallv_combine", "alltoallv_combine_composed")
 # the kinds that need the padded buffers (n blocks of the skewed shape's largest block)
@@ -124,7 +130,7 @@ VHALF_SKEW = ("all_gather_v_skew", "reduce_scatter_v_skew") + PADDED_KINDS
 # the kinds --dtype bf16 can time (the others' helpers are written for fp32 elements)
 # the kinds that run while big_b is a registered window, and the scratch form each is measured against
 WIN_KINDS = {"p2p_neighbor_win": "p2p_neighbor", "p2p_all_pairs_win": "p2p_all_pairs"}
-BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce") + ROWS_KINDS + COMBINE_KINDS + MX_KINDS
+BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce") + ROWS_KINDS + COMBINE_KINDS + MX_KINDS + MX4_KINDS
 
 
 def skew_matrix(n, chunk, seed):
@@ -146,13 +152,14 @@ def v_call(M, comm, send, recv, C, rank, stream):
 
 
 def rows_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stream):
-    """(fused, composed, buffers, solo, mx, mx_composed): bf16 rows of `row_elems` elements, block_bytes // row bytes rows
+    """(fused, composed, buffers, solo, mx, mx_composed, mx4, mx4_composed): bf16 rows of `row_elems` elements, block_bytes // row bytes rows
     per block (balanced) or skew_matrix's share of that (skew_seed >= 0); a top-2 router's list over
     half as many tokens as rows are sent, seeded per rank.  Fused: mncclAllToAllvRows.  Composed: the
     same gather as a kernel of its own into a packed buffer (mncclAllToAllvRows on a one-rank
     communicator runs rows_pack alone), then ncclAllToAllv on the packed rows.  mx / mx_composed: the
     same pair for mncclAllToAllvRowsMxfp8 -- rowsmx_pack into the packed buffer, then ncclAllToAllv of the
-    records' bytes -- in the same buffers (a record is shorter than its row)."""
+    records' bytes -- in the same buffers (a record is shorter than its row).  mx4 / mx4_composed: that
+    pair again for mncclAllToAllvRowsMxfp4 (rowsmx4_pack, records of row_elems // 2 + row_elems // 32 bytes)."""
     import numpy as np
     rb = 2 * row_elems
     per = max(1, block_bytes // rb)
@@ -174,16 +181,19 @@ def rows_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stre
         r = solo.all_to_all_v_rows(x.ptr, tokens, row_elems, idx.ptr, [total], [0], packed.ptr, [total], [0], row_elems,
                                    M.ncclBfloat16, stream)
         return r or comm.all_to_all_v(packed.ptr, e(sc), e(starts(sc)), recv.ptr, e(rc), e(starts(rc)), M.ncclBfloat16, stream)
-    P = row_elems + row_elems // 32
-    ep = lambda xs: [v * P for v in xs]
-    mx = lambda: comm.all_to_all_v_rows_mxfp8(x.ptr, tokens, row_elems, idx.ptr, sc, starts(sc), recv.ptr, rc, starts(rc),
-                                              row_elems, M.ncclBfloat16, stream)
 
-    def mx_composed():
-        r = solo.all_to_all_v_rows_mxfp8(x.ptr, tokens, row_elems, idx.ptr, [total], [0], packed.ptr, [total], [0], row_elems,
-                                         M.ncclBfloat16, stream)
-        return r or comm.all_to_all_v(packed.ptr, ep(sc), ep(starts(sc)), recv.ptr, ep(rc), ep(starts(rc)), M.ncclFloat8e4m3, stream)
-    return fused, composed, [x, idx, packed, recv], solo, mx, mx_composed
+    def mx_pair(entry, P):  # the fused call, and its pack through the one-rank communicator followed by the bytes' exchange
+        ep = lambda xs: [v * P for v in xs]
+        mx = lambda: getattr(comm, entry)(x.ptr, tokens, row_elems, idx.ptr, sc, starts(sc), recv.ptr, rc, starts(rc),
+                                          row_elems, M.ncclBfloat16, stream)
+
+        def mx_composed():
+            r = getattr(solo, entry)(x.ptr, tokens, row_elems, idx.ptr, [total], [0], packed.ptr, [total], [0], row_elems,
+                                     M.ncclBfloat16, stream)
+            return r or comm.all_to_all_v(packed.ptr, ep(sc), ep(starts(sc)), recv.ptr, ep(rc), ep(starts(rc)), M.ncclFloat8e4m3, stream)
+        return mx, mx_composed
+    return (fused, composed, [x, idx, packed, recv], solo) + mx_pair("all_to_all_v_rows_mxfp8", row_elems + row_elems // 32) + \
+        mx_pair("all_to_all_v_rows_mxfp4", row_elems // 2 + row_elems // 32)
 
 
 def combine_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stream):
@@ -325,8 +335,9 @@ def rank_main(a):
         calls["reduce_scatter_padded"] = lambda: comm.reduce_scatter(pads[0].ptr, pads[1].ptr, max(skew), M.ncclFloat,
                                                                      M.ncclSum, st.handle)
     solo = None
-    if any(k in ROWS_KINDS + MX_KINDS for k in kinds):
-        calls["alltoallv_rows"], calls["alltoallv_rows_composed"], more, solo, calls[MX_KINDS[0]], calls[MX_KINDS[1]] = rows_calls(
+    if any(k in ROWS_KINDS + MX_KINDS + MX4_KINDS for k in kinds):
+        (calls["alltoallv_rows"], calls["alltoallv_rows_composed"], more, solo, calls[MX_KINDS[0]], calls[MX_KINDS[1]],
+         calls[MX4_KINDS[0]], calls[MX4_KINDS[1]]) = rows_calls(
             M, hip_rt, comm, n, a.rank, a.bytes // n, a.row_elems, a.skew_seed if a.rows_skew else -1, st.handle)
         pads += more
     solo2 = None
@@ -463,7 +474,7 @@ def main():
         "rounds_ms": {k: [round(x, 4) for x in v] for k, v in rounds.items()},
         "hbm_bytes": {k: (2 * n if k in ("all_reduce", "all_reduce_premul", "all_to_all", "all_to_all_v") else n + 1) * chunk_bytes
                       for k in kinds if k not in ("all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
-                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") + VHALF_SKEW + ROWS_KINDS + COMBINE_KINDS + MX_KINDS
+                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") + VHALF_SKEW + ROWS_KINDS + COMBINE_KINDS + MX_KINDS + MX4_KINDS
                       and k not in WIN_KINDS},
         "ratio": dict([(f"{k}_over_all_reduce", round(med[k] / med["all_reduce"], 4)) for k in kinds if k != "all_reduce"] +
                       [(f"{k}_over_{y}", round(med[k] / med[y], 4))
@@ -529,6 +540,15 @@ def main():
         if "alltoallv_rows" in med:
             res["ratio"]["alltoallv_rows_mxfp8_over_alltoallv_rows"] = round(med[MX_KINDS[0]] / med["alltoallv_rows"], 4)
         for k in MX_KINDS:
+            res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
+    if all(k in med for k in MX4_KINDS):
+        res["rows_mxfp4"] = {"row_elems": a.row_elems, "record_bytes": a.row_elems // 2 + a.row_elems // 32,
+                             "matrix": "skew" if a.rows_skew else "balanced"}
+        res["ratio"]["alltoallv_rows_mxfp4_over_composed"] = round(med[MX4_KINDS[0]] / med[MX4_KINDS[1]], 4)
+        for other in ("alltoallv_rows_mxfp8", "alltoallv_rows"):
+            if other in med:
+                res["ratio"]["alltoallv_rows_mxfp4_over_" + other] = round(med[MX4_KINDS[0]] / med[other], 4)
+        for k in MX4_KINDS:
             res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
     if all(k in med for k in COMBINE_KINDS):
         res["combine"] = {"row_elems": a.row_elems, "row_bytes": 2 * a.row_elems, "topk": 2, "matrix": "skew" if a.rows_skew else "balanced"}
