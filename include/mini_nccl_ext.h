@@ -44,6 +44,7 @@
  *   mncclAllToAllvRowsMxfp4  the same with e2m1 elements, two to a byte: MXFP4 records.
  *   mncclAllToAllvCombine  the way back: the token owner pulls the top-k rows of each token out of the
  *                        experts' send buffers and folds them by gate weight (no packed recv, no atomics).
+ *   mncclAllToAllvCombineMxfp8  the same out of MXFP8 records, decoded in the fold: half of bf16's bytes back.
  *
  * and the all-reduce's halves with per-rank counts, which neither NCCL nor RCCL has (callers there
  * compose them from broadcasts / reduces inside one group, which this library does not take), under
@@ -599,6 +600,41 @@ ncclResult_t mncclAllToAllvCombine(const void* sendbuff, const size_t sendcounts
                                    size_t nrows, size_t rowstride, const int32_t* slotidx, const float* weights, int topk,
                                    const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
                                    ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
+
+/* The way back out of MXFP8 records: mncclAllToAllvCombine whose send side holds what
+ * mncclAllToAllvRowsMxfp8 delivers, so an expert whose epilogue writes records returns 1.03 bytes per
+ * element over the links instead of 2 (bf16) or 4 (f32).  Detected by symbol (MNCCL_VERSION stays 600).
+ *
+ * mncclAllToAllvCombine's arguments and meaning with two differences.  The send side: row i of sendbuff
+ * is one record of P = rowcount + rowcount / 32 bytes -- rowcount e4m3 elements, then one E8M0 scale
+ * byte per 32 consecutive elements -- dense, no stride; sendcounts, sdispls, recvcounts, rdispls and
+ * slotidx count records.  The output side: `datatype` is the recvbuff matrix's (ncclFloat, ncclFloat16
+ * or ncclBfloat16) and `rowstride` is in its elements.
+ *
+ * Result, bit for bit on every schedule and slice size: mncclAllToAllvCombine's rule with
+ * float(P[j][e]) replaced by the decoded element.  With c = byte e of record j and s = its byte
+ * rowcount + e / 32: NaN when s == 0xFF or c is 0x7F or 0xFF; else ldexpf(e4m3(c), s - 127) in IEEE
+ * single -- exact wherever it is representable (every s mncclAllToAllvRowsMxfp8 writes, at most 246,
+ * and all subnormal results: f32 denormals are on), +-inf for the s of 247 .. 254 that overflow.  Then
+ * acc from +0.0f, one unfused single multiply by the weight and one add per slot in slot order, one
+ * rounding to the datatype to nearest even.  A slot in no non-empty block contributes nothing and
+ * causes no access.  Where the rule gives NaN the output is a NaN of the datatype, no payload promised.
+ *
+ * Checks: mncclAllToAllvCombine's, in its order and with its verdicts (the send side's overflow and
+ * overlap checks count P bytes per row; any datatype but the three: ncclInternalError).  In front of
+ * its local ones, each ncclInvalidArgument: rowcount % 128 != 0 or outside [128, 16384]; sendbuff,
+ * recvbuff or rowstride in bytes not dword-aligned.  Ranks that mix this call with
+ * mncclAllToAllvCombine, or differ in datatype, rowcount or the schedule choice: ncclInvalidUsage on
+ * every rank, nothing launched.
+ *
+ * Schedules as mncclAllToAllvCombine: the persistent pull-and-fold kernel wherever ncclAllToAllv would
+ * run the read schedule (last_algo: mncclAlgoRead), else the padded ring carries the records as bytes
+ * into the stage and the local kernel decodes and folds out of it (last_algo: mncclAlgoRing; refused
+ * under capture). */
+ncclResult_t mncclAllToAllvCombineMxfp8(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[],
+                                        void* recvbuff, size_t nrows, size_t rowstride, const int32_t* slotidx,
+                                        const float* weights, int topk, const size_t recvcounts[], const size_t rdispls[],
+                                        size_t rowcount, ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
 
 /* The all-reduce's halves with per-rank counts.  Neither NCCL nor RCCL has them, so they carry the
  * library's prefix and MPI's argument order (MPI_Allgatherv / MPI_Reduce_scatter with displacements).

@@ -447,6 +447,30 @@ ncclResult_t mncclAllToAllvCombine(const void* sendbuff, const size_t sendcounts
   }
 }
 
+// The way back out of MXFP8 records (mini_nccl_ext.h): mncclAllToAllvCombine's checks in its order;
+// the datatype is the OUTPUT matrix's (Comm::combine with mx, combinemx.h).
+ncclResult_t mncclAllToAllvCombineMxfp8(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[],
+                                        void* recvbuff, size_t nrows, size_t rowstride, const int32_t* slotidx,
+                                        const float* weights, int topk, const size_t recvcounts[], const size_t rdispls[],
+                                        size_t rowcount, ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
+  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
+  RoctxRange range("mini_ncclAllToAllvCombineMxfp8");
+  if (datatype != ncclFloat && datatype != ncclFloat16 && datatype != ncclBfloat16) {
+    fprintf(stderr, "[Mini-NCCL] AllToAllvCombineMxfp8 Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->combine(sendbuff, sendcounts, sdispls, recvbuff, nrows, rowstride, slotidx, weights,
+                                                  topk, recvcounts, rdispls, rowcount, (int)datatype, stream, true);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] AllToAllvCombineMxfp8 Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
 // The halves with per-rank counts (mini_nccl_ext.h): the communicator and the two arrays, the open
 // group, then the datatype and the op; the data buffers may be NULL where the counts are zero, so
 // they are checked with the counts where the communicator's rank and size are known (Comm::vhalf,

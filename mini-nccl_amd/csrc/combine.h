@@ -36,11 +36,12 @@ enum CombineLocal : int {
 };
 
 // One rank's arguments.  esz: the element size in bytes; the arrays hold n entries.  The buffers are
-// only compared, never dereferenced.
+// only compared, never dereferenced.  send_row_bytes: the bytes of one row of `send` where they are not
+// rowcount * esz (combinemx.h: a record), else 0.
 inline int combine_check_local(int n, int esz, const void* send, const size_t* sendcounts, const size_t* sdispls,
                                const void* recv, size_t nrows, size_t rowstride, const int32_t* slotidx,
                                const float* weights, int topk, const size_t* recvcounts, const size_t* rdispls,
-                               size_t rowcount) {
+                               size_t rowcount, uint64_t send_row_bytes = 0) {
   bool any_s = false, any_r = false;
   for (int q = 0; q < n; ++q) {
     any_s = any_s || sendcounts[q] != 0;
@@ -53,16 +54,16 @@ inline int combine_check_local(int n, int esz, const void* send, const size_t* s
   if ((any_s && !send) || (nrows != 0 && (!recv || !slotidx))) return kCombineNullBuffer;
   const uint64_t e = (uint64_t)esz, top = ~(uint64_t)0;
   if (rowcount > (uint64_t)INT32_MAX / e) return kCombineOverflow;
-  const uint64_t rb = rowcount * e;
+  const uint64_t rb = rowcount * e, srb = send_row_bytes ? send_row_bytes : rb;
   // the send blocks as address ranges; the virtual blocks as ranges of positions
   uint64_t sb[kVarMaxRanks] = {}, sl[kVarMaxRanks] = {};
   const uint64_t sbase = (uint64_t)(uintptr_t)send;
   for (int q = 0; q < n; ++q) {
     const uint64_t c = sendcounts[q], d = sdispls[q];
     if (c == 0) continue;  // an empty block's displacement is never used
-    if (d > top - c || d + c > top / rb || sbase > top - (d + c) * rb) return kCombineOverflow;
-    sb[q] = sbase + d * rb;
-    sl[q] = c * rb;
+    if (d > top - c || d + c > top / srb || sbase > top - (d + c) * srb) return kCombineOverflow;
+    sb[q] = sbase + d * srb;
+    sl[q] = c * srb;
   }
   for (int q = 0; q < n; ++q)
     if (recvcounts[q] && rdispls[q] > top - recvcounts[q]) return kCombineOverflow;

@@ -1503,20 +1503,26 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
 // its rows through one more dense stage region and a strided copy.  Every count zero on every rank:
 // combine_local alone zero-fills (no protocol: every rank sees the same matrix); one rank: the same
 // kernel on the own block.  A rank with no output rows still serves its send; one with no send counts
-// still pulls.
+// still pulls.  mx (mncclAllToAllvCombineMxfp8): the same path with combinemx.h's rules -- a send row is a
+// record of mx_record_bytes(rowcount) bytes (sb below; rb stays the OUTPUT row's), the collective id is
+// kCollAllToAllVCombineMx, the kernels combinemx_fold / combinemx_local; the ring moves the records as bytes.
 ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv, size_t nrows,
                            size_t rowstride, const int32_t* slotidx, const float* weights, int topk,
                            const size_t* recvcounts, const size_t* rdispls, size_t rowcount, int dtype,
-                           hipStream_t stream) {
+                           hipStream_t stream, bool mx) {
   if (sticky_ != ncclSuccess) return sticky_;
   if (check_status() != ncclSuccess) return sticky_;
-  const int n = nranks_, esz = dtype_size(dtype), coll = kCollAllToAllVCombine;
-  const char* const name = "mncclAllToAllvCombine";
-  const int local = combine_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights, topk,
-                                        recvcounts, rdispls, rowcount);
+  const int n = nranks_, esz = dtype_size(dtype), coll = mx ? kCollAllToAllVCombineMx : kCollAllToAllVCombine;
+  const char* const name = mx ? "mncclAllToAllvCombineMxfp8" : "mncclAllToAllvCombine";
+  const int local = mx ? combinemx_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights,
+                                               topk, recvcounts, rdispls, rowcount)
+                       : combine_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights, topk,
+                                             recvcounts, rdispls, rowcount);
   if (local != kCombineOk) {
     fprintf(stderr, "[Mini-NCCL] rank %d: %s: %s\n", rank_, name,
-            local == kCombineTopk           ? "topk is outside [1, 16]"
+            local == kMxRowcount            ? "rowcount is no multiple of 128 in [128, 16384]"
+            : local == kMxAlign             ? "sendbuff, recvbuff or rowstride in bytes is not dword-aligned"
+            : local == kCombineTopk         ? "topk is outside [1, 16]"
             : local == kCombineZeroRow      ? "rowcount is 0 with a non-zero count or nrows"
             : local == kCombineStride       ? "rowstride is smaller than rowcount"
             : local == kCombineTooManySlots ? "nrows * topk is beyond what an int32 can count"
@@ -1527,7 +1533,8 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
                                             : "the recv matrix overlaps a send block, slotidx or weights");
     return ncclInvalidArgument;
   }
-  const size_t rb = rowcount * (size_t)esz;
+  // rb: an output row's bytes; sb: a send row's (mx: a record's)
+  const size_t rb = rowcount * (size_t)esz, sb = mx ? (size_t)mx_record_bytes(rowcount) : rb;
   auto how = [&](const void* p) {
     const void* k = p;
     bool l = false;
@@ -1566,9 +1573,11 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
       at[q] = disp[q];
     }
     CombineArgs v;
-    combine_fill_args(&v, n, esz, out_via ? stage_ + out_at : out, nrows, out_via ? rowcount : rowstride, kslot, kw, topk,
-                      recvcounts, rdispls, rowcount, send_of, at);
-    hip_check(launch_combine_local(dtype, n, v, packed, out_via ? stage_ + out_at : const_cast<void*>(out), stream),
+    (mx ? combinemx_fill_args : combine_fill_args)(&v, n, esz, out_via ? stage_ + out_at : out, nrows,
+                                                   out_via ? rowcount : rowstride, kslot, kw, topk, recvcounts, rdispls, rowcount,
+                                                   send_of, at);
+    hip_check((mx ? launch_combinemx_local : launch_combine_local)(dtype, n, v, packed,
+                                                                   out_via ? stage_ + out_at : const_cast<void*>(out), stream),
               "kernel launch");
     if (out_via)
       hip_check(hipMemcpy2DAsync(recv, rowstride * (size_t)esz, stage_ + out_at, rb, rb, nrows, hipMemcpyDefault, stream),
@@ -1582,12 +1591,12 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
     }
     if (nrows == 0) return ncclSuccess;
     const CallScope scope = begin_call(stream);
-    const size_t own = sendcounts[0] * rb, own_pad = (own + 15) & ~(size_t)15;
+    const size_t own = sendcounts[0] * sb, own_pad = (own + 15) & ~(size_t)15;
     const void* src = send;
     bool l = false;
     const bool in_via = own && reach(send, &src, &l) == Reach::kStaged;
     if (in_via || out_via) ensure_stage((in_via ? own_pad : 0) + out_bytes, stream);
-    if (in_via) hip_check(hipMemcpyAsync(stage_, (const char*)send + sdispls[0] * rb, own, hipMemcpyDefault, stream), "stage in");
+    if (in_via) hip_check(hipMemcpyAsync(stage_, (const char*)send + sdispls[0] * sb, own, hipMemcpyDefault, stream), "stage in");
     fold_local(in_via ? stage_ : static_cast<const char*>(src), in_via ? none : sdispls, in_via ? own_pad : 0);
     return end_call(scope, stream, 0);
   }
@@ -1663,7 +1672,7 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
   }
   const size_t M = (size_t)combine_max_rows(n, rows) * rb;  // the longest output: the same everywhere
   if (M == 0) return leave(ncclSuccess);                     // nobody has a row to write
-  const size_t Mb = (size_t)varblock_max_count(n, rows) * rb;  // the largest block
+  const size_t Mb = (size_t)varblock_max_count(n, rows) * sb;  // the largest block
   if (Mb == 0) {
     // nobody sends anything: the rows are zero-filled by the local kernel alone, no protocol
     if (nrows == 0) return leave(ncclSuccess);
@@ -1687,17 +1696,18 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
     }
     CombineArgs v;
     // (a rank without rows passes a stand-in list: never read)
-    combine_fill_args(&v, n, esz, rrecv, nrows, rowstride, nrows ? kslot : (const int32_t*)rsend, nrows ? kw : nullptr, topk,
-                      recvcounts, rdispls, rowcount, send_of, peer_sdispl);
+    (mx ? combinemx_fill_args : combine_fill_args)(&v, n, esz, rrecv, nrows, rowstride,
+                                                   nrows ? kslot : (const int32_t*)rsend, nrows ? kw : nullptr, topk, recvcounts,
+                                                   rdispls, rowcount, send_of, peer_sdispl);
     int A = 0;
     const CollParams p = make_params(2, rsend, rrecv, M, seq, psend, precv, 0, 0, coll, 0, 0, &A);
-    hip_check(launch_combine(dtype, A / geo_.waves, cfg_.threads, p, v, stream), "kernel launch");
+    hip_check((mx ? launch_combinemx : launch_combine)(dtype, A / geo_.waves, cfg_.threads, p, v, stream), "kernel launch");
     last_algo_ = 2;
   } else {
     const size_t Mpad = (Mb + 15) & ~(size_t)15;
     size_t P = 0;  // the virtual sequence's end, in bytes
     for (int q = 0; q < n; ++q)
-      if (recvcounts[q]) P = std::max(P, (size_t)(rdispls[q] + recvcounts[q]) * rb);
+      if (recvcounts[q]) P = std::max(P, (size_t)(rdispls[q] + recvcounts[q]) * sb);
     const size_t Ppad = (P + 15) & ~(size_t)15;
     ensure_stage(2 * (size_t)n * Mpad + Ppad + out_bytes, stream);
     char* in = stage_;
@@ -1706,15 +1716,15 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
     const char* s0 = static_cast<const char*>(send);
     for (int q = 0; q < n; ++q)
       if (q != rank_ && sendcounts[q])
-        hip_check(hipMemcpyAsync(in + (size_t)q * Mpad, s0 + sdispls[q] * rb, sendcounts[q] * rb, hipMemcpyDefault, stream),
+        hip_check(hipMemcpyAsync(in + (size_t)q * Mpad, s0 + sdispls[q] * sb, sendcounts[q] * sb, hipMemcpyDefault, stream),
                   "pack");
     launch(0, in, out, Mpad, dtype, kSum, stream, seq, true, nullptr, nullptr, 0, 0, kCollAllToAll);
     for (int q = 0; q < n; ++q)
       if (q != rank_ && recvcounts[q])
-        hip_check(hipMemcpyAsync(packed + rdispls[q] * rb, out + (size_t)q * Mpad, recvcounts[q] * rb, hipMemcpyDefault, stream),
+        hip_check(hipMemcpyAsync(packed + rdispls[q] * sb, out + (size_t)q * Mpad, recvcounts[q] * sb, hipMemcpyDefault, stream),
                   "unpack");
     if (sendcounts[rank_])
-      hip_check(hipMemcpyAsync(packed + rdispls[rank_] * rb, s0 + sdispls[rank_] * rb, sendcounts[rank_] * rb,
+      hip_check(hipMemcpyAsync(packed + rdispls[rank_] * sb, s0 + sdispls[rank_] * sb, sendcounts[rank_] * sb,
                                hipMemcpyDefault, stream), "own block");
     fold_local(packed, rdispls, 2 * (size_t)n * Mpad + Ppad);
   }

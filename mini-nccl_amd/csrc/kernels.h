@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "combine.h"
+#include "combinemx.h"
 #include "mxblock.h"
 #include "p2p.h"
 #include "rowblock.h"
@@ -172,6 +173,13 @@ hipError_t launch_combine(int dtype, int channels, int threads, const CollParams
 // The same fold as a plain grid launch out of one local buffer (kernels.hip combine_local): block q of
 // the virtual sequence lies at src + v.src_off[q], for every q < n.  No rows: nothing launched.
 hipError_t launch_combine_local(int dtype, int n, const CombineArgs& v, const void* src, void* recv, hipStream_t stream);
+// mncclAllToAllvCombineMxfp8 (kernels.hip combinemx_fold, combinemx_local): the two launches above with
+// MXFP8 records on the send side -- v from combinemx_fill_args (combinemx.h: row_bytes the OUTPUT row's,
+// src_off in records' bytes), p.coll kCollAllToAllVCombineMx, dtype the output's.  They refuse a rowcount
+// that is no multiple of 128 in [128, 16384] and a recv or stride that is not dword-aligned.
+hipError_t launch_combinemx(int dtype, int channels, int threads, const CollParams& p, const CombineArgs& v,
+                            hipStream_t stream);
+hipError_t launch_combinemx_local(int dtype, int n, const CombineArgs& v, const void* src, void* recv, hipStream_t stream);
 // mncclReduceScatterv / mncclAllGatherv on the read schedule (kernels.hip vhalf_fold / vhalf_push):
 // this rank's block of the array-side buffers, a second by-value kernel argument (CollParams stays
 // byte for byte what it was).  The arrays are the same on every rank, so `base` is the block's byte

@@ -45,6 +45,8 @@
 //                 weight in float in slot order and stores one row; vhalf_fold's protocol, the geometry
 //                 of the longest output; combine_local is the same fold as a grid kernel out of one
 //                 local packed buffer (one rank, and behind the padded ring).
+//  combinemx_fold / combinemx_local   the same pair out of MXFP8 records (mncclAllToAllvCombineMxfp8): 16
+//                 e4m3 bytes and their scale byte per lane and source, decoded in registers before the product.
 //  vhalf_fold / vhalf_push   the halves with per-rank counts (mncclReduceScatterv / mncclAllGatherv)
 //                 on the same protocol: scatter_fold and gather_push with a per-rank base and
 //                 length, the slices cut for the largest block.  Their fallback is the ring's
@@ -2660,6 +2662,238 @@ __global__ void __launch_bounds__(256) MNCCL_SCALAR_F32 combine_local(CombineArg
   }
 }
 
+// ---------------------------------------------------------------- the combine out of MXFP8 records
+// mncclAllToAllvCombineMxfp8 (combinemx_fold): combine_fold whose sources are the records
+// mncclAllToAllvRowsMxfp8 delivers (combinemx.h) -- rowcount e4m3 bytes, then a scale byte per 32
+// elements, P bytes in all -- decoded in registers between the pull and the product, so 1.03 bytes per
+// element cross the links where the bf16 combine moves 2.  combine_fold's protocol, geometry and slot
+// rules; v.row_bytes is the OUTPUT row's, rowcount = row_bytes / sizeof(T), and v.src_off is in bytes
+// of records.
+//
+// The unit is 16 consecutive elements: one 16-byte sc0 sc1 load of e4m3 bytes per lane and source, 16
+// float accumulators, 16 * sizeof(T) output bytes stored as two (fp16 / bf16) or four (f32) vectors.
+// rows_units with that output size says which units of a row a slice stores, so every output byte is
+// stored once.  rowcount is a multiple of 128 and everything dword-aligned (launch_combinemx): there is
+// no element path and no tail.  A unit is half a block, so a lane pair shares a scale byte: each lane
+// loads it as one byte through the SAME descriptor as its elements, at rowcount + unit / 2, and both
+// loads are range-checked against the record.
+//
+// Decode: v_cvt_pk_f32_fp8 (Fp8<e4m3_t>::dec2; 0x7F / 0xFF give NaN), then v_ldexp_f32 by scale - 127
+// -- exact where representable, subnormal results included (f32 denormals are on), +-inf beyond; a
+// block with scale 0xFF has its code words replaced by 0x7F7F7F7F before the convert, a select and no
+// branch.  Products and sums as combine_mac16.
+//
+// Wide rows (mx_lanes: 1024 elements and more), combinemx_wide: combine_wide's walk -- slots and
+// weights of 64 / topk rows per coalesced load with the next batch prefetched, readlane, the owner on
+// the scalar side -- with one descriptor per source RECORD (base its first byte, num_records P; 0 and
+// weight 0 for a slot that contributes nothing, whose element and scale loads then return 0 and add
+// +0).  G sources x V passes of 64 units, elements and scales all loaded before the first product.
+// Narrow rows, combinemx_unit: rowcount / 16 lanes per row, 64 / lanes rows a pass; the lanes of a
+// pass read records of different peers through one descriptor per distinct (peer, 2 GiB window)
+// among them, elements and scale alike, as combine_unit.
+__device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_mac16(float (&acc)[16], v4u x, uint32_t s, float w) {
+#pragma clang fp contract(off)
+  const int sh = (int)s - 127;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const uint32_t c = s == 255u ? 0x7f7f7f7fu : x[d];
+    const v2f lo = Fp8<e4m3_t>::dec2<false>(c), hi = Fp8<e4m3_t>::dec2<true>(c);
+    acc[4 * d] = acc[4 * d] + w * __builtin_ldexpf(lo.x, sh);
+    acc[4 * d + 1] = acc[4 * d + 1] + w * __builtin_ldexpf(lo.y, sh);
+    acc[4 * d + 2] = acc[4 * d + 2] + w * __builtin_ldexpf(hi.x, sh);
+    acc[4 * d + 3] = acc[4 * d + 3] + w * __builtin_ldexpf(hi.y, sh);
+  }
+}
+// vector c of a unit's 16 * sizeof(T) output bytes
+template <typename T>
+__device__ __forceinline__ v4u combinemx_pack(const float (&acc)[16], int c) {
+  v4u x;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if constexpr (sizeof(T) == 4) x[i] = CombineElem<T>::down(acc[4 * c + i]);
+    else x[i] = (uint32_t)CombineElem<T>::down(acc[8 * c + 2 * i]) | (uint32_t)CombineElem<T>::down(acc[8 * c + 2 * i + 1]) << 16;
+  }
+  return x;
+}
+
+// 2 KiB of codes per source and batch: 8 sources are 64 code registers and 16 scale registers (a byte each) in flight
+constexpr int kCombineMxV = 2;
+
+template <typename T, int G, int V>
+__device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_wide(const CollParams& p, const CombineArgs& v, u64 soff, u64 b,
+                                                                int lane) {
+  constexpr uint32_t UB = 16 * sizeof(T), step = 64 * V;
+  const int n = p.n;
+  const uint32_t rb = v.row_bytes, rc = rb / (uint32_t)sizeof(T), nu = rc >> 4, P = rc + (rc >> 5), topk = v.topk,
+                 rpb = 64 / topk;
+  const u64 nslots = (u64)v.nrows * topk;
+  // lane l: entry l of the rpb rows from row `base` on (-1 / 0 past them and past the matrix)
+  auto fetch_i = [&](u64 base) -> int32_t {
+    const u64 e = base * topk + (u64)lane;
+    return (uint32_t)lane < rpb * topk && e < nslots ? v.slotidx[e] : -1;
+  };
+  auto fetch_w = [&](u64 base) -> float {
+    const u64 e = base * topk + (u64)lane;
+    return (uint32_t)lane < rpb * topk && e < nslots ? (v.weights ? v.weights[e] : 1.0f) : 0.0f;
+  };
+  u64 tb = soff / rb;
+  int32_t ic = fetch_i(tb), in = fetch_i(tb + rpb);
+  float wc = fetch_w(tb), wn = fetch_w(tb + rpb);
+  for (u64 t = tb; t * rb < b; ++t) {
+    if (t - tb >= rpb) {
+      tb += rpb;
+      ic = in;
+      wc = wn;
+      in = fetch_i(tb + rpb);
+      wn = fetch_w(tb + rpb);
+    }
+    uint32_t i0, i1;
+    rows_units(soff, b, t * rb, 0, UB, nu, &i0, &i1);
+    const uint32_t nseg = i1 - i0;
+    if (nseg == 0) continue;
+    const rsrc_t dst = make_rsrc(p.recv + t * v.stride_bytes + (u64)i0 * UB, nseg * UB);
+    const uint32_t s0 = (uint32_t)(t - tb) * topk;
+    rsrc_t src[G];
+    float w[G];
+    // slots k0 .. k0 + G - 1 of row t: their records' descriptors, their weights
+    auto open = [&](uint32_t k0) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const uint32_t k = k0 + (uint32_t)g;
+        const int sl = __builtin_amdgcn_readfirstlane((int)(s0 + (k < topk ? k : 0u)));
+        const int32_t j = k < topk ? __builtin_amdgcn_readlane(ic, sl) : -1;
+        const float wk = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(wc), sl));
+        const int q = combine_owner(v, n, j);
+        const int qq = q < 0 ? 0 : q;
+        const char* from = p.peer_send[qq] + v.src_off[qq] + ((u64)(uint32_t)j - v.lo[qq]) * P;
+        src[g] = make_rsrc(q < 0 ? p.send : from, q < 0 ? 0u : P);
+        w[g] = q < 0 ? 0.0f : wk;
+      }
+    };
+    if (topk <= (uint32_t)G) open(0);
+    for (uint32_t at = 0; at < nseg; at += step) {
+      float acc[V][16];
+#pragma unroll
+      for (int u = 0; u < V; ++u)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[u][e] = 0.0f;
+      for (uint32_t k0 = 0; k0 < topk; k0 += G) {
+        if (topk > (uint32_t)G) open(k0);
+        v4u x[G][V];
+        uint32_t sc[G][V];
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+          for (int u = 0; u < V; ++u) {
+            // (a lane past the segment loads nothing: an offset beyond every record)
+            const uint32_t un = at + (uint32_t)(u * 64 + lane), iu = i0 + un;
+            x[g][u] = ld_slot16(src[g], un < nseg ? iu * 16u : kMxNowhere);
+            sc[g][u] = Scal<1>::ld(src[g], un < nseg ? rc + (iu >> 1) : kMxNowhere);
+          }
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+          for (int u = 0; u < V; ++u) combinemx_mac16(acc[u], x[g][u], sc[g][u], w[g]);
+      }
+#pragma unroll
+      for (int u = 0; u < V; ++u)
+#pragma unroll
+        for (int c = 0; c < (int)sizeof(T); ++c)
+          st_slot16(dst, (at + (uint32_t)(u * 64 + lane)) * UB + (uint32_t)c * 16u, combinemx_pack<T>(acc[u], c));
+    }
+  }
+}
+
+// Unit `unit` (16 elements) of output row `row`, by this lane alone: its topk slots in order.  Rank q's
+// send is peer_send[q], or `src` for every q (LOCAL).  A record lies whole in the window of its first byte.
+template <typename T, bool LOCAL>
+__device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_unit(const CollParams* p, const char* src, char* recv,
+                                                                const CombineArgs& v, int n, u64 row, uint32_t unit) {
+  const uint32_t rc = v.row_bytes / (uint32_t)sizeof(T), P = rc + (rc >> 5), topk = v.topk;
+  float acc[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+  for (uint32_t k = 0; k < topk; ++k) {
+    const u64 at = row * topk + k;
+    const int32_t j = v.slotidx[at];
+    const float w = v.weights ? v.weights[at] : 1.0f;
+    int q = -1;
+    u64 qlo = 0;  // combine_owner, keeping the range's start (the ranges are read with uniform indices)
+    for (int s = 0; s < n; ++s) {
+      const u64 l = v.lo[s];
+      if (j >= 0 && (u64)j >= l && (u64)j - l < v.cnt[s]) q = s, qlo = l;
+    }
+    const bool valid = q >= 0;
+    const int qq = valid ? q : 0;
+    const u64 rel = ((u64)(uint32_t)j - qlo) * P;  // the record's byte offset in q's block
+    const uint32_t key = (uint32_t)qq | (uint32_t)(rel >> 31) << 4;
+    v4u x4 = {0u, 0u, 0u, 0u};
+    uint32_t sc = 0;
+    bool pending = valid;
+    while (pending) {
+      const uint32_t kq = __builtin_amdgcn_readfirstlane(key);
+      if (key == kq) {
+        const int sq = (int)(kq & 15u);
+        const u64 win = (u64)(kq >> 4) << 31, left = v.cnt[sq] * P - win;
+        const char* from = src;
+        if constexpr (!LOCAL) from = p->peer_send[sq];
+        // (the window's records end below 2 GiB + P <= 2 GiB + 16896 bytes)
+        const rsrc_t s = make_rsrc(from + v.src_off[sq] + win, (uint32_t)(left < 0x80008000ull ? left : 0x80008000ull));
+        const uint32_t o = (uint32_t)(rel - win);
+        x4 = ld_slot16(s, o + unit * 16u);
+        sc = Scal<1>::ld(s, o + rc + (unit >> 1));
+        pending = false;
+      }
+    }
+    if (valid) combinemx_mac16(acc, x4, sc, w);
+  }
+  char* to = recv + row * v.stride_bytes + (u64)unit * (16 * sizeof(T));
+#pragma unroll
+  for (int c = 0; c < (int)sizeof(T); ++c)
+    __builtin_nontemporal_store(combinemx_pack<T>(acc, c), reinterpret_cast<v4u_dw*>(to + 16 * c));
+}
+
+// slice [soff, b) of this rank's packed output rows
+template <typename T>
+__device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_slice(const CollParams& p, const CombineArgs& v, u64 soff, u64 b,
+                                                                 int lane) {
+  constexpr uint32_t UB = 16 * sizeof(T);
+  const uint32_t rb = v.row_bytes;
+  const MxLanes g = mx_lanes(rb / (uint32_t)sizeof(T));
+  if (g.lanes == 64) {
+    if (v.topk <= 1) combinemx_wide<T, 1, kCombineMxV>(p, v, soff, b, lane);
+    else if (v.topk <= 2) combinemx_wide<T, 2, kCombineMxV>(p, v, soff, b, lane);
+    else if (v.topk <= 4) combinemx_wide<T, 4, kCombineMxV>(p, v, soff, b, lane);
+    else combinemx_wide<T, 8, kCombineMxV>(p, v, soff, b, lane);
+    return;
+  }
+  const uint32_t lr = (uint32_t)lane / g.lanes, lc = (uint32_t)lane % g.lanes;
+  if (lr >= g.rows) return;
+  for (u64 row = soff / rb + lr; row * rb < b; row += g.rows) {
+    const u64 at = row * rb + (u64)lc * UB;  // the unit's first byte: the slice that holds it stores the unit
+    if (at >= soff && at < b) combinemx_unit<T, false>(&p, nullptr, p.recv, v, p.n, row, lc);
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) MNCCL_SCALAR_F32 combinemx_fold(CollParams p, CombineArgs v) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half<false, true>(
+      p, s_tx, s_rx, [&p, &v](u64 coff, uint32_t len, int lane) { combinemx_slice<T>(p, v, coff, coff + len, lane); }, 0,
+      (u64)v.nrows * v.row_bytes);
+}
+
+// The same fold as a plain grid kernel out of ONE local buffer of records that holds block q at byte
+// src_off[q] (one rank; every count zero; the padded ring's packed stage): a thread per unit, the same
+// units, the same order of the sum.
+template <typename T>
+__global__ void __launch_bounds__(256) MNCCL_SCALAR_F32 combinemx_local(CombineArgs v, const char* src, char* recv, int n) {
+  const uint32_t nu = v.row_bytes / (16u * (uint32_t)sizeof(T));
+  const u64 total = (u64)v.nrows * nu;
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (u64)gridDim.x * blockDim.x)
+    combinemx_unit<T, true>(nullptr, src, recv, v, n, i / nu, (uint32_t)(i % nu));
+}
+
 // ---------------------------------------------------------------- point to point
 // ncclSend / ncclRecv (p2p_kernel): a send is the sender's half of one ring hop to an arbitrary
 // peer, a recv the receiver's half, on the scratch protocol of the file header -- the peer's region
@@ -3642,6 +3876,42 @@ hipError_t launch_combine_local(int dtype, int n, const CombineArgs& v, const vo
   const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);  // the rest by the grid's stride
   return for_combine_type(dtype, [&](auto t) {
     hipLaunchKernelGGL(combine_local<typename decltype(t)::type>, dim3(blocks), dim3(256), 0, st, v,
+                       static_cast<const char*>(src), static_cast<char*>(recv), n);
+    return hipGetLastError();
+  });
+}
+
+// what the MXFP8 combine's kernels assume of their argument beyond combine_args_ok: whole units and
+// whole blocks in every row, a strip of scale bytes mxblock.h allows, dword-aligned vectors on both sides
+static bool combinemx_args_ok(int dtype, const CombineArgs& v, const void* recv, int n) {
+  const uint32_t esz = (uint32_t)dtype_size(dtype), rc = v.row_bytes / esz;
+  if (!combine_args_ok(v, n) || v.row_bytes % esz || !v.vec) return false;
+  if (rc % kMxRowMultiple || rc < kMxRowMultiple || rc > kMxMaxRowcount) return false;
+  for (int q = 0; q < n; ++q)
+    if (v.cnt[q] && v.src_off[q] % 4) return false;
+  return ((u64)(uintptr_t)recv | v.stride_bytes) % 4 == 0;
+}
+
+hipError_t launch_combinemx(int dtype, int C, int nt, const CollParams& p, const CombineArgs& v, hipStream_t st) {
+  // (a rank with no output rows passes a stand-in list, Comm::combine: never read, but not NULL)
+  if (p.coll != kCollAllToAllVCombineMx || p.n < 2 || !v.slotidx || (dtype != kF32 && dtype != kF16 && dtype != kBF16) ||
+      !combinemx_args_ok(dtype, v, p.recv, p.n) || (u64)v.nrows * v.row_bytes > p.chunk_bytes)
+    return hipErrorInvalidValue;
+  return for_combine_type(dtype, [&](auto t) {
+    hipLaunchKernelGGL(combinemx_fold<typename decltype(t)::type>, dim3(C), dim3(nt), 0, st, p, v);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_combinemx_local(int dtype, int n, const CombineArgs& v, const void* src, void* recv, hipStream_t st) {
+  if ((dtype != kF32 && dtype != kF16 && dtype != kBF16) || !combinemx_args_ok(dtype, v, recv, n) || (v.nrows && !recv) ||
+      (u64)(uintptr_t)src % 4)
+    return hipErrorInvalidValue;
+  if (v.nrows == 0) return hipSuccess;
+  const u64 want = ((u64)v.nrows * (v.row_bytes / (16u * (uint32_t)dtype_size(dtype))) + 255) / 256;
+  const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);  // the rest by the grid's stride
+  return for_combine_type(dtype, [&](auto t) {
+    hipLaunchKernelGGL(combinemx_local<typename decltype(t)::type>, dim3(blocks), dim3(256), 0, st, v,
                        static_cast<const char*>(src), static_cast<char*>(recv), n);
     return hipGetLastError();
   });

@@ -175,7 +175,10 @@ enum Coll : int {
   // out (mxblock.h); its fallback is kCollAllToAllV's padded ring behind a gather-and-quantise kernel
   kCollAllToAllVRowsMx = 13,
   // mncclAllToAllvRowsMxfp4: the same with MXFP4 records (mxblock.h's mx4_ rules)
-  kCollAllToAllVRowsMx4 = 14
+  kCollAllToAllVRowsMx4 = 14,
+  // mncclAllToAllvCombineMxfp8: kCollAllToAllVCombine whose send side holds MXFP8 records, decoded in
+  // the fold (combinemx.h); the same fallback, with the records moved as bytes
+  kCollAllToAllVCombineMx = 15
 };
 
 // r, root: gather and scatter only (their op count depends on the rank's place in the chain; the

@@ -1684,6 +1684,42 @@ int mnccl_sim_combine_args(int n, int esz, uint64_t recv_addr, size_t nrows, siz
   return 0;
 }
 
+// csrc/combinemx.h, the host-side rules of mncclAllToAllvCombineMxfp8: one rank's local checks (an MxLocal
+// or a CombineLocal verdict; esz is the OUTPUT element's), the kernels' argument block (out: n lo[], n
+// cnt[], n src_off[], then row_bytes), and the host decode-and-fold of one output row out of `nrec`
+// packed records, before its rounding to the datatype.
+int mnccl_sim_combinemx_check_local(int n, int esz, const void* send, const size_t* sendcounts, const size_t* sdispls,
+                                    const void* recv, size_t nrows, size_t rowstride, const int32_t* slotidx,
+                                    const float* weights, int topk, const size_t* recvcounts, const size_t* rdispls,
+                                    size_t rowcount) {
+  if (n < 1 || n > mnccl::kVarMaxRanks || esz < 1) return -2;
+  return mnccl::combinemx_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights, topk,
+                                      recvcounts, rdispls, rowcount);
+}
+int mnccl_sim_combinemx_args(int n, int esz, uint64_t recv_addr, size_t nrows, size_t rowstride, int topk,
+                             const size_t* recvcounts, const size_t* rdispls, size_t rowcount, const uint64_t* send_addr,
+                             const uint64_t* peer_sdispl, uint64_t* out) {
+  if (n < 1 || n > mnccl::kVarMaxRanks) return -2;
+  const void* send_of[mnccl::kVarMaxRanks];
+  for (int q = 0; q < n; ++q) send_of[q] = (const void*)(uintptr_t)send_addr[q];
+  mnccl::CombineArgs v;
+  mnccl::combinemx_fill_args(&v, n, esz, (const void*)(uintptr_t)recv_addr, nrows, rowstride, nullptr, nullptr, topk,
+                             recvcounts, rdispls, rowcount, send_of, peer_sdispl);
+  for (int q = 0; q < n; ++q) {
+    out[q] = v.lo[q];
+    out[n + q] = v.cnt[q];
+    out[2 * n + q] = v.src_off[q];
+  }
+  out[3 * n] = v.row_bytes;
+  return 0;
+}
+int mnccl_sim_combinemx_fold_row(const uint8_t* recs, uint64_t nrec, uint32_t rowcount, const int32_t* slots,
+                                 const float* weights, int topk, float* out) {
+  if (rowcount % mnccl::kMxBlock || topk < 1 || topk > mnccl::kCombineMaxTopk) return -2;
+  mnccl::combinemx_fold_row(recs, nrec, rowcount, slots, weights, topk, out);
+  return 0;
+}
+
 // csrc/vhalves.h, the host-side rules of mncclAllGatherv / mncclReduceScatterv, and schedule.h's length
 // rule for them.  mnccl_vhalf_rows_differ: counts / displs are n x n, row r what rank r passed.
 int mnccl_vhalf_check_local(int n, int rank, int esz, const void* array_buf, const size_t* counts, const size_t* displs,

@@ -105,6 +105,8 @@ SIGNATURES = {
                                      ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllToAllvCombine": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _SZ, _VP, _VP, _I,
                                    ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
+    "mncclAllToAllvCombineMxfp8": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _SZ, _VP, _VP, _I,
+                                        ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllGatherv": (_I, [_VP, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _I, _VP, _VP]),
     "mncclReduceScatterv": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclGather": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
@@ -341,6 +343,16 @@ class Comm:
         arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
         return load().mncclAllToAllvCombine(send_ptr, arrays[0], arrays[1], recv_ptr, nrows, rowstride, slotidx_ptr,
                                             weights_ptr, topk, arrays[2], arrays[3], rowcount, dtype, self.handle, stream)
+
+    def all_to_all_v_combine_mxfp8(self, send_ptr, sendcounts, sdispls, recv_ptr, nrows, rowstride, slotidx_ptr, weights_ptr,
+                                   topk, recvcounts, rdispls, rowcount, dtype=ncclBfloat16, stream=0):
+        """mncclAllToAllvCombineMxfp8: all_to_all_v_combine whose send rows are MXFP8 records of
+        rowcount + rowcount // 32 bytes (what all_to_all_v_rows_mxfp8 delivers), decoded in the fold; dtype
+        and rowstride are the recv matrix's (float32, float16 or bfloat16).  Counts, displacements and
+        slotidx are in records; rowcount is a multiple of 128 in [128, 16384].  Returns the ncclResult_t."""
+        arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
+        return load().mncclAllToAllvCombineMxfp8(send_ptr, arrays[0], arrays[1], recv_ptr, nrows, rowstride, slotidx_ptr,
+                                                 weights_ptr, topk, arrays[2], arrays[3], rowcount, dtype, self.handle, stream)
 
     def all_gather_v(self, send_ptr, sendcount, recv_ptr, recvcounts, rdispls, dtype=ncclFloat, stream=0):
         """mncclAllGatherv: rank q's `sendcount` elements of send end up at elements [rdispls[q],

@@ -76,6 +76,9 @@ persistent form (mncclAlgoRead), fp32 Sum, stream-ordered (MINI_NCCL_BLOCKING=0)
                     buffer, then ncclAllToAllv.  Ratio alltoallv_rows_over_composed beside both spreads
     alltoallv_combine  mncclAllToAllvCombine, the way back of the same layer: the rows kinds' matrix
                     transposed, bf16 rows of --row-elems elements, every token's top-2 rows folded by weight
+    alltoallv_combine_mxfp8 / alltoallv_combine_mxfp8_composed   mncclAllToAllvCombineMxfp8 on as many MXFP8 records, and
+                    what a caller runs without it: a dequantise pass to bf16 rows, then mncclAllToAllvCombine.  Ratios
+                    alltoallv_combine_mxfp8_over_composed and, when timed too, alltoallv_combine_mxfp8_over_alltoallv_combine
     alltoallv_combine_composed   what a caller runs without it, on the same data: ncclAllToAllv into a
                     packed buffer, then the fold as a kernel of its own (combine_local, through a one-rank
                     communicator).  Ratio alltoallv_combine_over_composed beside both spreads
@@ -115,7 +118,7 @@ KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_pr
          "all_gather_v", "reduce_scatter_v", "all_gather_v_skew", "reduce_scatter_v_skew", "all_gather_padded",
          "reduce_scatter_padded", "alltoallv_rows", "alltoallv_rows_composed", "alltoallv_combine",
          "alltoallv_combine_composed", "alltoallv_rows_mxfp8", "alltoallv_rows_mxfp8_composed", "alltoallv_rows_mxfp4",
-         "alltoallv_rows_mxfp4_composed")
+         "alltoallv_rows_mxfp4_composed", "alltoallv_combine_mxfp8", "alltoallv_combine_mxfp8_composed")
 # mncclAllToAllvRows beside what a caller composes without it, on the same matrix and indices
 ROWS_KINDS = ("alltoallv_rows", "alltoallv_rows_composed")
 # mncclAllToAllvRowsMxfp8 beside the quantise kernel followed by ncclAllToAllv of bytes, same matrix and indices
@@ -124,13 +127,15 @@ MX_KINDS = ("alltoallv_rows_mxfp8", "alltoallv_rows_mxfp8_composed")
 MX4_KINDS = ("alltoallv_rows_mxfp4", "alltoallv_rows_mxfp4_composed")
 # mncclAllToAllvCombine beside ncclAllToAllv plus a fold of the caller's own, on the same data
 COMBINE_KINDS = ("alltoallv_combine", "alltoallv_combine_composed")
+# mncclAllToAllvCombineMxfp8 beside a dequantise pass to bf16 followed by mncclAllToAllvCombine, on the same counts and slots
+COMBINE_MX_KINDS = ("alltoallv_combine_mxfp8", "alltoallv_combine_mxfp8_composed")
 # the kinds that need the padded buffers (n blocks of the skewed shape's largest block)
 PADDED_KINDS = ("all_gather_padded", "reduce_scatter_padded")
 VHALF_SKEW = ("all_gather_v_skew", "reduce_scatter_v_skew") + PADDED_KINDS
 # the kinds --dtype bf16 can time (the others' helpers are written for fp32 elements)
 # the kinds that run while big_b is a registered window, and the scratch form each is measured against
 WIN_KINDS = {"p2p_neighbor_win": "p2p_neighbor", "p2p_all_pairs_win": "p2p_all_pairs"}
-BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce") + ROWS_KINDS + COMBINE_KINDS + MX_KINDS + MX4_KINDS
+BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce") + ROWS_KINDS + COMBINE_KINDS + COMBINE_MX_KINDS + MX_KINDS + MX4_KINDS
 
 
 def skew_matrix(n, chunk, seed):
@@ -197,12 +202,15 @@ def rows_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stre
 
 
 def combine_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stream):
-    """(fused, composed, buffers, solo): the way back of rows_calls' layer on its matrix -- this rank's
+    """(fused, composed, buffers, solo, mx, mx_composed): the way back of rows_calls' layer on its matrix -- this rank's
     experts return C[q][rank] rows to rank q and it gets C[rank][q] back from q, bf16 rows of `row_elems`
     elements; half as many tokens as rows come back, each folding two of them (a seeded top-2 list over
     the packed sequence) by seeded weights.  Fused: mncclAllToAllvCombine.  Composed: ncclAllToAllv into
     a packed buffer, then the same fold out of it (mncclAllToAllvCombine on a one-rank communicator runs
-    combine_local alone)."""
+    combine_local alone).  mx: mncclAllToAllvCombineMxfp8 with as many MXFP8 records of `row_elems` elements in
+    place of the rows.  mx_composed: the records dequantised to bf16 rows by a kernel of their own (the new call on
+    the one-rank communicator with topk 1, the identity list and no weights runs combinemx_local alone), then
+    mncclAllToAllvCombine."""
     import numpy as np
     rb = 2 * row_elems
     per = max(1, block_bytes // rb)
@@ -226,7 +234,20 @@ def combine_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, s
         r = comm.all_to_all_v(send.ptr, e(sc), e(starts(sc)), packed.ptr, e(rc), e(starts(rc)), M.ncclBfloat16, stream)
         return r or solo.all_to_all_v_combine(packed.ptr, [back], [0], y.ptr, tokens, row_elems, idx.ptr, w.ptr, 2, [back], [0],
                                               row_elems, M.ncclBfloat16, stream)
-    return fused, composed, [send, packed, y, idx, w], solo
+    if row_elems % 128 or not 128 <= row_elems <= 16384:  # no records of such rows: the mx kinds fail when called
+        return fused, composed, [send, packed, y, idx, w], solo, lambda: 4, lambda: 4
+    P, out = row_elems + row_elems // 32, max(1, sum(sc))
+    recs, ident = hip_rt.DeviceBuffer(out * P, fresh=True), hip_rt.DeviceBuffer(4 * out, fresh=True)
+    recs.fill_byte(0x38)  # (every element e4m3 1.0 at scale 2^-71: finite)
+    ident.upload(np.arange(out, dtype=np.int32))
+    mx = lambda: comm.all_to_all_v_combine_mxfp8(recs.ptr, sc, starts(sc), y.ptr, tokens, row_elems, idx.ptr, w.ptr, 2, rc,
+                                                 starts(rc), row_elems, M.ncclBfloat16, stream)
+
+    def mx_composed():
+        r = solo.all_to_all_v_combine_mxfp8(recs.ptr, [out], [0], send.ptr, out, row_elems, ident.ptr, None, 1, [out], [0],
+                                            row_elems, M.ncclBfloat16, stream)
+        return r or fused()
+    return fused, composed, [send, packed, y, idx, w, recs, ident], solo, mx, mx_composed
 
 
 def half_skew_counts(n, chunk):
@@ -341,8 +362,9 @@ def rank_main(a):
             M, hip_rt, comm, n, a.rank, a.bytes // n, a.row_elems, a.skew_seed if a.rows_skew else -1, st.handle)
         pads += more
     solo2 = None
-    if any(k in COMBINE_KINDS for k in kinds):
-        calls["alltoallv_combine"], calls["alltoallv_combine_composed"], more, solo2 = combine_calls(
+    if any(k in COMBINE_KINDS + COMBINE_MX_KINDS for k in kinds):
+        (calls["alltoallv_combine"], calls["alltoallv_combine_composed"], more, solo2, calls[COMBINE_MX_KINDS[0]],
+         calls[COMBINE_MX_KINDS[1]]) = combine_calls(
             M, hip_rt, comm, n, a.rank, a.bytes // n, a.row_elems, a.skew_seed if a.rows_skew else -1, st.handle)
         pads += more
     window = [None]
@@ -474,7 +496,7 @@ def main():
         "rounds_ms": {k: [round(x, 4) for x in v] for k, v in rounds.items()},
         "hbm_bytes": {k: (2 * n if k in ("all_reduce", "all_reduce_premul", "all_to_all", "all_to_all_v") else n + 1) * chunk_bytes
                       for k in kinds if k not in ("all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
-                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") + VHALF_SKEW + ROWS_KINDS + COMBINE_KINDS + MX_KINDS + MX4_KINDS
+                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") + VHALF_SKEW + ROWS_KINDS + COMBINE_KINDS + COMBINE_MX_KINDS + MX_KINDS + MX4_KINDS
                       and k not in WIN_KINDS},
         "ratio": dict([(f"{k}_over_all_reduce", round(med[k] / med["all_reduce"], 4)) for k in kinds if k != "all_reduce"] +
                       [(f"{k}_over_{y}", round(med[k] / med[y], 4))
@@ -554,6 +576,14 @@ def main():
         res["combine"] = {"row_elems": a.row_elems, "row_bytes": 2 * a.row_elems, "topk": 2, "matrix": "skew" if a.rows_skew else "balanced"}
         res["ratio"]["alltoallv_combine_over_composed"] = round(med["alltoallv_combine"] / med["alltoallv_combine_composed"], 4)
         for k in COMBINE_KINDS:
+            res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
+    if all(k in med for k in COMBINE_MX_KINDS):
+        res["combine_mxfp8"] = {"row_elems": a.row_elems, "record_bytes": a.row_elems + a.row_elems // 32,
+                                "out_row_bytes": 2 * a.row_elems, "topk": 2, "matrix": "skew" if a.rows_skew else "balanced"}
+        res["ratio"]["alltoallv_combine_mxfp8_over_composed"] = round(med[COMBINE_MX_KINDS[0]] / med[COMBINE_MX_KINDS[1]], 4)
+        if "alltoallv_combine" in med:
+            res["ratio"]["alltoallv_combine_mxfp8_over_alltoallv_combine"] = round(med[COMBINE_MX_KINDS[0]] / med["alltoallv_combine"], 4)
+        for k in COMBINE_MX_KINDS + (("alltoallv_combine",) if "alltoallv_combine" in med else ()):
             res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
     if "all_gather" in rounds:
         res["all_gather_spread"] = round((max(rounds["all_gather"]) - min(rounds["all_gather"])) / med["all_gather"], 4)
