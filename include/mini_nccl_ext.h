@@ -42,6 +42,8 @@
  *   mncclAllToAllvRowsMxfp8  the same from a bf16 / fp16 matrix with every row quantised to MXFP8 on the
  *                        way out: e4m3 elements and one E8M0 scale per 32, in one record per row.
  *   mncclAllToAllvRowsMxfp4  the same with e2m1 elements, two to a byte: MXFP4 records.
+ *   mncclAllToAllvRowsFp8Block128  the same with e4m3 elements and one f32 scale per 128 elements: the
+ *                        "1 x 128" activation format of the DeepSeek-V3 recipe's FP8 experts.
  *   mncclAllToAllvCombine  the way back: the token owner pulls the top-k rows of each token out of the
  *                        experts' send buffers and folds them by gate weight (no packed recv, no atomics).
  *   mncclAllToAllvCombineMxfp8  the same out of MXFP8 records, decoded in the fold: half of bf16's bytes back.
@@ -111,7 +113,7 @@ extern "C" {
    mncclAllGatherv and mncclReduceScatterv were added the same way (detected by symbol;
    mncclCommInfo_t did not grow); still 600: mncclAllToAllvRows was added the same way; still 600:
    mncclAllToAllvRowsMxfp8 was added the same way; still 600: mncclAllToAllvRowsMxfp4 was added the
-   same way */
+   same way; still 600: mncclAllToAllvRowsFp8Block128 was added the same way */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -541,6 +543,55 @@ ncclResult_t mncclAllToAllvRowsMxfp4(const void* sendbuff, size_t nrows, size_t 
                                      const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                                      const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
                                      ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
+
+/* mncclAllToAllvRowsMxfp8 with the block-scaled FP8 format of the DeepSeek-V3 recipe instead of OCP
+ * MX: e4m3 elements with one IEEE single scale per 128 consecutive elements of a row (the "1 x 128"
+ * activation quantisation that block-scale FP8 grouped GEMMs and fused-MoE kernels take as their A
+ * operand), 1.03 bytes per element on the wire instead of bf16's 2 -- a count from the layout.
+ * Detected by symbol (MNCCL_VERSION stays 600).
+ *
+ * The send side is mncclAllToAllvRowsMxfp8's: the strided bf16 / fp16 matrix (`datatype` is the
+ * matrix's), the device-side int32 index list read when the call runs (at replay, for a captured
+ * call), counts and displacements in rows, an index outside [0, nrows) standing for a row of zeros and
+ * causing no access.
+ *
+ * The receive side.  Each delivered row is one RECORD of P = rowcount + rowcount / 32 bytes: first
+ * rowcount e4m3 (OCP, e4m3fn) bytes, then rowcount / 128 IEEE single scales, little-endian, one per
+ * block of 128 consecutive elements.  recvcounts / rdispls are in records; bytes outside every block
+ * are never written.  Records are dword-aligned, so the scale part of a record is an aligned float
+ * array at row pitch P.
+ *
+ * Result, bit for bit on every schedule and slice size.  Per block of 128 elements, each widened
+ * exactly to f32: A is the largest magnitude, taken on the f32 bit patterns.  A's exponent field 255
+ * (a NaN or an infinity in the block): scale word 0x7FC00000 and all 128 element bytes 0x7F.  Otherwise
+ * a = max(A, 1e-4f), inv = 448.0f / a and scale = a / 448.0f, each one correctly rounded single
+ * division; the scale word is `scale`, and each element byte is e4m3 of round_f32(x * inv): one single
+ * multiply, then one rounding to nearest even onto e4m3's grid, subnormals of e4m3 included; results
+ * of magnitude 448 or above saturate to +-448 and the sign of zero is kept.  Subnormal bf16 / fp16
+ * inputs are not flushed.  A block of zeros (an out-of-range row) gives scale 1e-4f / 448.0f and bytes
+ * 0x00 / 0x80.  This is the rule of DeepSeek's and DeepEP's per-token-group quantiser: amax clamped at
+ * 1e-4, x * (448 / amax), scale amax / 448.
+ *
+ * Checks: mncclAllToAllvRowsMxfp8's, in its order and with its verdicts -- the open group; a datatype
+ * other than the two: ncclInternalError; rowcount % 128 != 0 or outside [128, 16384]:
+ * ncclInvalidArgument; dword alignment of sendbuff, rowstride in bytes and recvbuff; the overlap,
+ * overflow and NULL checks with P bytes per record; the rendezvous verdicts, all-zero counts, idle
+ * ranks with NULL buffers, one rank.  The call has a collective id of its own -- its record is as long
+ * as MXFP8's, so only that tells the two apart: ranks that mix it with mncclAllToAllvRowsMxfp8 or
+ * mncclAllToAllvRowsMxfp4, or that differ in rowcount, get ncclInvalidUsage on every rank with nothing
+ * launched and the communicator still usable.
+ *
+ * Schedules: mncclAllToAllvRowsMxfp8's, a kernel pair of its own (eight lanes per block of 128).  Where
+ * ncclAllToAllv runs the read schedule, one persistent kernel gathers, quantises and pushes into the
+ * peers' recv (last_algo mncclAlgoRead); otherwise a grid kernel gathers and quantises into the padded
+ * ring's stage and the rest is the fallback by bytes (mncclAlgoRing, refused under capture); one rank:
+ * the grid kernel alone.
+ * Not built: UE8M0-rounded scales, e5m2, group sizes other than 128, a separate or transposed scales
+ * buffer, f32 input, a combine out of these records, registered windows. */
+ncclResult_t mncclAllToAllvRowsFp8Block128(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                                           const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                                           const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
+                                           ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
 
 /* The way back of the same layer: ncclAllToAllv whose packed recv is never built, because the token
  * owner folds the up to top-k returned rows of each token, each times its gate weight, into one

@@ -422,6 +422,30 @@ ncclResult_t mncclAllToAllvRowsMxfp4(const void* sendbuff, size_t nrows, size_t 
   }
 }
 
+// The same with e4m3 records that carry one f32 scale per 128 elements (mini_nccl_ext.h): the MXFP8
+// entry's checks in its order (Comm::all_to_all_v_rows_fp8b, fp8block.h).
+ncclResult_t mncclAllToAllvRowsFp8Block128(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                                           const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                                           const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
+                                           ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
+  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
+  RoctxRange range("mini_ncclAllToAllvRowsFp8Block128");
+  if (datatype != ncclFloat16 && datatype != ncclBfloat16) {
+    fprintf(stderr, "[Mini-NCCL] AllToAllvRowsFp8Block128 Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->all_to_all_v_rows_fp8b(sendbuff, nrows, rowstride, rowidx, sendcounts, sdispls,
+                                                                 recvbuff, recvcounts, rdispls, rowcount, (int)datatype, stream);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] AllToAllvRowsFp8Block128 Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
 // The way back (mini_nccl_ext.h): mncclAllToAllvRows' checks in its order; the fold is in float, so
 // only the datatypes with one are taken.  The buffers and the lists are checked with the counts and
 // nrows where the communicator's size is known (Comm::combine, combine.h).

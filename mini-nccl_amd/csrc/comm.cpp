@@ -1198,17 +1198,23 @@ bool Comm::gather_rows(const VarRow& mine, int dtype, VarRow* rows, int coll, in
 // kernels.hip rowsmx_push.  Else rowsmx_pack quantises into the stage where rows_pack gathers, unit P.
 // mncclAllToAllvRowsMxfp4 (kRowsMxfp4) is the MXFP8 call with P4 = rowcount / 2 + rowcount / 32 bytes for
 // P, a collective id and a rendezvous flag of its own (kVarRowsMx4) and the kernels rowsmx4_push / rowsmx4_pack.
+// mncclAllToAllvRowsFp8Block128 (kRowsFp8Block128) is the MXFP8 call with fp8block.h's record -- as long as
+// MXFP8's -- a collective id and a rendezvous flag of its own (kVarRowsFp8b) and rowsfp8b_push / rowsfp8b_pack.
 ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
                                 const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream,
                                 const RowsCall* rows_call) {
   if (sticky_ != ncclSuccess) return sticky_;
   if (check_status() != ncclSuccess) return sticky_;
   const int n = nranks_, esz = dtype_size(dtype);
-  const bool fp4 = rows_call && rows_call->fmt == kRowsMxfp4, mx = fp4 || (rows_call && rows_call->fmt == kRowsMxfp8);
-  const char* const name = fp4 ? "mncclAllToAllvRowsMxfp4" : mx ? "mncclAllToAllvRowsMxfp8" : rows_call ? "mncclAllToAllvRows" : "ncclAllToAllv";
-  const int coll = fp4 ? kCollAllToAllVRowsMx4 : mx ? kCollAllToAllVRowsMx : rows_call ? kCollAllToAllVRows : kCollAllToAllV;
-  // a block's unit in bytes: the element, the row, or the row's MXFP8 / MXFP4 record
-  const size_t unit = fp4 ? (size_t)mx4_record_bytes(rows_call->rowcount) : mx ? (size_t)mx_record_bytes(rows_call->rowcount)
+  const bool fp4 = rows_call && rows_call->fmt == kRowsMxfp4, b128 = rows_call && rows_call->fmt == kRowsFp8Block128;
+  const bool mx = fp4 || b128 || (rows_call && rows_call->fmt == kRowsMxfp8);  // a quantised record: the walk's kernels
+  const char* const name = fp4 ? "mncclAllToAllvRowsMxfp4" : b128 ? "mncclAllToAllvRowsFp8Block128" : mx ? "mncclAllToAllvRowsMxfp8"
+                           : rows_call ? "mncclAllToAllvRows" : "ncclAllToAllv";
+  const int coll = fp4 ? kCollAllToAllVRowsMx4 : b128 ? kCollAllToAllVRowsFp8b : mx ? kCollAllToAllVRowsMx
+                   : rows_call ? kCollAllToAllVRows : kCollAllToAllV;
+  // a block's unit in bytes: the element, the row, or the row's MXFP8 / MXFP4 / FP8-block-128 record
+  const size_t unit = fp4 ? (size_t)mx4_record_bytes(rows_call->rowcount) : b128 ? (size_t)fp8b_record_bytes(rows_call->rowcount)
+                      : mx ? (size_t)mx_record_bytes(rows_call->rowcount)
                       : rows_call ? rows_call->rowcount * (size_t)esz : (size_t)esz;
   if (rows_call) {
     const int local = mx ? mx_check_local(n, esz, send, rows_call->nrows, rows_call->rowstride, rows_call->rowidx, sendcounts,
@@ -1290,7 +1296,7 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
         m.idx_off[q] = sdispls[q];
         m.count[q] = sendcounts[q];
       }
-      hip_check((fp4 ? launch_rowsmx4_pack : launch_rowsmx_pack)(dtype, m, stream), "kernel launch");
+      hip_check((fp4 ? launch_rowsmx4_pack : b128 ? launch_rowsfp8b_pack : launch_rowsmx_pack)(dtype, m, stream), "kernel launch");
       return;
     }
     RowsPackArgs a;
@@ -1344,7 +1350,7 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
     mine.rdispls[q] = rdispls[q];
   }
   mine.flags = (scope.capturing() ? (uint32_t)kVarCapturing : 0u) | (rows_call ? (uint32_t)kVarRows : 0u) |
-               (fp4 ? (uint32_t)kVarRowsMx4 : mx ? (uint32_t)kVarRowsMx : 0u);
+               (fp4 ? (uint32_t)kVarRowsMx4 : b128 ? (uint32_t)kVarRowsFp8b : mx ? (uint32_t)kVarRowsMx : 0u);
   mine.pad = rows_call ? (uint32_t)rows_call->rowcount : 0u;  // (below 2^31: rows_check_local)
 
   PeerBuffers::Decision d = PeerBuffers::kFallback;
@@ -1429,7 +1435,8 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
     }
     int A = 0;
     const CollParams p = make_params(2, rsend, rrecv, M, seq, psend, precv, 0, 0, coll, 0, 0, &A);
-    hip_check((fp4 ? launch_rowsmx4 : launch_rowsmx)(dtype, A / geo_.waves, cfg_.threads, p, m, stream), "kernel launch");
+    hip_check((fp4 ? launch_rowsmx4 : b128 ? launch_rowsfp8b : launch_rowsmx)(dtype, A / geo_.waves, cfg_.threads, p, m, stream),
+              "kernel launch");
     last_algo_ = 2;
   } else if (d == PeerBuffers::kRead && rows_call) {
     const void* recv_of[kMaxRanks];

@@ -160,6 +160,15 @@ class Comm {
     const RowsCall rows{nrows, rowstride, rowcount, rowidx, kRowsMxfp4};
     return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
   }
+  // And with e4m3 elements and one f32 scale per 128 (mncclAllToAllvRowsFp8Block128: records of MXFP8's
+  // size, fp8block.h's rules): kernels.hip rowsfp8b_push on the read schedule; else rowsfp8b_pack into
+  // the padded ring's stage.
+  ncclResult_t all_to_all_v_rows_fp8b(const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                                      const size_t* sendcounts, const size_t* sdispls, void* recv, const size_t* recvcounts,
+                                      const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream) {
+    const RowsCall rows{nrows, rowstride, rowcount, rowidx, kRowsFp8Block128};
+    return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
+  }
 
   // The way back (mncclAllToAllvCombine, mini_nccl_ext.h; counts and displacements in rows): the dense
   // send blocks are what ncclAllToAllv would deliver into a packed recv, which is never built -- row t
@@ -299,8 +308,9 @@ class Comm {
                    uint64_t scalar = 0);
   // the one call path of ncclAllToAllv (rows == nullptr: counts and displacements in elements of
   // `send`) and mncclAllToAllvRows (in rows of the matrix `rows` describes at `send`)
-  // what a delivered row is: the row itself, or its MXFP8 / MXFP4 record (mxblock.h)
-  enum RowsFormat { kRowsPlain, kRowsMxfp8, kRowsMxfp4 };
+  // what a delivered row is: the row itself, or its MXFP8 / MXFP4 record (mxblock.h), or its e4m3
+  // record with an f32 scale per 128 (fp8block.h)
+  enum RowsFormat { kRowsPlain, kRowsMxfp8, kRowsMxfp4, kRowsFp8Block128 };
   struct RowsCall {
     size_t nrows, rowstride, rowcount;
     const int32_t* rowidx;

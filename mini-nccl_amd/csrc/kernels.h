@@ -5,6 +5,7 @@
 
 #include "combine.h"
 #include "combinemx.h"
+#include "fp8block.h"
 #include "mxblock.h"
 #include "p2p.h"
 #include "rowblock.h"
@@ -164,6 +165,10 @@ hipError_t launch_rowsmx_pack(int dtype, const MxArgs& v, hipStream_t stream);
 // of mx4_record_bytes(rowcount) bytes, p.coll kCollAllToAllVRowsMx4 and the same argument checks.
 hipError_t launch_rowsmx4(int dtype, int channels, int threads, const CollParams& p, const MxArgs& v, hipStream_t stream);
 hipError_t launch_rowsmx4_pack(int dtype, const MxArgs& v, hipStream_t stream);
+// mncclAllToAllvRowsFp8Block128 (kernels.hip rowsfp8b_push, rowsfp8b_pack): the MXFP8 launches with
+// fp8block.h's records (the same size), p.coll kCollAllToAllVRowsFp8b and the same argument checks.
+hipError_t launch_rowsfp8b(int dtype, int channels, int threads, const CollParams& p, const MxArgs& v, hipStream_t stream);
+hipError_t launch_rowsfp8b_pack(int dtype, const MxArgs& v, hipStream_t stream);
 // mncclAllToAllvCombine on the read schedule (kernels.hip combine_fold): CombineArgs (combine.h), a
 // second by-value kernel argument.  p: p.coll kCollAllToAllVCombine; the geometry for chunk_bytes = the
 // longest output matrix of any rank in bytes of packed rows, p.recv this rank's matrix, p.peer_send

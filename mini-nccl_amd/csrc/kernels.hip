@@ -40,6 +40,9 @@
 //                 per 32; a lane pair per block, the scale bytes through a per-wave LDS strip.
 //  rowsmx4_push / rowsmx4_pack   the same walk for MXFP4 records (mncclAllToAllvRowsMxfp4): e2m1 nibbles,
 //                 a lane per block -- four vector loads, a lane-local amax, one vector store.
+//  rowsfp8b_push / rowsfp8b_pack   the same walk for the "1 x 128" FP8 records (mncclAllToAllvRowsFp8Block128):
+//                 e4m3 elements, one f32 scale per 128; eight lanes per block, a three-step DPP amax,
+//                 two IEEE divisions per block, a rounded multiply per element, scale dwords in the strip.
 //  combine_fold / combine_local   the way back of that layer (mncclAllToAllvCombine): the token owner
 //                 pulls the top-k rows of each of its tokens out of the peers' send, folds them by gate
 //                 weight in float in slot order and stores one row; vhalf_fold's protocol, the geometry
@@ -2115,9 +2118,9 @@ __global__ void __launch_bounds__(256) rows_pack(RowsPackArgs a) {
 // indices arrive 64 per coalesced load a batch ahead, a lane picks its row's with ds_bpermute and
 // range-checks it once per pass.  The walk is shared with rowsmx_pack, the same gather and quantise as
 // a plain grid kernel into local memory: `open` names the destinations and their record ranges.
+// a lane's 16 elements widened (exact), and the unsigned maximum of their magnitudes' f32 bits
 template <bool F16>
-__device__ __forceinline__ v4u mx_quant16(const v4u& a, const v4u& b, uint32_t* scale) {
-  float f[16];
+__device__ __forceinline__ void mx_widen16(const v4u& a, const v4u& b, float (&f)[16]) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const uint32_t w = i < 4 ? a[i] : b[i - 4];
@@ -2129,15 +2132,29 @@ __device__ __forceinline__ v4u mx_quant16(const v4u& a, const v4u& b, uint32_t* 
       f[2 * i + 1] = __uint_as_float(w & 0xffff0000u);
     }
   }
+}
+__device__ __forceinline__ uint32_t mx_amax16(const float (&f)[16]) {
   uint32_t am = 0;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const uint32_t m = __float_as_uint(f[i]) & 0x7fffffffu;
     am = m > am ? m : am;
   }
-  // the other lane of the pair: quad_perm [1, 0, 3, 2]; every lane of the wave is active here
-  const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)am, 0xB1, 0xf, 0xf, true);
-  am = nb > am ? nb : am;
+  return am;
+}
+// max(am, am of the lane a DPP control names); every lane of the wave is active where this is called
+template <int CTRL>
+__device__ __forceinline__ uint32_t mx_dpp_max(uint32_t am) {
+  const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)am, CTRL, 0xf, 0xf, true);
+  return nb > am ? nb : am;
+}
+
+template <bool F16>
+__device__ __forceinline__ v4u mx_quant16(const v4u& a, const v4u& b, uint32_t* scale) {
+  float f[16];
+  mx_widen16<F16>(a, b, f);
+  // the other lane of the pair: quad_perm [1, 0, 3, 2]
+  const uint32_t am = mx_dpp_max<0xB1>(mx_amax16(f));
   const uint32_t s = mx_scale_byte(am >> 23);
   *scale = s;
   const int sh = 127 - (int)s;
@@ -2149,6 +2166,39 @@ __device__ __forceinline__ v4u mx_quant16(const v4u& a, const v4u& b, uint32_t* 
     for (int e = 0; e < 4; ++e) y[e] = fp8_sat<e4m3_t>(__builtin_ldexpf(f[4 * d + e], sh));
     const uint32_t w = Fp8<e4m3_t>::enc2<true>(y[2], y[3], Fp8<e4m3_t>::enc2<false>(y[0], y[1], 0u));
     r[d] = s == 255u ? 0x7f7f7f7fu : w;
+  }
+  return r;
+}
+
+// mncclAllToAllvRowsFp8Block128 (rowsfp8b_push, rowsfp8b_pack): MXFP8's walk and lane split -- 16
+// elements and one 16-byte output vector per lane, records of the same P bytes -- with the "1 x 128"
+// format's quantiser (fp8block.h): one IEEE single scale per 128 elements, so a block is EIGHT lanes.
+// mx_lanes gives 8 / 16 / 32 / 64 lanes per row and a partial last pass ends on a multiple of 128
+// elements, so every group of eight lanes is aligned and wholly live or wholly idle (idle lanes hold
+// zeros and store nowhere).  Each lane takes the maximum of its 16 magnitudes' f32 bits; three DPP
+// moves -- quad_perm [1, 0, 3, 2], quad_perm [2, 3, 0, 1], row_half_mirror -- leave the block's A in
+// all eight lanes, no LDS, no branch.  Every lane then computes inv = 448 / a and scale = a / 448
+// itself, a = max(A, 1e-4f), with the compiler's correctly rounded f32 division (no v_rcp_f32 alone,
+// no fast-math: the rule's bits are fixed), and each element takes one v_mul_f32, fp8_sat's clamp and
+// v_cvt_pk_fp8_f32.  A block with a NaN or an infinity becomes 0x7f bytes and the NaN scale word by
+// selects.  The first lane of a group writes the scale DWORD into the strip (mx_walk).
+template <bool F16>
+__device__ __forceinline__ v4u fp8b_quant16(const v4u& a, const v4u& b, uint32_t* scale) {
+  float f[16];
+  mx_widen16<F16>(a, b, f);
+  const uint32_t am = mx_dpp_max<0x141>(mx_dpp_max<0x4E>(mx_dpp_max<0xB1>(mx_amax16(f))));
+  const bool bad = am >= 0x7f800000u;
+  const float av = __uint_as_float(fp8b_clamped_amax(am));
+  const float inv = kFp8bMax / av, sc = av / kFp8bMax;
+  *scale = bad ? kFp8bNanScale : __float_as_uint(sc);
+  v4u r;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    float y[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) y[e] = fp8_sat<e4m3_t>(f[4 * d + e] * inv);
+    const uint32_t w = Fp8<e4m3_t>::enc2<true>(y[2], y[3], Fp8<e4m3_t>::enc2<false>(y[0], y[1], 0u));
+    r[d] = bad ? 0x7f7f7f7fu : w;
   }
   return r;
 }
@@ -2207,20 +2257,29 @@ __device__ __forceinline__ v4u mx4_quant32(const v4u (&x)[4], uint32_t* scale) {
 }
 
 // What the walk needs to know of a format: a lane's elements per pass (64 source bytes at most), the
-// element bytes of a record, the lane split, and the quantiser of a lane's elements into one vector
+// elements and the bytes of one scale (a byte, or a dword-aligned dword; a record's scale part is
+// rowcount / 32 bytes in every format), the element bytes of a record, the lane split, and the quantiser
+// of a lane's elements into one vector
 struct MxFp8 {
-  static constexpr uint32_t kLaneElems = 16;
+  static constexpr uint32_t kLaneElems = 16, kScaleElems = kMxBlock, kScaleBytes = 1;
   static __device__ __forceinline__ uint32_t elem_bytes(uint32_t rc) { return rc; }
   static __device__ __forceinline__ MxLanes lanes(uint32_t rc) { return mx_lanes(rc); }
   template <bool F16>
   static __device__ __forceinline__ v4u quant(const v4u (&x)[2], uint32_t* s) { return mx_quant16<F16>(x[0], x[1], s); }
 };
 struct MxFp4 {
-  static constexpr uint32_t kLaneElems = 32;
+  static constexpr uint32_t kLaneElems = 32, kScaleElems = kMxBlock, kScaleBytes = 1;
   static __device__ __forceinline__ uint32_t elem_bytes(uint32_t rc) { return rc / 2; }
   static __device__ __forceinline__ MxLanes lanes(uint32_t rc) { return mx4_lanes(rc); }
   template <bool F16>
   static __device__ __forceinline__ v4u quant(const v4u (&x)[4], uint32_t* s) { return mx4_quant32<F16>(x, s); }
+};
+struct Fp8Block128 {
+  static constexpr uint32_t kLaneElems = 16, kScaleElems = kFp8bBlock, kScaleBytes = kFp8bScaleBytes;
+  static __device__ __forceinline__ uint32_t elem_bytes(uint32_t rc) { return rc; }
+  static __device__ __forceinline__ MxLanes lanes(uint32_t rc) { return mx_lanes(rc); }
+  template <bool F16>
+  static __device__ __forceinline__ v4u quant(const v4u (&x)[2], uint32_t* s) { return fp8b_quant16<F16>(x[0], x[1], s); }
 };
 
 // an offset beyond every pass's descriptor (a pass's records hold one output vector per lane: under
@@ -2233,7 +2292,7 @@ struct MxPass {
   rsrc_t dst;        // the pass's records, from the first one's first byte
   const char* from;  // this lane's 32 (64) source bytes
   uint32_t off;      // where this lane's 16 element bytes go in dst (kMxNowhere: an idle lane)
-  uint32_t sc;       // where this lane's scale byte goes in the strip (~0u: not this lane's to write)
+  uint32_t sc;       // the byte of the strip where this lane's scale goes (~0u: not this lane's to write)
   uint32_t nrec;     // records of the pass
   bool ld;           // the lane has a row, and its index is in range
   bool last;         // the records' last pass: the strip leaves after it
@@ -2245,7 +2304,8 @@ template <typename Fmt, bool F16, typename Open>
 __device__ __forceinline__ void mx_walk(const MxArgs& v, const char* send, int K, const Open& open, uint32_t* strip,
                                         int lane) {
   constexpr uint32_t kLane = Fmt::kLaneElems, kPass = 64u * kLane, kVecs = kLane / 8u;  // (a vector: 8 source elements)
-  constexpr uint32_t kPerBlock = kMxBlock / kLane;                                      // lanes per scale byte
+  constexpr uint32_t kPerBlock = Fmt::kScaleElems / kLane, kScale = Fmt::kScaleBytes;    // lanes per scale; its bytes
+  static_assert(kMxBlock * kScale == Fmt::kScaleElems, "a record's scale part is rowcount / 32 bytes");
   const uint32_t rc = v.rowcount, sb = rc / kMxBlock, eb = Fmt::elem_bytes(rc), P = eb + sb;
   const MxLanes g = Fmt::lanes(rc);
   const uint32_t lr = (uint32_t)lane / g.lanes, lc = (uint32_t)lane % g.lanes;
@@ -2271,7 +2331,7 @@ __device__ __forceinline__ void mx_walk(const MxArgs& v, const char* send, int K
         t.from = send + (u64)(uint32_t)idx * v.stride_bytes + (u64)e * 2;
         t.dst = make_rsrc(dbase + j * P, t.nrec * P);
         t.off = live ? lr * P + e / kLane * 16u : kMxNowhere;
-        t.sc = live && lc % kPerBlock == 0 ? i * (kPass / kMxBlock) + lr * sb + lc / kPerBlock : ~0u;
+        t.sc = live && lc % kPerBlock == 0 ? i * (kPass / kMxBlock) + lr * sb + lc / kPerBlock * kScale : ~0u;
         t.last = ++i == g.passes;
         return true;
       }
@@ -2306,9 +2366,13 @@ __device__ __forceinline__ void mx_walk(const MxArgs& v, const char* send, int K
     uint32_t s;
     const v4u y = Fmt::template quant<F16>(x, &s);
     st_slot16(t.dst, t.off, y);
-    if (t.sc != ~0u) reinterpret_cast<uint8_t*>(strip)[t.sc] = (uint8_t)s;
+    if constexpr (kScale == 1) {
+      if (t.sc != ~0u) reinterpret_cast<uint8_t*>(strip)[t.sc] = (uint8_t)s;
+    } else {
+      if (t.sc != ~0u) strip[t.sc >> 2] = s;  // (sb and every term of t.sc are multiples of 4)
+    }
     if (!t.last) return;
-    // the strip: the scale bytes of the pass's records, record after record, sb bytes each
+    // the strip: the scale parts of the pass's records, record after record, sb bytes each
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
     const uint32_t nv = g.rows == 1 ? sb >> 4 : 0u, dw = sb >> 2, at = nv * 4 + (uint32_t)lane;
@@ -2360,6 +2424,10 @@ template <bool F16>
 __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) rowsmx4_push(CollParams p, MxArgs v) {
   mx_push<MxFp4, F16>(p, v);
 }
+template <bool F16>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) rowsfp8b_push(CollParams p, MxArgs v) {
+  mx_push<Fp8Block128, F16>(p, v);
+}
 
 // The same as a plain grid kernel into local memory: the whole call at one rank, and the pack of the
 // padded ring (block q into the stage at q * Mpad, the own block into recv).  blockIdx.y is the
@@ -2386,6 +2454,10 @@ __global__ void __launch_bounds__(256) rowsmx_pack(MxArgs v) {
 template <bool F16>
 __global__ void __launch_bounds__(256) rowsmx4_pack(MxArgs v) {
   mx_pack<MxFp4, F16>(v);
+}
+template <bool F16>
+__global__ void __launch_bounds__(256) rowsfp8b_pack(MxArgs v) {
+  mx_pack<Fp8Block128, F16>(v);
 }
 
 // ---------------------------------------------------------------- the combine
@@ -3793,7 +3865,7 @@ hipError_t launch_rows_pack(int dtype, RowsPackArgs a, hipStream_t st) {
   });
 }
 
-// what the MXFP8 and MXFP4 kernels assume of their argument, checked before anything is launched: every access
+// what the MXFP8, MXFP4 and FP8-block-128 kernels assume of their argument, checked before anything is launched: every access
 // they form is a dword-aligned 16-byte vector inside a row, a record or the wave's strip
 static bool mx_args_ok(int dtype, const MxArgs& v, const char* src, int n) {
   if ((dtype != kBF16 && dtype != kF16) || n < 1 || n > kMaxRanks || !v.rowidx || !src) return false;
@@ -3804,42 +3876,53 @@ static bool mx_args_ok(int dtype, const MxArgs& v, const char* src, int n) {
   return true;
 }
 
-// fp4: the MXFP4 kernels and their record (launch_rowsmx4, launch_rowsmx4_pack)
-static hipError_t launch_mx_push(bool fp4, int dtype, int C, int nt, const CollParams& p, const MxArgs& v, hipStream_t st) {
+// the record formats of the walk's kernels: each its collective id, record size, lane split and kernel pair
+enum MxFormat { kFmtMxfp8, kFmtMxfp4, kFmtFp8Block128 };
+
+static hipError_t launch_mx_push(MxFormat fmt, int dtype, int C, int nt, const CollParams& p, const MxArgs& v, hipStream_t st) {
+  const int coll = fmt == kFmtMxfp4 ? kCollAllToAllVRowsMx4 : fmt == kFmtFp8Block128 ? kCollAllToAllVRowsFp8b : kCollAllToAllVRowsMx;
   // (a rank whose counts are all zero passes a stand-in matrix and list, Comm::var_exchange: never read, but not NULL)
-  if (p.coll != (fp4 ? kCollAllToAllVRowsMx4 : kCollAllToAllVRowsMx) || p.n < 2 || !mx_args_ok(dtype, v, p.send, p.n))
-    return hipErrorInvalidValue;
-  const u64 P = fp4 ? mx4_record_bytes(v.rowcount) : mx_record_bytes(v.rowcount);
+  if (p.coll != coll || p.n < 2 || !mx_args_ok(dtype, v, p.send, p.n)) return hipErrorInvalidValue;
+  const u64 P = fmt == kFmtMxfp4 ? mx4_record_bytes(v.rowcount) : fmt == kFmtFp8Block128 ? fp8b_record_bytes(v.rowcount)
+                                                                                         : mx_record_bytes(v.rowcount);
   for (int q = 0; q < p.n; ++q)
     if (v.count[q] * P > p.chunk_bytes) return hipErrorInvalidValue;
-  auto* const k = fp4 ? (dtype == kF16 ? rowsmx4_push<true> : rowsmx4_push<false>)
-                      : (dtype == kF16 ? rowsmx_push<true> : rowsmx_push<false>);
+  const bool h = dtype == kF16;
+  auto* const k = fmt == kFmtMxfp4         ? (h ? rowsmx4_push<true> : rowsmx4_push<false>)
+                  : fmt == kFmtFp8Block128 ? (h ? rowsfp8b_push<true> : rowsfp8b_push<false>)
+                                           : (h ? rowsmx_push<true> : rowsmx_push<false>);
   hipLaunchKernelGGL(k, dim3(C), dim3(nt), 0, st, p, v);
   return hipGetLastError();
 }
 hipError_t launch_rowsmx(int dtype, int C, int nt, const CollParams& p, const MxArgs& v, hipStream_t st) {
-  return launch_mx_push(false, dtype, C, nt, p, v, st);
+  return launch_mx_push(kFmtMxfp8, dtype, C, nt, p, v, st);
 }
 hipError_t launch_rowsmx4(int dtype, int C, int nt, const CollParams& p, const MxArgs& v, hipStream_t st) {
-  return launch_mx_push(true, dtype, C, nt, p, v, st);
+  return launch_mx_push(kFmtMxfp4, dtype, C, nt, p, v, st);
+}
+hipError_t launch_rowsfp8b(int dtype, int C, int nt, const CollParams& p, const MxArgs& v, hipStream_t st) {
+  return launch_mx_push(kFmtFp8Block128, dtype, C, nt, p, v, st);
 }
 
-static hipError_t launch_mx_pack(bool fp4, int dtype, const MxArgs& v, hipStream_t st) {
+static hipError_t launch_mx_pack(MxFormat fmt, int dtype, const MxArgs& v, hipStream_t st) {
   if (!mx_args_ok(dtype, v, v.src, v.n)) return hipErrorInvalidValue;
   u64 most = 0;
   for (int q = 0; q < v.n; ++q) most = v.count[q] > most ? v.count[q] : most;
   if (most == 0) return hipSuccess;
   // a wave per pass of the longest block, four to a workgroup; the rest by the waves' runs
-  const MxLanes g = fp4 ? mx4_lanes(v.rowcount) : mx_lanes(v.rowcount);
+  const MxLanes g = fmt == kFmtMxfp4 ? mx4_lanes(v.rowcount) : mx_lanes(v.rowcount);
   const u64 want = ((most + g.rows - 1) / g.rows + 3) / 4;
   const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);
-  auto* const k = fp4 ? (dtype == kF16 ? rowsmx4_pack<true> : rowsmx4_pack<false>)
-                      : (dtype == kF16 ? rowsmx_pack<true> : rowsmx_pack<false>);
+  const bool h = dtype == kF16;
+  auto* const k = fmt == kFmtMxfp4         ? (h ? rowsmx4_pack<true> : rowsmx4_pack<false>)
+                  : fmt == kFmtFp8Block128 ? (h ? rowsfp8b_pack<true> : rowsfp8b_pack<false>)
+                                           : (h ? rowsmx_pack<true> : rowsmx_pack<false>);
   hipLaunchKernelGGL(k, dim3(blocks, (unsigned)v.n), dim3(256), 0, st, v);
   return hipGetLastError();
 }
-hipError_t launch_rowsmx_pack(int dtype, const MxArgs& v, hipStream_t st) { return launch_mx_pack(false, dtype, v, st); }
-hipError_t launch_rowsmx4_pack(int dtype, const MxArgs& v, hipStream_t st) { return launch_mx_pack(true, dtype, v, st); }
+hipError_t launch_rowsmx_pack(int dtype, const MxArgs& v, hipStream_t st) { return launch_mx_pack(kFmtMxfp8, dtype, v, st); }
+hipError_t launch_rowsmx4_pack(int dtype, const MxArgs& v, hipStream_t st) { return launch_mx_pack(kFmtMxfp4, dtype, v, st); }
+hipError_t launch_rowsfp8b_pack(int dtype, const MxArgs& v, hipStream_t st) { return launch_mx_pack(kFmtFp8Block128, dtype, v, st); }
 
 // the combine's datatypes: the ones with a float to fold in
 template <typename F>

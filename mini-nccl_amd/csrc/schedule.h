@@ -178,7 +178,10 @@ enum Coll : int {
   kCollAllToAllVRowsMx4 = 14,
   // mncclAllToAllvCombineMxfp8: kCollAllToAllVCombine whose send side holds MXFP8 records, decoded in
   // the fold (combinemx.h); the same fallback, with the records moved as bytes
-  kCollAllToAllVCombineMx = 15
+  kCollAllToAllVCombineMx = 15,
+  // mncclAllToAllvRowsFp8Block128: kCollAllToAllVRowsMx with e4m3 elements and one f32 scale per 128
+  // (fp8block.h); its record is as long as MXFP8's, so only this id and kVarRowsFp8b tell the calls apart
+  kCollAllToAllVRowsFp8b = 16
 };
 
 // r, root: gather and scatter only (their op count depends on the rank's place in the chain; the

@@ -1653,6 +1653,23 @@ int mnccl_sim_mx4_owners(uint64_t count, uint64_t max_count, uint64_t rowcount, 
   return mx_owners(count, max_count, mnccl::mx4_record_bytes(rowcount), slice_bytes, owners);
 }
 
+// The same for mncclAllToAllvRowsFp8Block128 (csrc/fp8block.h): e4m3 elements and one f32 scale per 128.
+// Its record is as long as MXFP8's, so mnccl_sim_mx_owners and mnccl_sim_mx_slice_records serve it as they are.
+int mnccl_sim_fp8b_check_local(int n, int esz, const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
+                               const size_t* sendcounts, const size_t* sdispls, const void* recv, const size_t* recvcounts,
+                               const size_t* rdispls, size_t rowcount) {
+  if (n < 1 || n > mnccl::kVarMaxRanks || esz < 1) return -2;
+  return mnccl::mx_check_local(n, esz, send, nrows, rowstride, rowidx, sendcounts, sdispls, recv, recvcounts, rdispls,
+                               rowcount, mnccl::fp8b_record_bytes(rowcount));
+}
+uint64_t mnccl_sim_fp8b_record_bytes(uint64_t rowcount) { return mnccl::fp8b_record_bytes(rowcount); }
+int mnccl_sim_fp8b_quantise(const uint16_t* rows, int f16, uint32_t rowcount, uint64_t nrows, uint8_t* out) {
+  if (rowcount % mnccl::kFp8bBlock) return -2;
+  for (uint64_t t = 0; t < nrows; ++t)
+    mnccl::fp8b_quantise_row(rows + t * rowcount, f16 != 0, rowcount, out + t * mnccl::fp8b_record_bytes(rowcount));
+  return 0;
+}
+
 // csrc/combine.h, the host-side rules of mncclAllToAllvCombine, for the CPU suite: one rank's local
 // checks (a CombineLocal verdict; the buffers are only compared, never dereferenced), and the kernels'
 // argument block (out: n lo[], n cnt[], n src_off[], then vec) with the owner of each of `nj`

@@ -41,7 +41,10 @@ enum : uint32_t {
   // records of `pad` elements
   kVarRowsMx = 16u,
   // the row of an mncclAllToAllvRowsMxfp4 call, set beside kVarRows: MXFP4 records of `pad` elements
-  kVarRowsMx4 = 32u
+  kVarRowsMx4 = 32u,
+  // the row of an mncclAllToAllvRowsFp8Block128 call (fp8block.h), set beside kVarRows: records of `pad`
+  // e4m3 elements with an f32 scale per 128
+  kVarRowsFp8b = 64u
 };
 
 // The local checks' verdicts, in the order they are made

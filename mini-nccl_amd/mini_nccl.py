@@ -103,6 +103,8 @@ SIGNATURES = {
                                      ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllToAllvRowsMxfp4": (_I, [_VP, _SZ, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, ctypes.POINTER(_SZ),
                                      ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
+    "mncclAllToAllvRowsFp8Block128": (_I, [_VP, _SZ, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, ctypes.POINTER(_SZ),
+                                           ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllToAllvCombine": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _SZ, _VP, _VP, _I,
                                    ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllToAllvCombineMxfp8": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _SZ, _VP, _VP, _I,
@@ -331,6 +333,15 @@ class Comm:
         arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
         return load().mncclAllToAllvRowsMxfp4(send_ptr, nrows, rowstride, rowidx_ptr, arrays[0], arrays[1], recv_ptr,
                                               arrays[2], arrays[3], rowcount, dtype, self.handle, stream)
+
+    def all_to_all_v_rows_fp8_block128(self, send_ptr, nrows, rowstride, rowidx_ptr, sendcounts, sdispls, recv_ptr, recvcounts,
+                                       rdispls, rowcount, dtype=ncclBfloat16, stream=0):
+        """mncclAllToAllvRowsFp8Block128: all_to_all_v_rows_mxfp8 with records of the same rowcount + rowcount // 32
+        bytes in the "1 x 128" format: rowcount e4m3 bytes, then rowcount // 128 float32 scales (amax / 448,
+        amax clamped at 1e-4), one per 128 elements.  Returns the ncclResult_t."""
+        arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
+        return load().mncclAllToAllvRowsFp8Block128(send_ptr, nrows, rowstride, rowidx_ptr, arrays[0], arrays[1], recv_ptr,
+                                                    arrays[2], arrays[3], rowcount, dtype, self.handle, stream)
 
     def all_to_all_v_combine(self, send_ptr, sendcounts, sdispls, recv_ptr, nrows, rowstride, slotidx_ptr, weights_ptr, topk,
                              recvcounts, rdispls, rowcount, dtype=ncclFloat, stream=0):

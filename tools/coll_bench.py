@@ -71,6 +71,9 @@ persistent form (mncclAlgoRead), fp32 Sum, stream-ordered (MINI_NCCL_BLOCKING=0)
     alltoallv_rows_mxfp4 / alltoallv_rows_mxfp4_composed   the same pair for mncclAllToAllvRowsMxfp4.  Ratios
                     alltoallv_rows_mxfp4_over_composed and, when those kinds are timed too,
                     alltoallv_rows_mxfp4_over_alltoallv_rows_mxfp8 and alltoallv_rows_mxfp4_over_alltoallv_rows
+    alltoallv_rows_fp8_block128 / alltoallv_rows_fp8_block128_composed   the same pair for mncclAllToAllvRowsFp8Block128.
+                    Ratios alltoallv_rows_fp8_block128_over_composed and, when those kinds are timed too,
+                    alltoallv_rows_fp8_block128_over_alltoallv_rows_mxfp8 and alltoallv_rows_fp8_block128_over_alltoallv_rows
     alltoallv_rows_composed   what a caller runs without it, on the same matrix and indices: the gather
                     as a kernel of its own (rows_pack, through a one-rank communicator) into a packed
                     buffer, then ncclAllToAllv.  Ratio alltoallv_rows_over_composed beside both spreads
@@ -118,13 +121,16 @@ KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_pr
          "all_gather_v", "reduce_scatter_v", "all_gather_v_skew", "reduce_scatter_v_skew", "all_gather_padded",
          "reduce_scatter_padded", "alltoallv_rows", "alltoallv_rows_composed", "alltoallv_combine",
          "alltoallv_combine_composed", "alltoallv_rows_mxfp8", "alltoallv_rows_mxfp8_composed", "alltoallv_rows_mxfp4",
-         "alltoallv_rows_mxfp4_composed", "alltoallv_combine_mxfp8", "alltoallv_combine_mxfp8_composed")
+         "alltoallv_rows_mxfp4_composed", "alltoallv_combine_mxfp8", "alltoallv_combine_mxfp8_composed",
+         "alltoallv_rows_fp8_block128", "alltoallv_rows_fp8_block128_composed")
 # mncclAllToAllvRows beside what a caller composes without it, on the same matrix and indices
 ROWS_KINDS = ("alltoallv_rows", "alltoallv_rows_composed")
 # mncclAllToAllvRowsMxfp8 beside the quantise kernel followed by ncclAllToAllv of bytes, same matrix and indices
 MX_KINDS = ("alltoallv_rows_mxfp8", "alltoallv_rows_mxfp8_composed")
 # mncclAllToAllvRowsMxfp4 beside its composed form, built the same way
 MX4_KINDS = ("alltoallv_rows_mxfp4", "alltoallv_rows_mxfp4_composed")
+# mncclAllToAllvRowsFp8Block128 beside its composed form, built the same way
+FP8B_KINDS = ("alltoallv_rows_fp8_block128", "alltoallv_rows_fp8_block128_composed")
 # mncclAllToAllvCombine beside ncclAllToAllv plus a fold of the caller's own, on the same data
 COMBINE_KINDS = ("alltoallv_combine", "alltoallv_combine_composed")
 # mncclAllToAllvCombineMxfp8 beside a dequantise pass to bf16 followed by mncclAllToAllvCombine, on the same counts and slots
@@ -135,7 +141,7 @@ VHALF_SKEW = ("all_gather_v_skew", "reduce_scatter_v_skew") + PADDED_KINDS
 # the kinds --dtype bf16 can time (the others' helpers are written for fp32 elements)
 # the kinds that run while big_b is a registered window, and the scratch form each is measured against
 WIN_KINDS = {"p2p_neighbor_win": "p2p_neighbor", "p2p_all_pairs_win": "p2p_all_pairs"}
-BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce") + ROWS_KINDS + COMBINE_KINDS + COMBINE_MX_KINDS + MX_KINDS + MX4_KINDS
+BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce") + ROWS_KINDS + COMBINE_KINDS + COMBINE_MX_KINDS + MX_KINDS + MX4_KINDS + FP8B_KINDS
 
 
 def skew_matrix(n, chunk, seed):
@@ -157,14 +163,15 @@ def v_call(M, comm, send, recv, C, rank, stream):
 
 
 def rows_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stream):
-    """(fused, composed, buffers, solo, mx, mx_composed, mx4, mx4_composed): bf16 rows of `row_elems` elements, block_bytes // row bytes rows
+    """(fused, composed, buffers, solo, mx, mx_composed, mx4, mx4_composed, fp8b, fp8b_composed): bf16 rows of `row_elems` elements, block_bytes // row bytes rows
     per block (balanced) or skew_matrix's share of that (skew_seed >= 0); a top-2 router's list over
     half as many tokens as rows are sent, seeded per rank.  Fused: mncclAllToAllvRows.  Composed: the
     same gather as a kernel of its own into a packed buffer (mncclAllToAllvRows on a one-rank
     communicator runs rows_pack alone), then ncclAllToAllv on the packed rows.  mx / mx_composed: the
     same pair for mncclAllToAllvRowsMxfp8 -- rowsmx_pack into the packed buffer, then ncclAllToAllv of the
     records' bytes -- in the same buffers (a record is shorter than its row).  mx4 / mx4_composed: that
-    pair again for mncclAllToAllvRowsMxfp4 (rowsmx4_pack, records of row_elems // 2 + row_elems // 32 bytes)."""
+    pair again for mncclAllToAllvRowsMxfp4 (rowsmx4_pack, records of row_elems // 2 + row_elems // 32 bytes);
+    fp8b / fp8b_composed: and for mncclAllToAllvRowsFp8Block128 (rowsfp8b_pack, records of MXFP8's size)."""
     import numpy as np
     rb = 2 * row_elems
     per = max(1, block_bytes // rb)
@@ -198,7 +205,8 @@ def rows_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stre
             return r or comm.all_to_all_v(packed.ptr, ep(sc), ep(starts(sc)), recv.ptr, ep(rc), ep(starts(rc)), M.ncclFloat8e4m3, stream)
         return mx, mx_composed
     return (fused, composed, [x, idx, packed, recv], solo) + mx_pair("all_to_all_v_rows_mxfp8", row_elems + row_elems // 32) + \
-        mx_pair("all_to_all_v_rows_mxfp4", row_elems // 2 + row_elems // 32)
+        mx_pair("all_to_all_v_rows_mxfp4", row_elems // 2 + row_elems // 32) + \
+        mx_pair("all_to_all_v_rows_fp8_block128", row_elems + row_elems // 32)
 
 
 def combine_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stream):
@@ -356,9 +364,9 @@ def rank_main(a):
         calls["reduce_scatter_padded"] = lambda: comm.reduce_scatter(pads[0].ptr, pads[1].ptr, max(skew), M.ncclFloat,
                                                                      M.ncclSum, st.handle)
     solo = None
-    if any(k in ROWS_KINDS + MX_KINDS + MX4_KINDS for k in kinds):
+    if any(k in ROWS_KINDS + MX_KINDS + MX4_KINDS + FP8B_KINDS for k in kinds):
         (calls["alltoallv_rows"], calls["alltoallv_rows_composed"], more, solo, calls[MX_KINDS[0]], calls[MX_KINDS[1]],
-         calls[MX4_KINDS[0]], calls[MX4_KINDS[1]]) = rows_calls(
+         calls[MX4_KINDS[0]], calls[MX4_KINDS[1]], calls[FP8B_KINDS[0]], calls[FP8B_KINDS[1]]) = rows_calls(
             M, hip_rt, comm, n, a.rank, a.bytes // n, a.row_elems, a.skew_seed if a.rows_skew else -1, st.handle)
         pads += more
     solo2 = None
@@ -496,7 +504,7 @@ def main():
         "rounds_ms": {k: [round(x, 4) for x in v] for k, v in rounds.items()},
         "hbm_bytes": {k: (2 * n if k in ("all_reduce", "all_reduce_premul", "all_to_all", "all_to_all_v") else n + 1) * chunk_bytes
                       for k in kinds if k not in ("all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
-                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") + VHALF_SKEW + ROWS_KINDS + COMBINE_KINDS + COMBINE_MX_KINDS + MX_KINDS + MX4_KINDS
+                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") + VHALF_SKEW + ROWS_KINDS + COMBINE_KINDS + COMBINE_MX_KINDS + MX_KINDS + MX4_KINDS + FP8B_KINDS
                       and k not in WIN_KINDS},
         "ratio": dict([(f"{k}_over_all_reduce", round(med[k] / med["all_reduce"], 4)) for k in kinds if k != "all_reduce"] +
                       [(f"{k}_over_{y}", round(med[k] / med[y], 4))
@@ -571,6 +579,15 @@ def main():
             if other in med:
                 res["ratio"]["alltoallv_rows_mxfp4_over_" + other] = round(med[MX4_KINDS[0]] / med[other], 4)
         for k in MX4_KINDS:
+            res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
+    if all(k in med for k in FP8B_KINDS):
+        res["rows_fp8_block128"] = {"row_elems": a.row_elems, "record_bytes": a.row_elems + a.row_elems // 32,
+                                    "matrix": "skew" if a.rows_skew else "balanced"}
+        res["ratio"]["alltoallv_rows_fp8_block128_over_composed"] = round(med[FP8B_KINDS[0]] / med[FP8B_KINDS[1]], 4)
+        for other in ("alltoallv_rows_mxfp8", "alltoallv_rows"):
+            if other in med:
+                res["ratio"]["alltoallv_rows_fp8_block128_over_" + other] = round(med[FP8B_KINDS[0]] / med[other], 4)
+        for k in FP8B_KINDS:
             res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
     if all(k in med for k in COMBINE_KINDS):
         res["combine"] = {"row_elems": a.row_elems, "row_bytes": 2 * a.row_elems, "topk": 2, "matrix": "skew" if a.rows_skew else "balanced"}
