@@ -47,6 +47,7 @@
  *   mncclAllToAllvCombine  the way back: the token owner pulls the top-k rows of each token out of the
  *                        experts' send buffers and folds them by gate weight (no packed recv, no atomics).
  *   mncclAllToAllvCombineMxfp8  the same out of MXFP8 records, decoded in the fold: half of bf16's bytes back.
+ *   mncclAllToAllvCombineFp8Block128  the same out of the "1 x 128" records mncclAllToAllvRowsFp8Block128 delivers.
  *
  * and the all-reduce's halves with per-rank counts, which neither NCCL nor RCCL has (callers there
  * compose them from broadcasts / reduces inside one group, which this library does not take), under
@@ -113,7 +114,8 @@ extern "C" {
    mncclAllGatherv and mncclReduceScatterv were added the same way (detected by symbol;
    mncclCommInfo_t did not grow); still 600: mncclAllToAllvRows was added the same way; still 600:
    mncclAllToAllvRowsMxfp8 was added the same way; still 600: mncclAllToAllvRowsMxfp4 was added the
-   same way; still 600: mncclAllToAllvRowsFp8Block128 was added the same way */
+   same way; still 600: mncclAllToAllvRowsFp8Block128 was added the same way; still 600:
+   mncclAllToAllvCombineFp8Block128 was added the same way */
 #define MNCCL_VERSION 600
 
 /* schedules; all produce bit-identical results (same fold order per element) */
@@ -587,7 +589,8 @@ ncclResult_t mncclAllToAllvRowsMxfp4(const void* sendbuff, size_t nrows, size_t 
  * ring's stage and the rest is the fallback by bytes (mncclAlgoRing, refused under capture); one rank:
  * the grid kernel alone.
  * Not built: UE8M0-rounded scales, e5m2, group sizes other than 128, a separate or transposed scales
- * buffer, f32 input, a combine out of these records, registered windows. */
+ * buffer, f32 input, registered windows.  The way back out of these records:
+ * mncclAllToAllvCombineFp8Block128. */
 ncclResult_t mncclAllToAllvRowsFp8Block128(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
                                            const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                                            const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
@@ -686,6 +689,46 @@ ncclResult_t mncclAllToAllvCombineMxfp8(const void* sendbuff, const size_t sendc
                                         void* recvbuff, size_t nrows, size_t rowstride, const int32_t* slotidx,
                                         const float* weights, int topk, const size_t recvcounts[], const size_t rdispls[],
                                         size_t rowcount, ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
+
+/* The way back out of "1 x 128" FP8 records: mncclAllToAllvCombineMxfp8 whose send side holds what
+ * mncclAllToAllvRowsFp8Block128 delivers, so an expert whose block-scale FP8 epilogue writes these
+ * records returns 1.03 bytes per element over the links instead of bf16's 2, with no dequantise pass in
+ * front.  Detected by symbol (MNCCL_VERSION stays 600).
+ *
+ * mncclAllToAllvCombineMxfp8's arguments and meaning with two differences: the record and the decode.
+ * Row i of sendbuff is one record of P = rowcount + rowcount / 32 bytes -- rowcount e4m3fn bytes, then
+ * rowcount / 128 little-endian IEEE singles, one per 128 consecutive elements -- dense, no stride;
+ * sendcounts, sdispls, recvcounts, rdispls and slotidx count records.  `datatype` (ncclFloat,
+ * ncclFloat16 or ncclBfloat16) and `rowstride` are the recvbuff matrix's.
+ *
+ * Result, bit for bit on every schedule and slice size.  With c = byte e of record j and S = the single
+ * at its byte rowcount + 4 * (e / 128), used as its bit pattern says: the decoded element d is a NaN when
+ * (c & 0x7F) == 0x7F, else d = round_f32(e4m3(c) * S) -- ONE IEEE single multiply, denormals honoured
+ * on input and output, nothing special-cased.  So a NaN S gives NaN, an infinite S +-inf (NaN against a
+ * zero code), a negative S flips the sign, a zero or subnormal S acts as IEEE says; every scale the
+ * dispatch writes, its NaN word 0x7FC00000 and its floor 1e-4f / 448.0f included, falls out of the rule.
+ * Then mncclAllToAllvCombine's fold: acc = +0.0f; for k in slot order acc = acc + round_f32(w * d), the
+ * two multiplies and the add each rounded, never fused or reassociated (w * (v * S), not (w * S) * v);
+ * one rounding to the datatype, to nearest even.  A slot in no non-empty block contributes nothing and
+ * causes no access.  Where the rule gives NaN the output is a NaN of the datatype, no payload promised.
+ *
+ * Checks: mncclAllToAllvCombineMxfp8's, in its order and with its verdicts -- rowcount % 128 != 0 or
+ * outside [128, 16384], or sendbuff, recvbuff or rowstride in bytes not dword-aligned:
+ * ncclInvalidArgument, in front of mncclAllToAllvCombine's local ones (the send side's overflow and
+ * overlap checks count P bytes per row); any datatype but the three: ncclInternalError.  Ranks that mix
+ * this call with mncclAllToAllvCombine or mncclAllToAllvCombineMxfp8 (whose record is as long), or
+ * differ in datatype, rowcount or the schedule choice: ncclInvalidUsage on every rank, nothing
+ * launched, the communicator stays usable.
+ *
+ * Schedules as mncclAllToAllvCombineMxfp8: the persistent pull-and-fold kernel on the read schedule
+ * (last_algo: mncclAlgoRead; a captured call re-reads slotidx and weights at replay), else the padded
+ * ring carries the records as bytes into the stage and the local kernel decodes and folds out of it
+ * (last_algo: mncclAlgoRing; refused under capture); one rank, or every count zero: the local kernel.
+ * Not built: group sizes other than 128, UE8M0 scales, a separate scales buffer, registered windows. */
+ncclResult_t mncclAllToAllvCombineFp8Block128(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[],
+                                              void* recvbuff, size_t nrows, size_t rowstride, const int32_t* slotidx,
+                                              const float* weights, int topk, const size_t recvcounts[], const size_t rdispls[],
+                                              size_t rowcount, ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
 
 /* The all-reduce's halves with per-rank counts.  Neither NCCL nor RCCL has them, so they carry the
  * library's prefix and MPI's argument order (MPI_Allgatherv / MPI_Reduce_scatter with displacements).

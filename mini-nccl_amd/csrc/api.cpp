@@ -472,7 +472,7 @@ ncclResult_t mncclAllToAllvCombine(const void* sendbuff, const size_t sendcounts
 }
 
 // The way back out of MXFP8 records (mini_nccl_ext.h): mncclAllToAllvCombine's checks in its order;
-// the datatype is the OUTPUT matrix's (Comm::combine with mx, combinemx.h).
+// the datatype is the OUTPUT matrix's (Comm::combine with kCombineMxfp8, combinemx.h).
 ncclResult_t mncclAllToAllvCombineMxfp8(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[],
                                         void* recvbuff, size_t nrows, size_t rowstride, const int32_t* slotidx,
                                         const float* weights, int topk, const size_t recvcounts[], const size_t rdispls[],
@@ -486,9 +486,35 @@ ncclResult_t mncclAllToAllvCombineMxfp8(const void* sendbuff, const size_t sendc
   }
   try {
     return reinterpret_cast<Comm*>(comm)->combine(sendbuff, sendcounts, sdispls, recvbuff, nrows, rowstride, slotidx, weights,
-                                                  topk, recvcounts, rdispls, rowcount, (int)datatype, stream, true);
+                                                  topk, recvcounts, rdispls, rowcount, (int)datatype, stream,
+                                                  Comm::kCombineMxfp8);
   } catch (const std::exception& e) {
     fprintf(stderr, "[Mini-NCCL] AllToAllvCombineMxfp8 Internal Error: %s\n", e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
+// The way back out of "1 x 128" FP8 records (mini_nccl_ext.h): mncclAllToAllvCombine's checks in its order;
+// the datatype is the OUTPUT matrix's (Comm::combine with kCombineFp8Block128, combinefp8b.h).
+ncclResult_t mncclAllToAllvCombineFp8Block128(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[],
+                                              void* recvbuff, size_t nrows, size_t rowstride, const int32_t* slotidx,
+                                              const float* weights, int topk, const size_t recvcounts[], const size_t rdispls[],
+                                              size_t rowcount, ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
+  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
+  RoctxRange range("mini_ncclAllToAllvCombineFp8Block128");
+  if (datatype != ncclFloat && datatype != ncclFloat16 && datatype != ncclBfloat16) {
+    fprintf(stderr, "[Mini-NCCL] AllToAllvCombineFp8Block128 Internal Error: unsupported DataType\n");
+    return ncclInternalError;
+  }
+  try {
+    return reinterpret_cast<Comm*>(comm)->combine(sendbuff, sendcounts, sdispls, recvbuff, nrows, rowstride, slotidx, weights,
+                                                  topk, recvcounts, rdispls, rowcount, (int)datatype, stream,
+                                                  Comm::kCombineFp8Block128);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[Mini-NCCL] AllToAllvCombineFp8Block128 Internal Error: %s\n", e.what());
     return ncclInternalError;
   } catch (...) {
     return ncclSystemError;

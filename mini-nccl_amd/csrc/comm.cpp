@@ -1510,21 +1510,30 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
 // its rows through one more dense stage region and a strided copy.  Every count zero on every rank:
 // combine_local alone zero-fills (no protocol: every rank sees the same matrix); one rank: the same
 // kernel on the own block.  A rank with no output rows still serves its send; one with no send counts
-// still pulls.  mx (mncclAllToAllvCombineMxfp8): the same path with combinemx.h's rules -- a send row is a
-// record of mx_record_bytes(rowcount) bytes (sb below; rb stays the OUTPUT row's), the collective id is
-// kCollAllToAllVCombineMx, the kernels combinemx_fold / combinemx_local; the ring moves the records as bytes.
+// still pulls.  fmt kCombineMxfp8 (mncclAllToAllvCombineMxfp8) and kCombineFp8Block128
+// (mncclAllToAllvCombineFp8Block128): the same path with combinemx.h's or combinefp8b.h's rules -- a send row
+// is a record (sb below, the same for both; rb stays the OUTPUT row's), the collective id is
+// kCollAllToAllVCombineMx or kCollAllToAllVCombineFp8b, which alone tells the two apart in the rendezvous, the
+// kernels combinemx_* or combinefp8b_*; the ring moves the records as bytes.
 ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv, size_t nrows,
                            size_t rowstride, const int32_t* slotidx, const float* weights, int topk,
                            const size_t* recvcounts, const size_t* rdispls, size_t rowcount, int dtype,
-                           hipStream_t stream, bool mx) {
+                           hipStream_t stream, CombineFormat fmt) {
   if (sticky_ != ncclSuccess) return sticky_;
   if (check_status() != ncclSuccess) return sticky_;
-  const int n = nranks_, esz = dtype_size(dtype), coll = mx ? kCollAllToAllVCombineMx : kCollAllToAllVCombine;
-  const char* const name = mx ? "mncclAllToAllvCombineMxfp8" : "mncclAllToAllvCombine";
-  const int local = mx ? combinemx_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights,
-                                               topk, recvcounts, rdispls, rowcount)
-                       : combine_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights, topk,
-                                             recvcounts, rdispls, rowcount);
+  const bool b128 = fmt == kCombineFp8Block128, mx = fmt == kCombineMxfp8;
+  const int n = nranks_, esz = dtype_size(dtype),
+            coll = b128 ? kCollAllToAllVCombineFp8b : mx ? kCollAllToAllVCombineMx : kCollAllToAllVCombine;
+  const char* const name = b128 ? "mncclAllToAllvCombineFp8Block128" : mx ? "mncclAllToAllvCombineMxfp8" : "mncclAllToAllvCombine";
+  // the format's rules and kernels
+  const auto fill_args = b128 ? combinefp8b_fill_args : mx ? combinemx_fill_args : combine_fill_args;
+  const auto launch_fold = b128 ? launch_combinefp8b : mx ? launch_combinemx : launch_combine;
+  const auto launch_local = b128 ? launch_combinefp8b_local : mx ? launch_combinemx_local : launch_combine_local;
+  const int local = b128 || mx ? (b128 ? combinefp8b_check_local : combinemx_check_local)(
+                                     n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights, topk, recvcounts,
+                                     rdispls, rowcount)
+                               : combine_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights,
+                                                     topk, recvcounts, rdispls, rowcount);
   if (local != kCombineOk) {
     fprintf(stderr, "[Mini-NCCL] rank %d: %s: %s\n", rank_, name,
             local == kMxRowcount            ? "rowcount is no multiple of 128 in [128, 16384]"
@@ -1540,8 +1549,9 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
                                             : "the recv matrix overlaps a send block, slotidx or weights");
     return ncclInvalidArgument;
   }
-  // rb: an output row's bytes; sb: a send row's (mx: a record's)
-  const size_t rb = rowcount * (size_t)esz, sb = mx ? (size_t)mx_record_bytes(rowcount) : rb;
+  // rb: an output row's bytes; sb: a send row's (mx, b128: a record's)
+  const size_t rb = rowcount * (size_t)esz,
+               sb = b128 ? (size_t)fp8b_record_bytes(rowcount) : mx ? (size_t)mx_record_bytes(rowcount) : rb;
   auto how = [&](const void* p) {
     const void* k = p;
     bool l = false;
@@ -1580,12 +1590,9 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
       at[q] = disp[q];
     }
     CombineArgs v;
-    (mx ? combinemx_fill_args : combine_fill_args)(&v, n, esz, out_via ? stage_ + out_at : out, nrows,
-                                                   out_via ? rowcount : rowstride, kslot, kw, topk, recvcounts, rdispls, rowcount,
-                                                   send_of, at);
-    hip_check((mx ? launch_combinemx_local : launch_combine_local)(dtype, n, v, packed,
-                                                                   out_via ? stage_ + out_at : const_cast<void*>(out), stream),
-              "kernel launch");
+    fill_args(&v, n, esz, out_via ? stage_ + out_at : out, nrows, out_via ? rowcount : rowstride, kslot, kw, topk, recvcounts,
+              rdispls, rowcount, send_of, at);
+    hip_check(launch_local(dtype, n, v, packed, out_via ? stage_ + out_at : const_cast<void*>(out), stream), "kernel launch");
     if (out_via)
       hip_check(hipMemcpy2DAsync(recv, rowstride * (size_t)esz, stage_ + out_at, rb, rb, nrows, hipMemcpyDefault, stream),
                 "rows out");
@@ -1703,12 +1710,11 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
     }
     CombineArgs v;
     // (a rank without rows passes a stand-in list: never read)
-    (mx ? combinemx_fill_args : combine_fill_args)(&v, n, esz, rrecv, nrows, rowstride,
-                                                   nrows ? kslot : (const int32_t*)rsend, nrows ? kw : nullptr, topk, recvcounts,
-                                                   rdispls, rowcount, send_of, peer_sdispl);
+    fill_args(&v, n, esz, rrecv, nrows, rowstride, nrows ? kslot : (const int32_t*)rsend, nrows ? kw : nullptr, topk,
+              recvcounts, rdispls, rowcount, send_of, peer_sdispl);
     int A = 0;
     const CollParams p = make_params(2, rsend, rrecv, M, seq, psend, precv, 0, 0, coll, 0, 0, &A);
-    hip_check((mx ? launch_combinemx : launch_combine)(dtype, A / geo_.waves, cfg_.threads, p, v, stream), "kernel launch");
+    hip_check(launch_fold(dtype, A / geo_.waves, cfg_.threads, p, v, stream), "kernel launch");
     last_algo_ = 2;
   } else {
     const size_t Mpad = (Mb + 15) & ~(size_t)15;

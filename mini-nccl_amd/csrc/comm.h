@@ -177,12 +177,14 @@ class Comm {
   // of its own (comm.cpp combine) modelled on all_to_all_v's, with the rules of combine.h: kernels.hip
   // combine_fold on the read schedule; else ncclAllToAllv's padded ring into a packed stage and
   // combine_local out of it.
-  // mx (mncclAllToAllvCombineMxfp8, combinemx.h): the send rows are MXFP8 records of rowcount elements,
-  // counted in records; dtype and rowstride are the recv matrix's.  The same path with a record's bytes
-  // for the send row's, a collective id of its own, and combinemx_fold / combinemx_local.
+  // fmt: what a send row is.  kCombineMxfp8 (mncclAllToAllvCombineMxfp8, combinemx.h) and kCombineFp8Block128
+  // (mncclAllToAllvCombineFp8Block128, combinefp8b.h): records of rowcount elements, counted in records;
+  // dtype and rowstride are the recv matrix's.  The same path with a record's bytes for the send row's, a
+  // collective id per format, and combinemx_fold / combinemx_local or combinefp8b_fold / combinefp8b_local.
+  enum CombineFormat { kCombinePlain, kCombineMxfp8, kCombineFp8Block128 };
   ncclResult_t combine(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv, size_t nrows,
                        size_t rowstride, const int32_t* slotidx, const float* weights, int topk, const size_t* recvcounts,
-                       const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream, bool mx = false);
+                       const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream, CombineFormat fmt = kCombinePlain);
 
   // The halves with per-rank counts (mncclAllGatherv / mncclReduceScatterv, mini_nccl_ext.h; counts and
   // displacements in elements, host arrays of n entries read before the call returns, the same on

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "combine.h"
+#include "combinefp8b.h"
 #include "combinemx.h"
 #include "fp8block.h"
 #include "mxblock.h"
@@ -185,6 +186,12 @@ hipError_t launch_combine_local(int dtype, int n, const CombineArgs& v, const vo
 hipError_t launch_combinemx(int dtype, int channels, int threads, const CollParams& p, const CombineArgs& v,
                             hipStream_t stream);
 hipError_t launch_combinemx_local(int dtype, int n, const CombineArgs& v, const void* src, void* recv, hipStream_t stream);
+// mncclAllToAllvCombineFp8Block128 (kernels.hip combinefp8b_fold, combinefp8b_local): the same two with
+// fp8block.h's records (as long) on the send side -- v from combinefp8b_fill_args (combinefp8b.h), p.coll
+// kCollAllToAllVCombineFp8b -- and the same argument checks.
+hipError_t launch_combinefp8b(int dtype, int channels, int threads, const CollParams& p, const CombineArgs& v,
+                              hipStream_t stream);
+hipError_t launch_combinefp8b_local(int dtype, int n, const CombineArgs& v, const void* src, void* recv, hipStream_t stream);
 // mncclReduceScatterv / mncclAllGatherv on the read schedule (kernels.hip vhalf_fold / vhalf_push):
 // this rank's block of the array-side buffers, a second by-value kernel argument (CollParams stays
 // byte for byte what it was).  The arrays are the same on every rank, so `base` is the block's byte

@@ -50,6 +50,8 @@
 //                 local packed buffer (one rank, and behind the padded ring).
 //  combinemx_fold / combinemx_local   the same pair out of MXFP8 records (mncclAllToAllvCombineMxfp8): 16
 //                 e4m3 bytes and their scale byte per lane and source, decoded in registers before the product.
+//  combinefp8b_fold / combinefp8b_local   the same walks out of "1 x 128" FP8 records (mncclAllToAllvCombineFp8Block128):
+//                 the f32 scale of eight lanes as one dword load each, one rounded multiply by it per element.
 //  vhalf_fold / vhalf_push   the halves with per-rank counts (mncclReduceScatterv / mncclAllGatherv)
 //                 on the same protocol: scatter_fold and gather_push with a per-rank base and
 //                 length, the slices cut for the largest block.  Their fallback is the ring's
@@ -2763,19 +2765,52 @@ __global__ void __launch_bounds__(256) MNCCL_SCALAR_F32 combine_local(CombineArg
 // Narrow rows, combinemx_unit: rowcount / 16 lanes per row, 64 / lanes rows a pass; the lanes of a
 // pass read records of different peers through one descriptor per distinct (peer, 2 GiB window)
 // among them, elements and scale alike, as combine_unit.
-__device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_mac16(float (&acc)[16], v4u x, uint32_t s, float w) {
+//
+// mncclAllToAllvCombineFp8Block128 (combinefp8b_fold, combinefp8b_local) runs the same two walks over
+// the records mncclAllToAllvRowsFp8Block128 delivers (fp8block.h: as long, with rowcount / 128 IEEE
+// singles behind the codes).  What differs is the format trait the walks take: where a unit's scale
+// lies behind the codes, how it is loaded, and the decode inside the multiply-accumulate.
+struct CombineMxfp8 {
+  // the byte offset of unit u's scale behind the record's rowcount codes, and the access that loads it
+  static __device__ __forceinline__ uint32_t scale_at(uint32_t u) { return u >> 1; }
+  typedef Scal<1> ScaleLd;
+  static __device__ __forceinline__ MNCCL_SCALAR_F32 void mac16(float (&acc)[16], v4u x, uint32_t s, float w) {
 #pragma clang fp contract(off)
-  const int sh = (int)s - 127;
+    const int sh = (int)s - 127;
 #pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    const uint32_t c = s == 255u ? 0x7f7f7f7fu : x[d];
-    const v2f lo = Fp8<e4m3_t>::dec2<false>(c), hi = Fp8<e4m3_t>::dec2<true>(c);
-    acc[4 * d] = acc[4 * d] + w * __builtin_ldexpf(lo.x, sh);
-    acc[4 * d + 1] = acc[4 * d + 1] + w * __builtin_ldexpf(lo.y, sh);
-    acc[4 * d + 2] = acc[4 * d + 2] + w * __builtin_ldexpf(hi.x, sh);
-    acc[4 * d + 3] = acc[4 * d + 3] + w * __builtin_ldexpf(hi.y, sh);
+    for (int d = 0; d < 4; ++d) {
+      const uint32_t c = s == 255u ? 0x7f7f7f7fu : x[d];
+      const v2f lo = Fp8<e4m3_t>::dec2<false>(c), hi = Fp8<e4m3_t>::dec2<true>(c);
+      acc[4 * d] = acc[4 * d] + w * __builtin_ldexpf(lo.x, sh);
+      acc[4 * d + 1] = acc[4 * d + 1] + w * __builtin_ldexpf(lo.y, sh);
+      acc[4 * d + 2] = acc[4 * d + 2] + w * __builtin_ldexpf(hi.x, sh);
+      acc[4 * d + 3] = acc[4 * d + 3] + w * __builtin_ldexpf(hi.y, sh);
+    }
   }
-}
+};
+// Eight consecutive units share one f32 scale.  Every lane loads it as one dword through the descriptor
+// of its codes, at rowcount + 4 * (unit / 8): dword-aligned (rowcount % 128 == 0, records are whole
+// dwords), range-checked against the record, and one request for the eight lanes, whose addresses are
+// the same.  The decoded element is ONE rounded single multiply of the code's value by the scale as its
+// bits say, so a NaN, infinite, negative, zero or subnormal scale acts as IEEE says (f32 denormals are
+// on) and a NaN code (0x7F / 0xFF out of v_cvt_pk_f32_fp8) stays a NaN; then the weight's multiply and
+// the add, never fused or reassociated: w * (c * S), not (w * S) * c.  No ldexp, no select on the scale.
+struct CombineFp8b {
+  static __device__ __forceinline__ uint32_t scale_at(uint32_t u) { return (u >> 3) * kFp8bScaleBytes; }
+  typedef Scal<4> ScaleLd;
+  static __device__ __forceinline__ MNCCL_SCALAR_F32 void mac16(float (&acc)[16], v4u x, uint32_t s, float w) {
+#pragma clang fp contract(off)
+    const float S = __uint_as_float(s);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const v2f lo = Fp8<e4m3_t>::dec2<false>(x[d]), hi = Fp8<e4m3_t>::dec2<true>(x[d]);
+      acc[4 * d] = acc[4 * d] + w * (lo.x * S);
+      acc[4 * d + 1] = acc[4 * d + 1] + w * (lo.y * S);
+      acc[4 * d + 2] = acc[4 * d + 2] + w * (hi.x * S);
+      acc[4 * d + 3] = acc[4 * d + 3] + w * (hi.y * S);
+    }
+  }
+};
 // vector c of a unit's 16 * sizeof(T) output bytes
 template <typename T>
 __device__ __forceinline__ v4u combinemx_pack(const float (&acc)[16], int c) {
@@ -2791,7 +2826,7 @@ __device__ __forceinline__ v4u combinemx_pack(const float (&acc)[16], int c) {
 // 2 KiB of codes per source and batch: 8 sources are 64 code registers and 16 scale registers (a byte each) in flight
 constexpr int kCombineMxV = 2;
 
-template <typename T, int G, int V>
+template <typename Fmt, typename T, int G, int V>
 __device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_wide(const CollParams& p, const CombineArgs& v, u64 soff, u64 b,
                                                                 int lane) {
   constexpr uint32_t UB = 16 * sizeof(T), step = 64 * V;
@@ -2860,12 +2895,12 @@ __device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_wide(const CollParams
             // (a lane past the segment loads nothing: an offset beyond every record)
             const uint32_t un = at + (uint32_t)(u * 64 + lane), iu = i0 + un;
             x[g][u] = ld_slot16(src[g], un < nseg ? iu * 16u : kMxNowhere);
-            sc[g][u] = Scal<1>::ld(src[g], un < nseg ? rc + (iu >> 1) : kMxNowhere);
+            sc[g][u] = Fmt::ScaleLd::ld(src[g], un < nseg ? rc + Fmt::scale_at(iu) : kMxNowhere);
           }
 #pragma unroll
         for (int g = 0; g < G; ++g)
 #pragma unroll
-          for (int u = 0; u < V; ++u) combinemx_mac16(acc[u], x[g][u], sc[g][u], w[g]);
+          for (int u = 0; u < V; ++u) Fmt::mac16(acc[u], x[g][u], sc[g][u], w[g]);
       }
 #pragma unroll
       for (int u = 0; u < V; ++u)
@@ -2878,7 +2913,7 @@ __device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_wide(const CollParams
 
 // Unit `unit` (16 elements) of output row `row`, by this lane alone: its topk slots in order.  Rank q's
 // send is peer_send[q], or `src` for every q (LOCAL).  A record lies whole in the window of its first byte.
-template <typename T, bool LOCAL>
+template <typename Fmt, typename T, bool LOCAL>
 __device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_unit(const CollParams* p, const char* src, char* recv,
                                                                 const CombineArgs& v, int n, u64 row, uint32_t unit) {
   const uint32_t rc = v.row_bytes / (uint32_t)sizeof(T), P = rc + (rc >> 5), topk = v.topk;
@@ -2913,11 +2948,11 @@ __device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_unit(const CollParams
         const rsrc_t s = make_rsrc(from + v.src_off[sq] + win, (uint32_t)(left < 0x80008000ull ? left : 0x80008000ull));
         const uint32_t o = (uint32_t)(rel - win);
         x4 = ld_slot16(s, o + unit * 16u);
-        sc = Scal<1>::ld(s, o + rc + (unit >> 1));
+        sc = Fmt::ScaleLd::ld(s, o + rc + Fmt::scale_at(unit));
         pending = false;
       }
     }
-    if (valid) combinemx_mac16(acc, x4, sc, w);
+    if (valid) Fmt::mac16(acc, x4, sc, w);
   }
   char* to = recv + row * v.stride_bytes + (u64)unit * (16 * sizeof(T));
 #pragma unroll
@@ -2926,24 +2961,24 @@ __device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_unit(const CollParams
 }
 
 // slice [soff, b) of this rank's packed output rows
-template <typename T>
+template <typename Fmt, typename T>
 __device__ __forceinline__ MNCCL_SCALAR_F32 void combinemx_slice(const CollParams& p, const CombineArgs& v, u64 soff, u64 b,
                                                                  int lane) {
   constexpr uint32_t UB = 16 * sizeof(T);
   const uint32_t rb = v.row_bytes;
   const MxLanes g = mx_lanes(rb / (uint32_t)sizeof(T));
   if (g.lanes == 64) {
-    if (v.topk <= 1) combinemx_wide<T, 1, kCombineMxV>(p, v, soff, b, lane);
-    else if (v.topk <= 2) combinemx_wide<T, 2, kCombineMxV>(p, v, soff, b, lane);
-    else if (v.topk <= 4) combinemx_wide<T, 4, kCombineMxV>(p, v, soff, b, lane);
-    else combinemx_wide<T, 8, kCombineMxV>(p, v, soff, b, lane);
+    if (v.topk <= 1) combinemx_wide<Fmt, T, 1, kCombineMxV>(p, v, soff, b, lane);
+    else if (v.topk <= 2) combinemx_wide<Fmt, T, 2, kCombineMxV>(p, v, soff, b, lane);
+    else if (v.topk <= 4) combinemx_wide<Fmt, T, 4, kCombineMxV>(p, v, soff, b, lane);
+    else combinemx_wide<Fmt, T, 8, kCombineMxV>(p, v, soff, b, lane);
     return;
   }
   const uint32_t lr = (uint32_t)lane / g.lanes, lc = (uint32_t)lane % g.lanes;
   if (lr >= g.rows) return;
   for (u64 row = soff / rb + lr; row * rb < b; row += g.rows) {
     const u64 at = row * rb + (u64)lc * UB;  // the unit's first byte: the slice that holds it stores the unit
-    if (at >= soff && at < b) combinemx_unit<T, false>(&p, nullptr, p.recv, v, p.n, row, lc);
+    if (at >= soff && at < b) combinemx_unit<Fmt, T, false>(&p, nullptr, p.recv, v, p.n, row, lc);
   }
 }
 
@@ -2951,7 +2986,7 @@ template <typename T>
 __global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) MNCCL_SCALAR_F32 combinemx_fold(CollParams p, CombineArgs v) {
   __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
   read_half<false, true>(
-      p, s_tx, s_rx, [&p, &v](u64 coff, uint32_t len, int lane) { combinemx_slice<T>(p, v, coff, coff + len, lane); }, 0,
+      p, s_tx, s_rx, [&p, &v](u64 coff, uint32_t len, int lane) { combinemx_slice<CombineMxfp8, T>(p, v, coff, coff + len, lane); }, 0,
       (u64)v.nrows * v.row_bytes);
 }
 
@@ -2963,7 +2998,23 @@ __global__ void __launch_bounds__(256) MNCCL_SCALAR_F32 combinemx_local(CombineA
   const uint32_t nu = v.row_bytes / (16u * (uint32_t)sizeof(T));
   const u64 total = (u64)v.nrows * nu;
   for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (u64)gridDim.x * blockDim.x)
-    combinemx_unit<T, true>(nullptr, src, recv, v, n, i / nu, (uint32_t)(i % nu));
+    combinemx_unit<CombineMxfp8, T, true>(nullptr, src, recv, v, n, i / nu, (uint32_t)(i % nu));
+}
+
+// mncclAllToAllvCombineFp8Block128: the same pair over fp8block.h's records (CombineFp8b)
+template <typename T>
+__global__ void __launch_bounds__(kMaxThreads, kMinWavesPerSimd) MNCCL_SCALAR_F32 combinefp8b_fold(CollParams p, CombineArgs v) {
+  __shared__ u64 s_tx[kMaxWaves][kMaxRanks], s_rx[kMaxWaves][kMaxRanks];
+  read_half<false, true>(
+      p, s_tx, s_rx, [&p, &v](u64 coff, uint32_t len, int lane) { combinemx_slice<CombineFp8b, T>(p, v, coff, coff + len, lane); },
+      0, (u64)v.nrows * v.row_bytes);
+}
+template <typename T>
+__global__ void __launch_bounds__(256) MNCCL_SCALAR_F32 combinefp8b_local(CombineArgs v, const char* src, char* recv, int n) {
+  const uint32_t nu = v.row_bytes / (16u * (uint32_t)sizeof(T));
+  const u64 total = (u64)v.nrows * nu;
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (u64)gridDim.x * blockDim.x)
+    combinemx_unit<CombineFp8b, T, true>(nullptr, src, recv, v, n, i / nu, (uint32_t)(i % nu));
 }
 
 // ---------------------------------------------------------------- point to point
@@ -3975,18 +4026,30 @@ static bool combinemx_args_ok(int dtype, const CombineArgs& v, const void* recv,
   return ((u64)(uintptr_t)recv | v.stride_bytes) % 4 == 0;
 }
 
-hipError_t launch_combinemx(int dtype, int C, int nt, const CollParams& p, const CombineArgs& v, hipStream_t st) {
+// (the two record formats are as long and take the same checks: only the collective id and the kernels differ)
+static hipError_t launch_combine_records(bool fp8b, int dtype, int C, int nt, const CollParams& p, const CombineArgs& v,
+                                         hipStream_t st) {
   // (a rank with no output rows passes a stand-in list, Comm::combine: never read, but not NULL)
-  if (p.coll != kCollAllToAllVCombineMx || p.n < 2 || !v.slotidx || (dtype != kF32 && dtype != kF16 && dtype != kBF16) ||
-      !combinemx_args_ok(dtype, v, p.recv, p.n) || (u64)v.nrows * v.row_bytes > p.chunk_bytes)
+  if (p.coll != (fp8b ? kCollAllToAllVCombineFp8b : kCollAllToAllVCombineMx) || p.n < 2 || !v.slotidx ||
+      (dtype != kF32 && dtype != kF16 && dtype != kBF16) || !combinemx_args_ok(dtype, v, p.recv, p.n) ||
+      (u64)v.nrows * v.row_bytes > p.chunk_bytes)
     return hipErrorInvalidValue;
   return for_combine_type(dtype, [&](auto t) {
-    hipLaunchKernelGGL(combinemx_fold<typename decltype(t)::type>, dim3(C), dim3(nt), 0, st, p, v);
+    typedef typename decltype(t)::type T;
+    auto* const k = fp8b ? combinefp8b_fold<T> : combinemx_fold<T>;
+    hipLaunchKernelGGL(k, dim3(C), dim3(nt), 0, st, p, v);
     return hipGetLastError();
   });
 }
+hipError_t launch_combinemx(int dtype, int C, int nt, const CollParams& p, const CombineArgs& v, hipStream_t st) {
+  return launch_combine_records(false, dtype, C, nt, p, v, st);
+}
+hipError_t launch_combinefp8b(int dtype, int C, int nt, const CollParams& p, const CombineArgs& v, hipStream_t st) {
+  return launch_combine_records(true, dtype, C, nt, p, v, st);
+}
 
-hipError_t launch_combinemx_local(int dtype, int n, const CombineArgs& v, const void* src, void* recv, hipStream_t st) {
+static hipError_t launch_combine_records_local(bool fp8b, int dtype, int n, const CombineArgs& v, const void* src, void* recv,
+                                               hipStream_t st) {
   if ((dtype != kF32 && dtype != kF16 && dtype != kBF16) || !combinemx_args_ok(dtype, v, recv, n) || (v.nrows && !recv) ||
       (u64)(uintptr_t)src % 4)
     return hipErrorInvalidValue;
@@ -3994,10 +4057,17 @@ hipError_t launch_combinemx_local(int dtype, int n, const CombineArgs& v, const 
   const u64 want = ((u64)v.nrows * (v.row_bytes / (16u * (uint32_t)dtype_size(dtype))) + 255) / 256;
   const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);  // the rest by the grid's stride
   return for_combine_type(dtype, [&](auto t) {
-    hipLaunchKernelGGL(combinemx_local<typename decltype(t)::type>, dim3(blocks), dim3(256), 0, st, v,
-                       static_cast<const char*>(src), static_cast<char*>(recv), n);
+    typedef typename decltype(t)::type T;
+    auto* const k = fp8b ? combinefp8b_local<T> : combinemx_local<T>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, v, static_cast<const char*>(src), static_cast<char*>(recv), n);
     return hipGetLastError();
   });
+}
+hipError_t launch_combinemx_local(int dtype, int n, const CombineArgs& v, const void* src, void* recv, hipStream_t st) {
+  return launch_combine_records_local(false, dtype, n, v, src, recv, st);
+}
+hipError_t launch_combinefp8b_local(int dtype, int n, const CombineArgs& v, const void* src, void* recv, hipStream_t st) {
+  return launch_combine_records_local(true, dtype, n, v, src, recv, st);
 }
 
 // the shapes both point-to-point kernels assume, checked before anything is launched: every index

@@ -181,7 +181,10 @@ enum Coll : int {
   kCollAllToAllVCombineMx = 15,
   // mncclAllToAllvRowsFp8Block128: kCollAllToAllVRowsMx with e4m3 elements and one f32 scale per 128
   // (fp8block.h); its record is as long as MXFP8's, so only this id and kVarRowsFp8b tell the calls apart
-  kCollAllToAllVRowsFp8b = 16
+  kCollAllToAllVRowsFp8b = 16,
+  // mncclAllToAllvCombineFp8Block128: kCollAllToAllVCombineMx out of fp8block.h's records (combinefp8b.h);
+  // the records are as long as MXFP8's, so only this id tells the two combines apart
+  kCollAllToAllVCombineFp8b = 17
 };
 
 // r, root: gather and scatter only (their op count depends on the rank's place in the chain; the

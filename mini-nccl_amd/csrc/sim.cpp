@@ -1737,6 +1737,23 @@ int mnccl_sim_combinemx_fold_row(const uint8_t* recs, uint64_t nrec, uint32_t ro
   return 0;
 }
 
+// csrc/combinefp8b.h, the host-side rules of mncclAllToAllvCombineFp8Block128: the same local checks over
+// fp8block.h's records, and the host decode-and-fold of one output row (one rounded multiply by the f32 scale)
+int mnccl_sim_combinefp8b_check_local(int n, int esz, const void* send, const size_t* sendcounts, const size_t* sdispls,
+                                      const void* recv, size_t nrows, size_t rowstride, const int32_t* slotidx,
+                                      const float* weights, int topk, const size_t* recvcounts, const size_t* rdispls,
+                                      size_t rowcount) {
+  if (n < 1 || n > mnccl::kVarMaxRanks || esz < 1) return -2;
+  return mnccl::combinefp8b_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights, topk,
+                                        recvcounts, rdispls, rowcount);
+}
+int mnccl_sim_combinefp8b_fold_row(const uint8_t* recs, uint64_t nrec, uint32_t rowcount, const int32_t* slots,
+                                   const float* weights, int topk, float* out) {
+  if (rowcount % mnccl::kFp8bBlock || topk < 1 || topk > mnccl::kCombineMaxTopk) return -2;
+  mnccl::combinefp8b_fold_row(recs, nrec, rowcount, slots, weights, topk, out);
+  return 0;
+}
+
 // csrc/vhalves.h, the host-side rules of mncclAllGatherv / mncclReduceScatterv, and schedule.h's length
 // rule for them.  mnccl_vhalf_rows_differ: counts / displs are n x n, row r what rank r passed.
 int mnccl_vhalf_check_local(int n, int rank, int esz, const void* array_buf, const size_t* counts, const size_t* displs,

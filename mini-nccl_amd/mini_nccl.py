@@ -109,6 +109,8 @@ SIGNATURES = {
                                    ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllToAllvCombineMxfp8": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _SZ, _VP, _VP, _I,
                                         ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
+    "mncclAllToAllvCombineFp8Block128": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _SZ, _VP, _VP, _I,
+                                              ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _SZ, _I, _VP, _VP]),
     "mncclAllGatherv": (_I, [_VP, _SZ, _VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _I, _VP, _VP]),
     "mncclReduceScatterv": (_I, [_VP, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), _VP, _SZ, _I, _I, _VP, _VP]),
     "ncclGather": (_I, [_VP, _VP, _SZ, _I, _I, _VP, _VP]),
@@ -364,6 +366,18 @@ class Comm:
         arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
         return load().mncclAllToAllvCombineMxfp8(send_ptr, arrays[0], arrays[1], recv_ptr, nrows, rowstride, slotidx_ptr,
                                                  weights_ptr, topk, arrays[2], arrays[3], rowcount, dtype, self.handle, stream)
+
+    def all_to_all_v_combine_fp8_block128(self, send_ptr, sendcounts, sdispls, recv_ptr, nrows, rowstride, slotidx_ptr,
+                                          weights_ptr, topk, recvcounts, rdispls, rowcount, dtype=ncclBfloat16, stream=0):
+        """mncclAllToAllvCombineFp8Block128: all_to_all_v_combine whose send rows are the records
+        all_to_all_v_rows_fp8_block128 delivers -- rowcount e4m3 bytes, then rowcount // 128 float32 scales --
+        each element one rounded float32 multiply by its block's scale inside the fold; dtype and rowstride are
+        the recv matrix's (float32, float16 or bfloat16).  Counts, displacements and slotidx are in records;
+        rowcount is a multiple of 128 in [128, 16384].  Returns the ncclResult_t."""
+        arrays = [(ctypes.c_size_t * len(a))(*[int(x) for x in a]) for a in (sendcounts, sdispls, recvcounts, rdispls)]
+        return load().mncclAllToAllvCombineFp8Block128(send_ptr, arrays[0], arrays[1], recv_ptr, nrows, rowstride, slotidx_ptr,
+                                                       weights_ptr, topk, arrays[2], arrays[3], rowcount, dtype, self.handle,
+                                                       stream)
 
     def all_gather_v(self, send_ptr, sendcount, recv_ptr, recvcounts, rdispls, dtype=ncclFloat, stream=0):
         """mncclAllGatherv: rank q's `sendcount` elements of send end up at elements [rdispls[q],

@@ -82,6 +82,9 @@ persistent form (mncclAlgoRead), fp32 Sum, stream-ordered (MINI_NCCL_BLOCKING=0)
     alltoallv_combine_mxfp8 / alltoallv_combine_mxfp8_composed   mncclAllToAllvCombineMxfp8 on as many MXFP8 records, and
                     what a caller runs without it: a dequantise pass to bf16 rows, then mncclAllToAllvCombine.  Ratios
                     alltoallv_combine_mxfp8_over_composed and, when timed too, alltoallv_combine_mxfp8_over_alltoallv_combine
+    alltoallv_combine_fp8b / alltoallv_combine_fp8b_composed   the same pair for mncclAllToAllvCombineFp8Block128 on as many
+                    "1 x 128" records.  Ratios alltoallv_combine_fp8b_over_composed and, when those kinds are timed too,
+                    alltoallv_combine_fp8b_over_alltoallv_combine_mxfp8 and alltoallv_combine_fp8b_over_alltoallv_combine
     alltoallv_combine_composed   what a caller runs without it, on the same data: ncclAllToAllv into a
                     packed buffer, then the fold as a kernel of its own (combine_local, through a one-rank
                     communicator).  Ratio alltoallv_combine_over_composed beside both spreads
@@ -122,7 +125,8 @@ KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_pr
          "reduce_scatter_padded", "alltoallv_rows", "alltoallv_rows_composed", "alltoallv_combine",
          "alltoallv_combine_composed", "alltoallv_rows_mxfp8", "alltoallv_rows_mxfp8_composed", "alltoallv_rows_mxfp4",
          "alltoallv_rows_mxfp4_composed", "alltoallv_combine_mxfp8", "alltoallv_combine_mxfp8_composed",
-         "alltoallv_rows_fp8_block128", "alltoallv_rows_fp8_block128_composed")
+         "alltoallv_rows_fp8_block128", "alltoallv_rows_fp8_block128_composed", "alltoallv_combine_fp8b",
+         "alltoallv_combine_fp8b_composed")
 # mncclAllToAllvRows beside what a caller composes without it, on the same matrix and indices
 ROWS_KINDS = ("alltoallv_rows", "alltoallv_rows_composed")
 # mncclAllToAllvRowsMxfp8 beside the quantise kernel followed by ncclAllToAllv of bytes, same matrix and indices
@@ -135,13 +139,15 @@ FP8B_KINDS = ("alltoallv_rows_fp8_block128", "alltoallv_rows_fp8_block128_compos
 COMBINE_KINDS = ("alltoallv_combine", "alltoallv_combine_composed")
 # mncclAllToAllvCombineMxfp8 beside a dequantise pass to bf16 followed by mncclAllToAllvCombine, on the same counts and slots
 COMBINE_MX_KINDS = ("alltoallv_combine_mxfp8", "alltoallv_combine_mxfp8_composed")
+# mncclAllToAllvCombineFp8Block128 beside the same composition out of its records
+COMBINE_FP8B_KINDS = ("alltoallv_combine_fp8b", "alltoallv_combine_fp8b_composed")
 # the kinds that need the padded buffers (n blocks of the skewed shape's largest block)
 PADDED_KINDS = ("all_gather_padded", "reduce_scatter_padded")
 VHALF_SKEW = ("all_gather_v_skew", "reduce_scatter_v_skew") + PADDED_KINDS
 # the kinds --dtype bf16 can time (the others' helpers are written for fp32 elements)
 # the kinds that run while big_b is a registered window, and the scratch form each is measured against
 WIN_KINDS = {"p2p_neighbor_win": "p2p_neighbor", "p2p_all_pairs_win": "p2p_all_pairs"}
-BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce") + ROWS_KINDS + COMBINE_KINDS + COMBINE_MX_KINDS + MX_KINDS + MX4_KINDS + FP8B_KINDS
+BF16_KINDS = ("all_reduce", "all_reduce_premul", "reduce_scatter", "reduce_scatter_premul", "reduce") + ROWS_KINDS + COMBINE_KINDS + COMBINE_MX_KINDS + COMBINE_FP8B_KINDS + MX_KINDS + MX4_KINDS + FP8B_KINDS
 
 
 def skew_matrix(n, chunk, seed):
@@ -210,7 +216,7 @@ def rows_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stre
 
 
 def combine_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, stream):
-    """(fused, composed, buffers, solo, mx, mx_composed): the way back of rows_calls' layer on its matrix -- this rank's
+    """(fused, composed, buffers, solo, mx, mx_composed, fp8b, fp8b_composed): the way back of rows_calls' layer on its matrix -- this rank's
     experts return C[q][rank] rows to rank q and it gets C[rank][q] back from q, bf16 rows of `row_elems`
     elements; half as many tokens as rows come back, each folding two of them (a seeded top-2 list over
     the packed sequence) by seeded weights.  Fused: mncclAllToAllvCombine.  Composed: ncclAllToAllv into
@@ -218,7 +224,8 @@ def combine_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, s
     combine_local alone).  mx: mncclAllToAllvCombineMxfp8 with as many MXFP8 records of `row_elems` elements in
     place of the rows.  mx_composed: the records dequantised to bf16 rows by a kernel of their own (the new call on
     the one-rank communicator with topk 1, the identity list and no weights runs combinemx_local alone), then
-    mncclAllToAllvCombine."""
+    mncclAllToAllvCombine.  fp8b / fp8b_composed: the same two with mncclAllToAllvCombineFp8Block128 on the same bytes read
+    as "1 x 128" records."""
     import numpy as np
     rb = 2 * row_elems
     per = max(1, block_bytes // rb)
@@ -243,19 +250,23 @@ def combine_calls(M, hip_rt, comm, n, rank, block_bytes, row_elems, skew_seed, s
         return r or solo.all_to_all_v_combine(packed.ptr, [back], [0], y.ptr, tokens, row_elems, idx.ptr, w.ptr, 2, [back], [0],
                                               row_elems, M.ncclBfloat16, stream)
     if row_elems % 128 or not 128 <= row_elems <= 16384:  # no records of such rows: the mx kinds fail when called
-        return fused, composed, [send, packed, y, idx, w], solo, lambda: 4, lambda: 4
+        return fused, composed, [send, packed, y, idx, w], solo, lambda: 4, lambda: 4, lambda: 4, lambda: 4
     P, out = row_elems + row_elems // 32, max(1, sum(sc))
     recs, ident = hip_rt.DeviceBuffer(out * P, fresh=True), hip_rt.DeviceBuffer(4 * out, fresh=True)
-    recs.fill_byte(0x38)  # (every element e4m3 1.0 at scale 2^-71: finite)
+    recs.fill_byte(0x38)  # (every element e4m3 1.0 at scale 2^-71, or at the single 0x38383838: finite)
     ident.upload(np.arange(out, dtype=np.int32))
-    mx = lambda: comm.all_to_all_v_combine_mxfp8(recs.ptr, sc, starts(sc), y.ptr, tokens, row_elems, idx.ptr, w.ptr, 2, rc,
-                                                 starts(rc), row_elems, M.ncclBfloat16, stream)
+    def pair(entry):  # the entry on the communicator; the entry as a dequantise kernel on the one-rank one, then the bf16 combine
+        def whole():
+            return entry(comm, recs.ptr, sc, starts(sc), y.ptr, tokens, row_elems, idx.ptr, w.ptr, 2, rc, starts(rc), row_elems,
+                         M.ncclBfloat16, stream)
 
-    def mx_composed():
-        r = solo.all_to_all_v_combine_mxfp8(recs.ptr, [out], [0], send.ptr, out, row_elems, ident.ptr, None, 1, [out], [0],
-                                            row_elems, M.ncclBfloat16, stream)
-        return r or fused()
-    return fused, composed, [send, packed, y, idx, w, recs, ident], solo, mx, mx_composed
+        def in_two():
+            r = entry(solo, recs.ptr, [out], [0], send.ptr, out, row_elems, ident.ptr, None, 1, [out], [0], row_elems,
+                      M.ncclBfloat16, stream)
+            return r or fused()
+        return whole, in_two
+    return (fused, composed, [send, packed, y, idx, w, recs, ident], solo) + pair(type(comm).all_to_all_v_combine_mxfp8) + \
+        pair(type(comm).all_to_all_v_combine_fp8_block128)
 
 
 def half_skew_counts(n, chunk):
@@ -370,9 +381,9 @@ def rank_main(a):
             M, hip_rt, comm, n, a.rank, a.bytes // n, a.row_elems, a.skew_seed if a.rows_skew else -1, st.handle)
         pads += more
     solo2 = None
-    if any(k in COMBINE_KINDS + COMBINE_MX_KINDS for k in kinds):
+    if any(k in COMBINE_KINDS + COMBINE_MX_KINDS + COMBINE_FP8B_KINDS for k in kinds):
         (calls["alltoallv_combine"], calls["alltoallv_combine_composed"], more, solo2, calls[COMBINE_MX_KINDS[0]],
-         calls[COMBINE_MX_KINDS[1]]) = combine_calls(
+         calls[COMBINE_MX_KINDS[1]], calls[COMBINE_FP8B_KINDS[0]], calls[COMBINE_FP8B_KINDS[1]]) = combine_calls(
             M, hip_rt, comm, n, a.rank, a.bytes // n, a.row_elems, a.skew_seed if a.rows_skew else -1, st.handle)
         pads += more
     window = [None]
@@ -504,7 +515,7 @@ def main():
         "rounds_ms": {k: [round(x, 4) for x in v] for k, v in rounds.items()},
         "hbm_bytes": {k: (2 * n if k in ("all_reduce", "all_reduce_premul", "all_to_all", "all_to_all_v") else n + 1) * chunk_bytes
                       for k in kinds if k not in ("all_to_all_v_skew", "all_to_all_ring", "p2p_neighbor", "p2p_all_pairs",
-                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") + VHALF_SKEW + ROWS_KINDS + COMBINE_KINDS + COMBINE_MX_KINDS + MX_KINDS + MX4_KINDS + FP8B_KINDS
+                                                  "gather", "gather_p2p", "scatter", "scatter_p2p") + VHALF_SKEW + ROWS_KINDS + COMBINE_KINDS + COMBINE_MX_KINDS + COMBINE_FP8B_KINDS + MX_KINDS + MX4_KINDS + FP8B_KINDS
                       and k not in WIN_KINDS},
         "ratio": dict([(f"{k}_over_all_reduce", round(med[k] / med["all_reduce"], 4)) for k in kinds if k != "all_reduce"] +
                       [(f"{k}_over_{y}", round(med[k] / med[y], 4))
@@ -601,6 +612,15 @@ def main():
         if "alltoallv_combine" in med:
             res["ratio"]["alltoallv_combine_mxfp8_over_alltoallv_combine"] = round(med[COMBINE_MX_KINDS[0]] / med["alltoallv_combine"], 4)
         for k in COMBINE_MX_KINDS + (("alltoallv_combine",) if "alltoallv_combine" in med else ()):
+            res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
+    if all(k in med for k in COMBINE_FP8B_KINDS):
+        res["combine_fp8b"] = {"row_elems": a.row_elems, "record_bytes": a.row_elems + a.row_elems // 32,
+                               "out_row_bytes": 2 * a.row_elems, "topk": 2, "matrix": "skew" if a.rows_skew else "balanced"}
+        res["ratio"]["alltoallv_combine_fp8b_over_composed"] = round(med[COMBINE_FP8B_KINDS[0]] / med[COMBINE_FP8B_KINDS[1]], 4)
+        for other in ("alltoallv_combine_mxfp8", "alltoallv_combine"):
+            if other in med:
+                res["ratio"]["alltoallv_combine_fp8b_over_" + other] = round(med[COMBINE_FP8B_KINDS[0]] / med[other], 4)
+        for k in COMBINE_FP8B_KINDS:
             res[k + "_spread"] = round((max(rounds[k]) - min(rounds[k])) / med[k], 4)
     if "all_gather" in rounds:
         res["all_gather_spread"] = round((max(rounds["all_gather"]) - min(rounds["all_gather"])) / med["all_gather"], 4)
