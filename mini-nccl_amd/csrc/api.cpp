@@ -79,6 +79,67 @@ struct RoctxRange {
   ~RoctxRange() { roctxRangePop(); }
 };
 
+// The exception firewall: fn's result, or a std::exception as its message under the entry's name
+// (`what`; internal = false: the older entries that print no "Internal") and ncclInternalError,
+// anything else as ncclSystemError.  The checks an entry makes before it stay in front of it.
+template <typename Fn>
+ncclResult_t guarded(const char* what, Fn&& fn, bool internal = true) {
+  try {
+    return fn();
+  } catch (const std::exception& e) {
+    fprintf(stderr, internal ? "[Mini-NCCL] %s Internal Error: %s\n" : "[Mini-NCCL] %s Error: %s\n", what, e.what());
+    return ncclInternalError;
+  } catch (...) {
+    return ncclSystemError;
+  }
+}
+
+// the datatype check's refusal, as every entry prints it
+ncclResult_t unsupported_dtype(const char* what) {
+  fprintf(stderr, "[Mini-NCCL] %s Internal Error: unsupported DataType\n", what);
+  return ncclInternalError;
+}
+
+// The four dispatches (mini_nccl_ext.h: mncclAllToAllvRows and its quantising forms): ncclAllToAllv's
+// checks in its order; the data buffers and the index list may be NULL on a rank whose counts are all
+// zero, so they are checked with the counts (Comm::var_exchange; rowblock.h, mxblock.h, fp8block.h).
+// A plain row is any datatype; only the two 16-bit floats have a quantiser, and the datatype is the
+// matrix's.  range_name: the roctx range's; what the messages print follows its "mini_nccl".
+ncclResult_t rows_entry(const char* range_name, Comm::RowsFormat fmt, const void* sendbuff, size_t nrows, size_t rowstride,
+                        const int32_t* rowidx, const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
+                        const size_t recvcounts[], const size_t rdispls[], size_t rowcount, ncclDataType_t datatype,
+                        ncclComm_t comm, hipStream_t stream) {
+  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
+  RoctxRange range(range_name);
+  const char* const what = range_name + sizeof("mini_nccl") - 1;
+  if (fmt == Comm::kRowsPlain ? !dtype_ok(datatype) : datatype != ncclFloat16 && datatype != ncclBfloat16)
+    return unsupported_dtype(what);
+  return guarded(what, [&] {
+    return reinterpret_cast<Comm*>(comm)->all_to_all_v_rows(sendbuff, nrows, rowstride, rowidx, sendcounts, sdispls, recvbuff,
+                                                            recvcounts, rdispls, rowcount, (int)datatype, stream, fmt);
+  });
+}
+
+// The three ways back (mini_nccl_ext.h: mncclAllToAllvCombine and its record forms): the dispatches'
+// checks in their order; the fold is in float, so only the datatypes with one are taken -- the OUTPUT
+// matrix's where the send side holds records.  The buffers and the lists are checked with the counts
+// and nrows where the communicator's size is known (Comm::combine; combine.h, combinemx.h, combinefp8b.h).
+ncclResult_t combine_entry(const char* range_name, Comm::CombineFormat fmt, const void* sendbuff, const size_t sendcounts[],
+                           const size_t sdispls[], void* recvbuff, size_t nrows, size_t rowstride, const int32_t* slotidx,
+                           const float* weights, int topk, const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
+                           ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
+  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
+  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
+  RoctxRange range(range_name);
+  const char* const what = range_name + sizeof("mini_nccl") - 1;
+  if (datatype != ncclFloat && datatype != ncclFloat16 && datatype != ncclBfloat16) return unsupported_dtype(what);
+  return guarded(what, [&] {
+    return reinterpret_cast<Comm*>(comm)->combine(sendbuff, sendcounts, sdispls, recvbuff, nrows, rowstride, slotidx, weights,
+                                                  topk, recvcounts, rdispls, rowcount, (int)datatype, stream, fmt);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -146,23 +207,15 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
   if (count == 0) return ncclSuccess;                               // api.cpp:140
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclAllReduce");
-  if (!dtype_ok(datatype)) {
-    // the reference throws inside get_type_size / to_internal_op -> ncclInternalError (:182-185)
-    fprintf(stderr, "[Mini-NCCL] AllReduce Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
+  // the reference throws inside get_type_size / to_internal_op -> ncclInternalError (:182-185)
+  if (!dtype_ok(datatype)) return unsupported_dtype("AllReduce");
   int kop = 0;
   uint64_t scalar = 0;
   const ncclResult_t orc = resolve_op("AllReduce", reinterpret_cast<const Comm*>(comm), datatype, op, &kop, &scalar);
   if (orc != ncclSuccess) return orc;
-  try {
+  return guarded("AllReduce", [&] {
     return reinterpret_cast<Comm*>(comm)->allreduce(sendbuff, recvbuff, count, (int)datatype, kop, stream, scalar);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllReduce Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  });
 }
 
 // ------------------------------------------------------------------ extensions
@@ -174,22 +227,14 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
   if (recvcount == 0) return ncclSuccess;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclReduceScatter");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] ReduceScatter Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
+  if (!dtype_ok(datatype)) return unsupported_dtype("ReduceScatter");
   int kop = 0;
   uint64_t scalar = 0;
   const ncclResult_t orc = resolve_op("ReduceScatter", reinterpret_cast<const Comm*>(comm), datatype, op, &kop, &scalar);
   if (orc != ncclSuccess) return orc;
-  try {
+  return guarded("ReduceScatter", [&] {
     return reinterpret_cast<Comm*>(comm)->reduce_scatter(sendbuff, recvbuff, recvcount, (int)datatype, kop, stream, scalar);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] ReduceScatter Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  });
 }
 
 ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype,
@@ -198,18 +243,10 @@ ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcoun
   if (sendcount == 0) return ncclSuccess;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclAllGather");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] AllGather Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
+  if (!dtype_ok(datatype)) return unsupported_dtype("AllGather");
+  return guarded("AllGather", [&] {
     return reinterpret_cast<Comm*>(comm)->all_gather(sendbuff, recvbuff, sendcount, (int)datatype, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllGather Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  });
 }
 
 // The two rooted collectives (mini_nccl_ext.h).  The buffer a rank's role does not use may be NULL,
@@ -221,18 +258,10 @@ ncclResult_t ncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, n
   if (count == 0) return ncclSuccess;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclBroadcast");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] Broadcast Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
+  if (!dtype_ok(datatype)) return unsupported_dtype("Broadcast");
+  return guarded("Broadcast", [&] {
     return reinterpret_cast<Comm*>(comm)->broadcast(sendbuff, recvbuff, count, (int)datatype, root, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] Broadcast Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  });
 }
 
 ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclRedOp_t op,
@@ -241,22 +270,14 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
   if (count == 0) return ncclSuccess;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclReduce");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] Reduce Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
+  if (!dtype_ok(datatype)) return unsupported_dtype("Reduce");
   int kop = 0;
   uint64_t scalar = 0;
   const ncclResult_t orc = resolve_op("Reduce", reinterpret_cast<const Comm*>(comm), datatype, op, &kop, &scalar);
   if (orc != ncclSuccess) return orc;
-  try {
+  return guarded("Reduce", [&] {
     return reinterpret_cast<Comm*>(comm)->reduce(sendbuff, recvbuff, count, (int)datatype, kop, root, stream, scalar);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] Reduce Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  });
 }
 
 // The all-to-all (mini_nccl_ext.h): the halves' checks in their order; the overlap of the two
@@ -267,18 +288,10 @@ ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, nc
   if (count == 0) return ncclSuccess;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclAllToAll");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] AllToAll Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
+  if (!dtype_ok(datatype)) return unsupported_dtype("AllToAll");
+  return guarded("AllToAll", [&] {
     return reinterpret_cast<Comm*>(comm)->all_to_all(sendbuff, recvbuff, count, (int)datatype, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllToAll Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  });
 }
 
 // Gather and scatter (mini_nccl_ext.h): the rooted collectives' checks in their order -- the large
@@ -290,18 +303,10 @@ ncclResult_t ncclGather(const void* sendbuff, void* recvbuff, size_t sendcount, 
   if (sendcount == 0) return ncclSuccess;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclGather");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] Gather Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
+  if (!dtype_ok(datatype)) return unsupported_dtype("Gather");
+  return guarded("Gather", [&] {
     return reinterpret_cast<Comm*>(comm)->gather(sendbuff, recvbuff, sendcount, (int)datatype, root, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] Gather Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  });
 }
 
 ncclResult_t ncclScatter(const void* sendbuff, void* recvbuff, size_t recvcount, ncclDataType_t datatype, int root,
@@ -310,18 +315,10 @@ ncclResult_t ncclScatter(const void* sendbuff, void* recvbuff, size_t recvcount,
   if (recvcount == 0) return ncclSuccess;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclScatter");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] Scatter Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
+  if (!dtype_ok(datatype)) return unsupported_dtype("Scatter");
+  return guarded("Scatter", [&] {
     return reinterpret_cast<Comm*>(comm)->scatter(sendbuff, recvbuff, recvcount, (int)datatype, root, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] Scatter Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  });
 }
 
 // The variable all-to-all (mini_nccl_ext.h): the communicator and the four arrays, then the
@@ -333,192 +330,68 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
   if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclAllToAllv");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllv Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
+  if (!dtype_ok(datatype)) return unsupported_dtype("AllToAllv");
+  return guarded("AllToAllv", [&] {
     return reinterpret_cast<Comm*>(comm)->all_to_all_v(sendbuff, sendcounts, sdispls, recvbuff, recvcounts, rdispls,
                                                        (int)datatype, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllv Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  });
 }
 
-// The same gathered by row index (mini_nccl_ext.h): ncclAllToAllv's checks in its order; the data
-// buffers and the index list may be NULL on a rank whose counts are all zero, so they are checked with
-// the counts (Comm::all_to_all_v_rows, rowblock.h).
+// The dispatches and the ways back (mini_nccl_ext.h): one body each, rows_entry and combine_entry above.
 ncclResult_t mncclAllToAllvRows(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
                                 const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                                 const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
                                 ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
-  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
-  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
-  RoctxRange range("mini_ncclAllToAllvRows");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvRows Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
-    return reinterpret_cast<Comm*>(comm)->all_to_all_v_rows(sendbuff, nrows, rowstride, rowidx, sendcounts, sdispls, recvbuff,
-                                                            recvcounts, rdispls, rowcount, (int)datatype, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvRows Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return rows_entry("mini_ncclAllToAllvRows", Comm::kRowsPlain, sendbuff, nrows, rowstride, rowidx, sendcounts, sdispls, recvbuff,
+                    recvcounts, rdispls, rowcount, datatype, comm, stream);
 }
 
-// The same quantised to MXFP8 records on the way out (mini_nccl_ext.h): mncclAllToAllvRows' checks in
-// its order; the datatype is the matrix's, and only the two 16-bit floats have a quantiser
-// (Comm::all_to_all_v_rows_mx, mxblock.h).
 ncclResult_t mncclAllToAllvRowsMxfp8(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
                                      const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                                      const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
                                      ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
-  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
-  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
-  RoctxRange range("mini_ncclAllToAllvRowsMxfp8");
-  if (datatype != ncclFloat16 && datatype != ncclBfloat16) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvRowsMxfp8 Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
-    return reinterpret_cast<Comm*>(comm)->all_to_all_v_rows_mx(sendbuff, nrows, rowstride, rowidx, sendcounts, sdispls,
-                                                               recvbuff, recvcounts, rdispls, rowcount, (int)datatype, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvRowsMxfp8 Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return rows_entry("mini_ncclAllToAllvRowsMxfp8", Comm::kRowsMxfp8, sendbuff, nrows, rowstride, rowidx, sendcounts, sdispls,
+                    recvbuff, recvcounts, rdispls, rowcount, datatype, comm, stream);
 }
 
-// The same with MXFP4 records (mini_nccl_ext.h): the MXFP8 entry's checks in its order
-// (Comm::all_to_all_v_rows_mx4, mxblock.h).
 ncclResult_t mncclAllToAllvRowsMxfp4(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
                                      const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                                      const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
                                      ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
-  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
-  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
-  RoctxRange range("mini_ncclAllToAllvRowsMxfp4");
-  if (datatype != ncclFloat16 && datatype != ncclBfloat16) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvRowsMxfp4 Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
-    return reinterpret_cast<Comm*>(comm)->all_to_all_v_rows_mx4(sendbuff, nrows, rowstride, rowidx, sendcounts, sdispls,
-                                                                recvbuff, recvcounts, rdispls, rowcount, (int)datatype, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvRowsMxfp4 Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return rows_entry("mini_ncclAllToAllvRowsMxfp4", Comm::kRowsMxfp4, sendbuff, nrows, rowstride, rowidx, sendcounts, sdispls,
+                    recvbuff, recvcounts, rdispls, rowcount, datatype, comm, stream);
 }
 
-// The same with e4m3 records that carry one f32 scale per 128 elements (mini_nccl_ext.h): the MXFP8
-// entry's checks in its order (Comm::all_to_all_v_rows_fp8b, fp8block.h).
 ncclResult_t mncclAllToAllvRowsFp8Block128(const void* sendbuff, size_t nrows, size_t rowstride, const int32_t* rowidx,
                                            const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                                            const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
                                            ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
-  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
-  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
-  RoctxRange range("mini_ncclAllToAllvRowsFp8Block128");
-  if (datatype != ncclFloat16 && datatype != ncclBfloat16) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvRowsFp8Block128 Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
-    return reinterpret_cast<Comm*>(comm)->all_to_all_v_rows_fp8b(sendbuff, nrows, rowstride, rowidx, sendcounts, sdispls,
-                                                                 recvbuff, recvcounts, rdispls, rowcount, (int)datatype, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvRowsFp8Block128 Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return rows_entry("mini_ncclAllToAllvRowsFp8Block128", Comm::kRowsFp8Block128, sendbuff, nrows, rowstride, rowidx, sendcounts,
+                    sdispls, recvbuff, recvcounts, rdispls, rowcount, datatype, comm, stream);
 }
 
-// The way back (mini_nccl_ext.h): mncclAllToAllvRows' checks in its order; the fold is in float, so
-// only the datatypes with one are taken.  The buffers and the lists are checked with the counts and
-// nrows where the communicator's size is known (Comm::combine, combine.h).
 ncclResult_t mncclAllToAllvCombine(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
                                    size_t nrows, size_t rowstride, const int32_t* slotidx, const float* weights, int topk,
                                    const size_t recvcounts[], const size_t rdispls[], size_t rowcount,
                                    ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
-  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
-  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
-  RoctxRange range("mini_ncclAllToAllvCombine");
-  if (datatype != ncclFloat && datatype != ncclFloat16 && datatype != ncclBfloat16) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvCombine Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
-    return reinterpret_cast<Comm*>(comm)->combine(sendbuff, sendcounts, sdispls, recvbuff, nrows, rowstride, slotidx, weights,
-                                                  topk, recvcounts, rdispls, rowcount, (int)datatype, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvCombine Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return combine_entry("mini_ncclAllToAllvCombine", Comm::kCombinePlain, sendbuff, sendcounts, sdispls, recvbuff, nrows, rowstride,
+                       slotidx, weights, topk, recvcounts, rdispls, rowcount, datatype, comm, stream);
 }
 
-// The way back out of MXFP8 records (mini_nccl_ext.h): mncclAllToAllvCombine's checks in its order;
-// the datatype is the OUTPUT matrix's (Comm::combine with kCombineMxfp8, combinemx.h).
 ncclResult_t mncclAllToAllvCombineMxfp8(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[],
                                         void* recvbuff, size_t nrows, size_t rowstride, const int32_t* slotidx,
                                         const float* weights, int topk, const size_t recvcounts[], const size_t rdispls[],
                                         size_t rowcount, ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
-  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
-  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
-  RoctxRange range("mini_ncclAllToAllvCombineMxfp8");
-  if (datatype != ncclFloat && datatype != ncclFloat16 && datatype != ncclBfloat16) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvCombineMxfp8 Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
-    return reinterpret_cast<Comm*>(comm)->combine(sendbuff, sendcounts, sdispls, recvbuff, nrows, rowstride, slotidx, weights,
-                                                  topk, recvcounts, rdispls, rowcount, (int)datatype, stream,
-                                                  Comm::kCombineMxfp8);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvCombineMxfp8 Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return combine_entry("mini_ncclAllToAllvCombineMxfp8", Comm::kCombineMxfp8, sendbuff, sendcounts, sdispls, recvbuff, nrows,
+                       rowstride, slotidx, weights, topk, recvcounts, rdispls, rowcount, datatype, comm, stream);
 }
 
-// The way back out of "1 x 128" FP8 records (mini_nccl_ext.h): mncclAllToAllvCombine's checks in its order;
-// the datatype is the OUTPUT matrix's (Comm::combine with kCombineFp8Block128, combinefp8b.h).
 ncclResult_t mncclAllToAllvCombineFp8Block128(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[],
                                               void* recvbuff, size_t nrows, size_t rowstride, const int32_t* slotidx,
                                               const float* weights, int topk, const size_t recvcounts[], const size_t rdispls[],
                                               size_t rowcount, ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
-  if (!comm || !sendcounts || !sdispls || !recvcounts || !rdispls) return ncclInvalidArgument;
-  if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
-  RoctxRange range("mini_ncclAllToAllvCombineFp8Block128");
-  if (datatype != ncclFloat && datatype != ncclFloat16 && datatype != ncclBfloat16) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvCombineFp8Block128 Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
-    return reinterpret_cast<Comm*>(comm)->combine(sendbuff, sendcounts, sdispls, recvbuff, nrows, rowstride, slotidx, weights,
-                                                  topk, recvcounts, rdispls, rowcount, (int)datatype, stream,
-                                                  Comm::kCombineFp8Block128);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllToAllvCombineFp8Block128 Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return combine_entry("mini_ncclAllToAllvCombineFp8Block128", Comm::kCombineFp8Block128, sendbuff, sendcounts, sdispls, recvbuff,
+                       nrows, rowstride, slotidx, weights, topk, recvcounts, rdispls, rowcount, datatype, comm, stream);
 }
 
 // The halves with per-rank counts (mini_nccl_ext.h): the communicator and the two arrays, the open
@@ -530,19 +403,11 @@ ncclResult_t mncclAllGatherv(const void* sendbuff, size_t sendcount, void* recvb
   if (!comm || !recvcounts || !rdispls) return ncclInvalidArgument;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclAllGatherv");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] AllGatherv Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
-  try {
+  if (!dtype_ok(datatype)) return unsupported_dtype("AllGatherv");
+  return guarded("AllGatherv", [&] {
     return reinterpret_cast<Comm*>(comm)->all_gather_v(sendbuff, sendcount, recvbuff, recvcounts, rdispls, (int)datatype,
                                                        stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] AllGatherv Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  });
 }
 
 ncclResult_t mncclReduceScatterv(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[], void* recvbuff,
@@ -551,23 +416,15 @@ ncclResult_t mncclReduceScatterv(const void* sendbuff, const size_t sendcounts[]
   if (!comm || !sendcounts || !sdispls) return ncclInvalidArgument;
   if (group_open()) return ncclInvalidUsage;  // no deferred collectives (mini_nccl_ext.h)
   RoctxRange range("mini_ncclReduceScatterv");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] ReduceScatterv Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
+  if (!dtype_ok(datatype)) return unsupported_dtype("ReduceScatterv");
   int kop = 0;
   uint64_t scalar = 0;
   const ncclResult_t orc = resolve_op("ReduceScatterv", reinterpret_cast<const Comm*>(comm), datatype, op, &kop, &scalar);
   if (orc != ncclSuccess) return orc;
-  try {
+  return guarded("ReduceScatterv", [&] {
     return reinterpret_cast<Comm*>(comm)->reduce_scatter_v(sendbuff, sendcounts, sdispls, recvbuff, recvcount,
                                                            (int)datatype, kop, stream, scalar);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] ReduceScatterv Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  });
 }
 
 // Point to point (mini_nccl_ext.h): the checks in the header's order.  Inside a group a call only
@@ -583,10 +440,7 @@ static ncclResult_t p2p_call(bool send, const void* buff, size_t count, ncclData
   if (!comm || (!buff && count != 0)) return fail(ncclInvalidArgument);
   if (count == 0) return ncclSuccess;  // both ends skip it: nothing recorded, matching stays consistent
   RoctxRange range(send ? "mini_ncclSend" : "mini_ncclRecv");
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] %s Internal Error: unsupported DataType\n", send ? "Send" : "Recv");
-    return fail(ncclInternalError);
-  }
+  if (!dtype_ok(datatype)) return fail(unsupported_dtype(send ? "Send" : "Recv"));
   Comm* c = reinterpret_cast<Comm*>(comm);
   try {
     if (!grouped) {
@@ -637,14 +491,7 @@ ncclResult_t ncclGroupEnd(void) {
   if (done.err != ncclSuccess) return done.err;  // poisoned: nothing is launched
   if (done.ops.nops == 0 || !done.comm) return ncclSuccess;
   RoctxRange range("mini_ncclGroupEnd");
-  try {
-    return done.comm->p2p_group(done.ops, done.stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] GroupEnd Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return guarded("GroupEnd", [&] { return done.comm->p2p_group(done.ops, done.stream); });
 }
 
 // User-created reduction ops (mini_nccl_ext.h): the checks in the header's order.  The scalar is read
@@ -652,10 +499,7 @@ ncclResult_t ncclGroupEnd(void) {
 ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataType_t datatype,
                                       ncclScalarResidence_t residence, ncclComm_t comm) {
   if (!comm || !op || !scalar) return ncclInvalidArgument;
-  if (!dtype_ok(datatype)) {
-    fprintf(stderr, "[Mini-NCCL] RedOpCreatePreMulSum Internal Error: unsupported DataType\n");
-    return ncclInternalError;
-  }
+  if (!dtype_ok(datatype)) return unsupported_dtype("RedOpCreatePreMulSum");
   Comm* c = reinterpret_cast<Comm*>(comm);
   if (c->sticky_error() != ncclSuccess) return c->sticky_error();
   if (residence != ncclScalarHostImmediate) {
@@ -699,14 +543,8 @@ ncclResult_t mncclLocalReduce(void* out, const void* local, const void* incoming
   if (!out || !local || !incoming) return ncclInvalidArgument;
   if (count == 0) return ncclSuccess;
   if (!dtype_ok(datatype) || !op_ok(op)) return ncclInternalError;
-  try {
-    return mnccl::local_reduce(out, local, incoming, count, (int)datatype, (int)op, stream);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] LocalReduce Internal Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return guarded("LocalReduce",
+                 [&] { return mnccl::local_reduce(out, local, incoming, count, (int)datatype, (int)op, stream); });
 }
 
 ncclResult_t mncclCommGetAsyncError(ncclComm_t comm, ncclResult_t* asyncError) {
@@ -796,38 +634,17 @@ ncclResult_t mncclCommSetAlgo(ncclComm_t comm, int algo) {
 
 ncclResult_t mncclCommLinkProbe(ncclComm_t comm, int allPeers, size_t bytes, int iters, double* gbps) {
   if (!comm || !gbps) return ncclInvalidArgument;
-  try {
-    return reinterpret_cast<Comm*>(comm)->link_probe(allPeers, bytes, iters, gbps);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] LinkProbe Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return guarded("LinkProbe", [&] { return reinterpret_cast<Comm*>(comm)->link_probe(allPeers, bytes, iters, gbps); }, false);
 }
 
 ncclResult_t mncclCommRegister(ncclComm_t comm, void* buff, size_t size, void** handle) {
   if (!comm || !buff || !handle || size == 0) return ncclInvalidArgument;
-  try {
-    return reinterpret_cast<Comm*>(comm)->register_window(buff, size, handle);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] CommRegister Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return guarded("CommRegister", [&] { return reinterpret_cast<Comm*>(comm)->register_window(buff, size, handle); }, false);
 }
 
 ncclResult_t mncclCommDeregister(ncclComm_t comm, void* handle) {
   if (!comm || !handle) return ncclInvalidArgument;
-  try {
-    return reinterpret_cast<Comm*>(comm)->deregister_window(handle);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[Mini-NCCL] CommDeregister Error: %s\n", e.what());
-    return ncclInternalError;
-  } catch (...) {
-    return ncclSystemError;
-  }
+  return guarded("CommDeregister", [&] { return reinterpret_cast<Comm*>(comm)->deregister_window(handle); }, false);
 }
 
 ncclResult_t mncclDataTypeSize(ncclDataType_t datatype, size_t* size) {

@@ -915,8 +915,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       const bool vec_w = win_s->aligned && win_r->aligned && os % 4 == 0 && orv % 4 == 0 && chunk_bytes % 4 == 0;
       const size_t body = chunk_bytes * (size_t)n;
       const size_t tail = send != recv && bytes > body ? bytes - body : 0;
-      seq = ++call_seq_;
-      if (seq == 0) seq = ++call_seq_;
+      seq = next_seq();
       launch(2, send, recv, chunk_bytes, dtype, op, stream, seq, vec_w, psend, precv, tail, sig, kCollAllReduce, 0, 0,
              scalar);
       ++window_calls_;
@@ -1018,8 +1017,7 @@ ncclResult_t Comm::collective(int coll, const void* send, void* recv, size_t cou
       }
     }
     if (algo == 0 && small) algo = 3;
-    seq = ++call_seq_;
-    if (seq == 0) seq = ++call_seq_;  // 0 = "no kernel" (wait_for)
+    seq = next_seq();
     if (ag_own_copy && algo == 0)
       hip_check(hipMemcpyAsync((char*)krecv + mine, ksend, chunk_bytes, hipMemcpyDefault, stream), "own chunk");
     // the ring's broadcast leaves the root's recv alone (the root only sends): out of place, it gets
@@ -1170,52 +1168,140 @@ bool Comm::gather_rows(const VarRow& mine, int dtype, VarRow* rows, int coll, in
   return same;
 }
 
+// The v-family's rendezvous (comm.h).  The order matters: the stub is allocated only where the read
+// schedule is open and the rank has neither buffer; reap runs before the buffers are classified
+// (known() must not name a freed allocation's export); a windows peer poisons the communicator and aborts the
+// peers before the device is restored.
+bool Comm::var_meet(const VarCall& c, const void* send, void* recv, const VarRow& mine, int cur_dev, VarMeet* m) {
+  m->rsend = send ? send : recv;
+  m->rrecv = recv ? recv : const_cast<void*>(send);
+  if (pbuf_.available()) {
+    const bool read_ok = ((algo_ == 2 || algo_ == 4) && (!auto_ || topo_read_)) || (algo_ == 3 && topo_read_);
+    if (!m->rsend && read_ok) {
+      if (!var_stub_ && hipMalloc((void**)&var_stub_, 256) != hipSuccess) {
+        (void)hipGetLastError();
+        var_stub_ = nullptr;
+      }
+      m->rsend = m->rrecv = var_stub_;
+    }
+    bool eligible = false;
+    if (read_ok && m->rsend) {
+      pbuf_.reap(m->rsend, m->rrecv);
+      bool local_s = false, local_r = false;
+      const void* ks = m->rsend;
+      const void* kr = m->rrecv;
+      const bool dev_s = pbuf_.known(m->rsend) ? (local_s = true) : reach(m->rsend, &ks, &local_s) == Reach::kDevice;
+      const bool dev_r = pbuf_.known(m->rrecv) ? (local_r = true) : reach(m->rrecv, &kr, &local_r) == Reach::kDevice;
+      eligible = dev_s && dev_r && local_s && local_r;
+    }
+    try {
+      m->d = pbuf_.negotiate(m->rsend, m->rrecv, eligible, 0, c.dtype, c.op, cfg_.timeout_ms / 1000.0 + 2.0,
+                             [this] { wait_previous_call(); }, m->psend, m->precv, &m->vec_all,
+                             (auto_ ? 0xff : algo_) | c.coll << 8, &mine, m->rows, c.scalar);
+    } catch (const PeerGaveUp& e) {
+      m->rc = rendezvous_failed(e, true, cur_dev);
+      return false;
+    } catch (const std::exception& e) {
+      m->rc = rendezvous_failed(e, false, cur_dev);
+      return false;
+    }
+    if (m->d == PeerBuffers::kWindowPeer) {
+      fprintf(stderr, "[Mini-NCCL] rank %d: a peer ran this call on registered windows where this rank called %s; "
+              "communicator is no longer usable\n", rank_, c.name);
+      sticky_ = ncclInvalidUsage;
+      abort_peers();
+      m->rc = leave(cur_dev, sticky_);
+      return false;
+    }
+    if (m->d != PeerBuffers::kMismatch) return true;
+    if (c.same_rows)
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: the ranks passed different counts or displacements, or called different "
+              "collectives / datatypes / ops (or scalars) / schedules (mncclCommSetAlgo)\n", rank_, c.name);
+    else
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: some rank's sendcounts[q] differs from rank q's recvcounts for it, or the "
+              "ranks called different collectives / datatypes%s / schedules (mncclCommSetAlgo)\n", rank_, c.name, c.also);
+  } else {
+    // no board: the rows travel over the bootstrap and are compared here
+    const int n = nranks_;
+    const bool same = gather_rows(mine, c.dtype, m->rows, c.coll, c.op, c.scalar);
+    if (c.same_rows) {
+      if (same && vhalf_rows_differ(n, m->rows) == 0) return true;
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: the ranks passed different counts or displacements, or called different "
+              "collectives / datatypes / ops (or scalars)\n", rank_, c.name);
+    } else {
+      if (same && varblock_matrix_mismatch(n, m->rows) == 0 && !varblock_rowcounts_differ(n, m->rows)) return true;
+      fprintf(stderr, "[Mini-NCCL] rank %d: %s: some rank's sendcounts[q] differs from rank q's recvcounts for it, or the "
+              "ranks passed different datatypes%s\n", rank_, c.name, c.also);
+    }
+  }
+  m->rc = leave(cur_dev, ncclInvalidUsage);
+  return false;
+}
+
+// The padded ring's stage may have to be allocated, which a graph capture cannot do: where the
+// decision is the fallback and ANY rank is capturing (its flag rides in its row), every rank refuses.
+ncclResult_t Comm::ring_in_capture(const char* name, int cur_dev) {
+  fprintf(stderr, "[Mini-NCCL] rank %d: %s: this call runs the padded ring, whose stage cannot be allocated inside a "
+          "HIP graph capture (some rank's stream is capturing)\n", rank_, name);
+  return leave(cur_dev, ncclInvalidUsage);
+}
+
+// What tells the dispatches' formats apart (index: Comm::RowsFormat): the name the messages print,
+// the collective id and the flags that ride in the rendezvous (ranks that mix formats get kMismatch),
+// and for a quantised record its bytes per row of rowcount elements and its kernels -- `push` on the
+// read schedule, `pack` into local memory (one rank, and the padded ring's stage).  Plain rows have
+// no record: their unit is the row, their argument blocks RowsArgs / RowsPackArgs (rowblock.h,
+// kernels.h) and their branches in var_exchange their own.  A new format is a new row here.
+struct RowsFormatInfo {
+  const char* name;
+  int coll;
+  uint32_t flags;
+  uint64_t (*record_bytes)(uint64_t rowcount);
+  hipError_t (*push)(int, int, int, const CollParams&, const MxArgs&, hipStream_t);
+  hipError_t (*pack)(int, const MxArgs&, hipStream_t);
+};
+static const RowsFormatInfo kRowsFormats[] = {
+    {"mncclAllToAllvRows", kCollAllToAllVRows, kVarRows, nullptr, nullptr, nullptr},
+    {"mncclAllToAllvRowsMxfp8", kCollAllToAllVRowsMx, kVarRows | kVarRowsMx, mx_record_bytes, launch_rowsmx, launch_rowsmx_pack},
+    {"mncclAllToAllvRowsMxfp4", kCollAllToAllVRowsMx4, kVarRows | kVarRowsMx4, mx4_record_bytes, launch_rowsmx4,
+     launch_rowsmx4_pack},
+    {"mncclAllToAllvRowsFp8Block128", kCollAllToAllVRowsFp8b, kVarRows | kVarRowsFp8b, fp8b_record_bytes, launch_rowsfp8b,
+     launch_rowsfp8b_pack},
+};
+
 // ncclAllToAllv.  The caller's local errors first (varblock.h: nothing launched, nothing
-// negotiated); then every rank's counts reach every rank -- through the read schedule's rendezvous
-// wherever the board exists, whatever the schedule (a rank the read schedule is closed to takes part
-// as ineligible), else over the bootstrap -- so every rank checks the same matrix and derives the
-// same geometry from its largest block M.  On the read schedule: kernels.hip varblock_push.  Else
-// the ring's all-to-all on blocks padded to Mpad = M rounded up to 16: the non-empty off-diagonal
-// blocks are packed into the stage at q * Mpad by stream-ordered copies straight from the user's
-// send (device, pinned or pageable alike), exchanged into a second stage region, and unpacked
-// straight into the user's recv; 2 n Mpad bytes of stage, and the padding crosses the links.  The
-// stage may have to be allocated, which a graph capture cannot do: if the decision is the fallback
-// and ANY rank is capturing (its flag rides in its row), every rank returns ncclInvalidUsage.
-// A rank whose counts are all zero still takes part in the rendezvous and the protocol: its peers
-// exchange among themselves and every pair's counters advance alike.
+// negotiated); then every rank's counts reach every rank (var_meet), so every rank checks the same
+// matrix and derives the same geometry from its largest block M.  On the read schedule: kernels.hip
+// varblock_push.  Else the ring's all-to-all on blocks padded to Mpad = M rounded up to 16: the
+// non-empty off-diagonal blocks are packed into the stage at q * Mpad by stream-ordered copies
+// straight from the user's send (device, pinned or pageable alike), exchanged into a second stage
+// region, and unpacked straight into the user's recv; 2 n Mpad bytes of stage, and the padding
+// crosses the links; refused while any rank is capturing (ring_in_capture).  A rank whose counts are
+// all zero still takes part in the rendezvous and the protocol: its peers exchange among themselves
+// and every pair's counters advance alike.
 //
-// mncclAllToAllvRows (rows != nullptr) is the same call with rows for elements: counts and
-// displacements in rows of rows->rowcount elements, so a block's unit is `unit` bytes where
-// ncclAllToAllv's is the element; the send side is a matrix read through rows->rowidx (rowblock.h has
-// its local rules), the rendezvous row carries kVarRows and the row's length, which the ranks must pass
-// alike.  On the read schedule: kernels.hip rows_push.  Else ONE rows_pack launch gathers the blocks
+// The dispatches (rows_call != nullptr) are the same call with rows for elements: counts and
+// displacements in rows of rows_call->rowcount elements, so a block's unit is `unit` bytes where
+// ncclAllToAllv's is the element; the send side is a matrix read through rows_call->rowidx (rowblock.h
+// has its local rules), the rendezvous row carries the row's length, which the ranks must pass alike.
+// Plain rows: kernels.hip rows_push on the read schedule; else ONE rows_pack launch gathers the blocks
 // where the copies above pack them -- the peers' into the stage at q * Mpad, the own one straight into
-// recv -- and the exchange and the unpack are the ones above.  One rank: rows_pack alone.
-//
-// mncclAllToAllvRowsMxfp8 (rows->mx) is that call again with the row's MXFP8 record for the row on the
-// receive side and on the wire (mxblock.h: P = rowcount + rowcount / 32 bytes, its local rules on top
-// of rowblock.h's); the rendezvous row carries kVarRowsMx beside kVarRows.  On the read schedule:
-// kernels.hip rowsmx_push.  Else rowsmx_pack quantises into the stage where rows_pack gathers, unit P.
-// mncclAllToAllvRowsMxfp4 (kRowsMxfp4) is the MXFP8 call with P4 = rowcount / 2 + rowcount / 32 bytes for
-// P, a collective id and a rendezvous flag of its own (kVarRowsMx4) and the kernels rowsmx4_push / rowsmx4_pack.
-// mncclAllToAllvRowsFp8Block128 (kRowsFp8Block128) is the MXFP8 call with fp8block.h's record -- as long as
-// MXFP8's -- a collective id and a rendezvous flag of its own (kVarRowsFp8b) and rowsfp8b_push / rowsfp8b_pack.
+// recv -- and the exchange and the unpack are the ones above.  One rank: rows_pack alone.  A quantised
+// format (kRowsFormats: `f` below) puts the row's record for the row on the receive side and on the
+// wire, with mxblock.h's local rules on top of rowblock.h's; its push kernel stands for rows_push and
+// its pack kernel quantises where rows_pack gathers.
 ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
                                 const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream,
                                 const RowsCall* rows_call) {
   if (sticky_ != ncclSuccess) return sticky_;
   if (check_status() != ncclSuccess) return sticky_;
   const int n = nranks_, esz = dtype_size(dtype);
-  const bool fp4 = rows_call && rows_call->fmt == kRowsMxfp4, b128 = rows_call && rows_call->fmt == kRowsFp8Block128;
-  const bool mx = fp4 || b128 || (rows_call && rows_call->fmt == kRowsMxfp8);  // a quantised record: the walk's kernels
-  const char* const name = fp4 ? "mncclAllToAllvRowsMxfp4" : b128 ? "mncclAllToAllvRowsFp8Block128" : mx ? "mncclAllToAllvRowsMxfp8"
-                           : rows_call ? "mncclAllToAllvRows" : "ncclAllToAllv";
-  const int coll = fp4 ? kCollAllToAllVRowsMx4 : b128 ? kCollAllToAllVRowsFp8b : mx ? kCollAllToAllVRowsMx
-                   : rows_call ? kCollAllToAllVRows : kCollAllToAllV;
-  // a block's unit in bytes: the element, the row, or the row's MXFP8 / MXFP4 / FP8-block-128 record
-  const size_t unit = fp4 ? (size_t)mx4_record_bytes(rows_call->rowcount) : b128 ? (size_t)fp8b_record_bytes(rows_call->rowcount)
-                      : mx ? (size_t)mx_record_bytes(rows_call->rowcount)
-                      : rows_call ? rows_call->rowcount * (size_t)esz : (size_t)esz;
+  const RowsFormatInfo* const f = rows_call ? &kRowsFormats[rows_call->fmt] : nullptr;
+  const bool mx = f && f->record_bytes;  // a quantised record: MxArgs and the format's kernels
+  const char* const name = f ? f->name : "ncclAllToAllv";
+  const int coll = f ? f->coll : kCollAllToAllV;
+  // a block's unit in bytes: the element, the row, or the row's record
+  const size_t unit = mx ? (size_t)f->record_bytes(rows_call->rowcount) : rows_call ? rows_call->rowcount * (size_t)esz : (size_t)esz;
   if (rows_call) {
     const int local = mx ? mx_check_local(n, esz, send, rows_call->nrows, rows_call->rowstride, rows_call->rowidx, sendcounts,
                                           sdispls, recv, recvcounts, rdispls, rows_call->rowcount, unit)
@@ -1274,6 +1360,19 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
     return reach(p, &k, &l);
   };
   const bool src_via = src_extra && how(send) == Reach::kStaged;
+  // a quantised format's argument block but for the per-peer dst / idx_off / count, which its two
+  // launches fill differently
+  auto mx_args = [&](const void* src, const int32_t* idx) {
+    MxArgs m;
+    memset(&m, 0, sizeof m);
+    m.src = static_cast<const char*>(src);
+    m.rowidx = idx;
+    m.stride_bytes = (uint64_t)rows_call->rowstride * (uint64_t)esz;
+    m.rowcount = (uint32_t)rows_call->rowcount;
+    m.nrows = (uint32_t)rows_call->nrows;
+    m.n = n;
+    return m;
+  };
   auto pack_rows = [&](char* const* dst, char* src_stage) {
     const void* src = send;
     bool l = false;
@@ -1282,21 +1381,14 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
       src = src_stage;
     }
     if (mx) {
-      MxArgs m;
-      memset(&m, 0, sizeof m);
-      m.src = static_cast<const char*>(src);
-      m.rowidx = kidx;
-      m.stride_bytes = (uint64_t)rows_call->rowstride * (uint64_t)esz;
-      m.rowcount = (uint32_t)rows_call->rowcount;
-      m.nrows = (uint32_t)rows_call->nrows;
-      m.n = n;
+      MxArgs m = mx_args(src, kidx);
       for (int q = 0; q < n; ++q) {
         if (!dst[q] || !sendcounts[q]) continue;
         m.dst[q] = dst[q];
         m.idx_off[q] = sdispls[q];
         m.count[q] = sendcounts[q];
       }
-      hip_check((fp4 ? launch_rowsmx4_pack : b128 ? launch_rowsfp8b_pack : launch_rowsmx_pack)(dtype, m, stream), "kernel launch");
+      hip_check(f->pack(dtype, m, stream), "kernel launch");
       return;
     }
     RowsPackArgs a;
@@ -1338,96 +1430,34 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
     return end_call(scope, stream, 0);
   }
   const CallScope scope = begin_call(stream);
-  auto leave = [&](ncclResult_t rc) {
-    if (scope.cur_dev != device_) hipSetDevice(scope.cur_dev);
-    return rc;
-  };
-  VarRow mine, rows[kMaxRanks];
+  VarRow mine;
   memset(&mine, 0, sizeof mine);
   for (int q = 0; q < n; ++q) {
     mine.sendcounts[q] = sendcounts[q];
     mine.recvcounts[q] = recvcounts[q];
     mine.rdispls[q] = rdispls[q];
   }
-  mine.flags = (scope.capturing() ? (uint32_t)kVarCapturing : 0u) | (rows_call ? (uint32_t)kVarRows : 0u) |
-               (fp4 ? (uint32_t)kVarRowsMx4 : b128 ? (uint32_t)kVarRowsFp8b : mx ? (uint32_t)kVarRowsMx : 0u);
+  mine.flags = (scope.capturing() ? (uint32_t)kVarCapturing : 0u) | (f ? f->flags : 0u);
   mine.pad = rows_call ? (uint32_t)rows_call->rowcount : 0u;  // (below 2^31: rows_check_local)
 
-  PeerBuffers::Decision d = PeerBuffers::kFallback;
-  const char* psend[kMaxRanks] = {};
-  const char* precv[kMaxRanks] = {};
-  // a buffer this rank does not use (all its counts zero: it may be NULL) is stood in for by the
-  // other one, as the rooted collectives do; a rank with neither by the communicator's stub
-  const void* rsend = send ? send : recv;
-  void* rrecv = recv ? recv : const_cast<void*>(send);
-  if (pbuf_.available()) {
-    const bool read_ok = ((algo_ == 2 || algo_ == 4) && (!auto_ || topo_read_)) || (algo_ == 3 && topo_read_);
-    if (!rsend && read_ok) {
-      if (!var_stub_ && hipMalloc((void**)&var_stub_, 256) != hipSuccess) {
-        (void)hipGetLastError();
-        var_stub_ = nullptr;
-      }
-      rsend = rrecv = var_stub_;
-    }
-    bool eligible = false;
-    if (read_ok && rsend) {
-      pbuf_.reap(rsend, rrecv);
-      bool local_s = false, local_r = false;
-      const void* ks = rsend;
-      const void* kr = rrecv;
-      const bool dev_s = pbuf_.known(rsend) ? (local_s = true) : reach(rsend, &ks, &local_s) == Reach::kDevice;
-      const bool dev_r = pbuf_.known(rrecv) ? (local_r = true) : reach(rrecv, &kr, &local_r) == Reach::kDevice;
-      eligible = dev_s && dev_r && local_s && local_r;
-    }
-    bool vec_all = false;
-    try {
-      d = pbuf_.negotiate(rsend, rrecv, eligible, 0, dtype, 0, cfg_.timeout_ms / 1000.0 + 2.0,
-                          [this] { wait_previous_call(); }, psend, precv, &vec_all,
-                          (auto_ ? 0xff : algo_) | coll << 8, &mine, rows);
-    } catch (const PeerGaveUp& e) {
-      return rendezvous_failed(e, true, scope.cur_dev);
-    } catch (const std::exception& e) {
-      return rendezvous_failed(e, false, scope.cur_dev);
-    }
-    if (d == PeerBuffers::kWindowPeer) {
-      fprintf(stderr, "[Mini-NCCL] rank %d: a peer ran this call on registered windows where this rank called "
-              "%s; communicator is no longer usable\n", rank_, name);
-      sticky_ = ncclInvalidUsage;
-      abort_peers();
-      return leave(sticky_);
-    }
-    if (d == PeerBuffers::kMismatch) {
-      fprintf(stderr, "[Mini-NCCL] rank %d: %s: some rank's sendcounts[q] differs from rank q's recvcounts "
-              "for it, or the ranks called different collectives / datatypes%s / schedules (mncclCommSetAlgo)\n", rank_, name,
-              rows_call ? " / rowcounts" : "");
-      return leave(ncclInvalidUsage);
-    }
-  } else if (!gather_rows(mine, dtype, rows, coll) || varblock_matrix_mismatch(n, rows) != 0 ||
-             varblock_rowcounts_differ(n, rows)) {
-    fprintf(stderr, "[Mini-NCCL] rank %d: %s: some rank's sendcounts[q] differs from rank q's recvcounts "
-            "for it, or the ranks passed different datatypes%s\n", rank_, name, rows_call ? " / rowcounts" : "");
-    return leave(ncclInvalidUsage);
-  }
+  VarMeet rv;
+  if (!var_meet({name, coll, dtype, 0, 0, false, rows_call ? " / rowcounts" : ""}, send, recv, mine, scope.cur_dev, &rv))
+    return rv.rc;
+  const PeerBuffers::Decision d = rv.d;
+  const char* const* const psend = rv.psend;
+  const char* const* const precv = rv.precv;
+  const VarRow* const rows = rv.rows;
+  const void* const rsend = rv.rsend;
+  void* const rrecv = rv.rrecv;
   const size_t M = (size_t)varblock_max_count(n, rows) * unit;  // the largest block: the same everywhere
-  if (M == 0) return leave(ncclSuccess);  // nobody sends anything: nothing launched on any rank
-  if (d != PeerBuffers::kRead && varblock_any_capturing(n, rows)) {
-    fprintf(stderr, "[Mini-NCCL] rank %d: %s: this call runs the padded ring, whose stage cannot be "
-            "allocated inside a HIP graph capture (some rank's stream is capturing)\n", rank_, name);
-    return leave(ncclInvalidUsage);
-  }
-  uint32_t seq = ++call_seq_;
-  if (seq == 0) seq = ++call_seq_;
+  if (M == 0) return leave(scope.cur_dev, ncclSuccess);  // nobody sends anything: nothing launched on any rank
+  if (d != PeerBuffers::kRead && varblock_any_capturing(n, rows)) return ring_in_capture(name, scope.cur_dev);
+  const uint32_t seq = next_seq();
   const char* s0 = static_cast<const char*>(send);
   char* r0 = static_cast<char*>(recv);
   if (d == PeerBuffers::kRead && mx) {
-    MxArgs m;
-    memset(&m, 0, sizeof m);
     // (an idle rank's stand-in matrix and list are never read: its counts are all zero)
-    m.rowidx = kidx ? kidx : (const int32_t*)rsend;
-    m.stride_bytes = (uint64_t)rows_call->rowstride * (uint64_t)esz;
-    m.rowcount = (uint32_t)rows_call->rowcount;
-    m.nrows = (uint32_t)rows_call->nrows;
-    m.n = n;
+    MxArgs m = mx_args(nullptr, kidx ? kidx : (const int32_t*)rsend);
     for (int q = 0; q < n; ++q) {
       m.idx_off[q] = sdispls[q];
       m.count[q] = sendcounts[q];
@@ -1435,8 +1465,7 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
     }
     int A = 0;
     const CollParams p = make_params(2, rsend, rrecv, M, seq, psend, precv, 0, 0, coll, 0, 0, &A);
-    hip_check((fp4 ? launch_rowsmx4 : b128 ? launch_rowsfp8b : launch_rowsmx)(dtype, A / geo_.waves, cfg_.threads, p, m, stream),
-              "kernel launch");
+    hip_check(f->push(dtype, A / geo_.waves, cfg_.threads, p, m, stream), "kernel launch");
     last_algo_ = 2;
   } else if (d == PeerBuffers::kRead && rows_call) {
     const void* recv_of[kMaxRanks];
@@ -1499,6 +1528,36 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
   return end_call(scope, stream, seq);
 }
 
+// What tells the combines' formats apart (index: Comm::CombineFormat): the name, the collective id --
+// which alone tells them apart in the rendezvous, so ranks that mix them get kMismatch -- a send
+// row's bytes where it is a record, the local rules, the CombineArgs fill, the fold on the read
+// schedule and the fold out of one local buffer (combine.h, combinemx.h, combinefp8b.h; kernels.h).
+// A new format is a new row here.
+static int combine_plain_check_local(int n, int esz, const void* send, const size_t* sendcounts, const size_t* sdispls,
+                                     const void* recv, size_t nrows, size_t rowstride, const int32_t* slotidx,
+                                     const float* weights, int topk, const size_t* recvcounts, const size_t* rdispls,
+                                     size_t rowcount) {  // (combine_check_local has one more, defaulted, parameter)
+  return combine_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights, topk, recvcounts,
+                             rdispls, rowcount);
+}
+struct CombineFormatInfo {
+  const char* name;
+  int coll;
+  uint64_t (*record_bytes)(uint64_t rowcount);  // nullptr: a send row is an output row
+  decltype(&combinemx_check_local) check_local;
+  decltype(&combinemx_fill_args) fill_args;
+  decltype(&launch_combinemx) fold;
+  decltype(&launch_combinemx_local) local;
+};
+static const CombineFormatInfo kCombineFormats[] = {
+    {"mncclAllToAllvCombine", kCollAllToAllVCombine, nullptr, combine_plain_check_local, combine_fill_args, launch_combine,
+     launch_combine_local},
+    {"mncclAllToAllvCombineMxfp8", kCollAllToAllVCombineMx, mx_record_bytes, combinemx_check_local, combinemx_fill_args,
+     launch_combinemx, launch_combinemx_local},
+    {"mncclAllToAllvCombineFp8Block128", kCollAllToAllVCombineFp8b, fp8b_record_bytes, combinefp8b_check_local,
+     combinefp8b_fill_args, launch_combinefp8b, launch_combinefp8b_local},
+};
+
 // mncclAllToAllvCombine.  var_exchange's call path with the rules of combine.h: the caller's local
 // errors first (nothing launched, nothing negotiated); then every rank's counts reach every rank, with
 // two things ncclAllToAllv keeps private -- the rank's SEND displacements (the puller computes where
@@ -1510,30 +1569,20 @@ ncclResult_t Comm::var_exchange(const void* send, const size_t* sendcounts, cons
 // its rows through one more dense stage region and a strided copy.  Every count zero on every rank:
 // combine_local alone zero-fills (no protocol: every rank sees the same matrix); one rank: the same
 // kernel on the own block.  A rank with no output rows still serves its send; one with no send counts
-// still pulls.  fmt kCombineMxfp8 (mncclAllToAllvCombineMxfp8) and kCombineFp8Block128
-// (mncclAllToAllvCombineFp8Block128): the same path with combinemx.h's or combinefp8b.h's rules -- a send row
-// is a record (sb below, the same for both; rb stays the OUTPUT row's), the collective id is
-// kCollAllToAllVCombineMx or kCollAllToAllVCombineFp8b, which alone tells the two apart in the rendezvous, the
-// kernels combinemx_* or combinefp8b_*; the ring moves the records as bytes.
+// still pulls.  The send side's format (kCombineFormats: `f` below) changes what a send row is -- the
+// row, or a record of sb bytes (rb stays the OUTPUT row's) -- and with it the local rules and the two
+// kernels; the path is one, and the ring moves records as bytes.
 ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv, size_t nrows,
                            size_t rowstride, const int32_t* slotidx, const float* weights, int topk,
                            const size_t* recvcounts, const size_t* rdispls, size_t rowcount, int dtype,
                            hipStream_t stream, CombineFormat fmt) {
   if (sticky_ != ncclSuccess) return sticky_;
   if (check_status() != ncclSuccess) return sticky_;
-  const bool b128 = fmt == kCombineFp8Block128, mx = fmt == kCombineMxfp8;
-  const int n = nranks_, esz = dtype_size(dtype),
-            coll = b128 ? kCollAllToAllVCombineFp8b : mx ? kCollAllToAllVCombineMx : kCollAllToAllVCombine;
-  const char* const name = b128 ? "mncclAllToAllvCombineFp8Block128" : mx ? "mncclAllToAllvCombineMxfp8" : "mncclAllToAllvCombine";
-  // the format's rules and kernels
-  const auto fill_args = b128 ? combinefp8b_fill_args : mx ? combinemx_fill_args : combine_fill_args;
-  const auto launch_fold = b128 ? launch_combinefp8b : mx ? launch_combinemx : launch_combine;
-  const auto launch_local = b128 ? launch_combinefp8b_local : mx ? launch_combinemx_local : launch_combine_local;
-  const int local = b128 || mx ? (b128 ? combinefp8b_check_local : combinemx_check_local)(
-                                     n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights, topk, recvcounts,
-                                     rdispls, rowcount)
-                               : combine_check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights,
-                                                     topk, recvcounts, rdispls, rowcount);
+  const CombineFormatInfo* const f = &kCombineFormats[fmt];
+  const int n = nranks_, esz = dtype_size(dtype), coll = f->coll;
+  const char* const name = f->name;
+  const int local = f->check_local(n, esz, send, sendcounts, sdispls, recv, nrows, rowstride, slotidx, weights, topk, recvcounts,
+                                   rdispls, rowcount);
   if (local != kCombineOk) {
     fprintf(stderr, "[Mini-NCCL] rank %d: %s: %s\n", rank_, name,
             local == kMxRowcount            ? "rowcount is no multiple of 128 in [128, 16384]"
@@ -1549,9 +1598,8 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
                                             : "the recv matrix overlaps a send block, slotidx or weights");
     return ncclInvalidArgument;
   }
-  // rb: an output row's bytes; sb: a send row's (mx, b128: a record's)
-  const size_t rb = rowcount * (size_t)esz,
-               sb = b128 ? (size_t)fp8b_record_bytes(rowcount) : mx ? (size_t)mx_record_bytes(rowcount) : rb;
+  // rb: an output row's bytes; sb: a send row's
+  const size_t rb = rowcount * (size_t)esz, sb = f->record_bytes ? (size_t)f->record_bytes(rowcount) : rb;
   auto how = [&](const void* p) {
     const void* k = p;
     bool l = false;
@@ -1590,9 +1638,9 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
       at[q] = disp[q];
     }
     CombineArgs v;
-    fill_args(&v, n, esz, out_via ? stage_ + out_at : out, nrows, out_via ? rowcount : rowstride, kslot, kw, topk, recvcounts,
-              rdispls, rowcount, send_of, at);
-    hip_check(launch_local(dtype, n, v, packed, out_via ? stage_ + out_at : const_cast<void*>(out), stream), "kernel launch");
+    f->fill_args(&v, n, esz, out_via ? stage_ + out_at : out, nrows, out_via ? rowcount : rowstride, kslot, kw, topk, recvcounts,
+                 rdispls, rowcount, send_of, at);
+    hip_check(f->local(dtype, n, v, packed, out_via ? stage_ + out_at : const_cast<void*>(out), stream), "kernel launch");
     if (out_via)
       hip_check(hipMemcpy2DAsync(recv, rowstride * (size_t)esz, stage_ + out_at, rb, rb, nrows, hipMemcpyDefault, stream),
                 "rows out");
@@ -1615,11 +1663,7 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
     return end_call(scope, stream, 0);
   }
   const CallScope scope = begin_call(stream);
-  auto leave = [&](ncclResult_t rc) {
-    if (scope.cur_dev != device_) hipSetDevice(scope.cur_dev);
-    return rc;
-  };
-  VarRow mine, rows[kMaxRanks];
+  VarRow mine;
   memset(&mine, 0, sizeof mine);
   for (int q = 0; q < n; ++q) {
     mine.sendcounts[q] = sendcounts[q];
@@ -1630,77 +1674,26 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
   mine.pad = (uint32_t)rowcount;  // (below 2^31: combine_check_local)
   mine.nrows = nrows;
 
-  PeerBuffers::Decision d = PeerBuffers::kFallback;
-  const char* psend[kMaxRanks] = {};
-  const char* precv[kMaxRanks] = {};
-  // a buffer this rank does not use (it may be NULL) is stood in for by the other one; a rank with
-  // neither by the communicator's stub
-  const void* rsend = send ? send : recv;
-  void* rrecv = recv ? recv : const_cast<void*>(send);
-  if (pbuf_.available()) {
-    const bool read_ok = ((algo_ == 2 || algo_ == 4) && (!auto_ || topo_read_)) || (algo_ == 3 && topo_read_);
-    if (!rsend && read_ok) {
-      if (!var_stub_ && hipMalloc((void**)&var_stub_, 256) != hipSuccess) {
-        (void)hipGetLastError();
-        var_stub_ = nullptr;
-      }
-      rsend = rrecv = var_stub_;
-    }
-    bool eligible = false;
-    if (read_ok && rsend) {
-      pbuf_.reap(rsend, rrecv);
-      bool local_s = false, local_r = false;
-      const void* ks = rsend;
-      const void* kr = rrecv;
-      const bool dev_s = pbuf_.known(rsend) ? (local_s = true) : reach(rsend, &ks, &local_s) == Reach::kDevice;
-      const bool dev_r = pbuf_.known(rrecv) ? (local_r = true) : reach(rrecv, &kr, &local_r) == Reach::kDevice;
-      eligible = dev_s && dev_r && local_s && local_r;
-    }
-    bool vec_all = false;
-    try {
-      d = pbuf_.negotiate(rsend, rrecv, eligible, 0, dtype, 0, cfg_.timeout_ms / 1000.0 + 2.0,
-                          [this] { wait_previous_call(); }, psend, precv, &vec_all, (auto_ ? 0xff : algo_) | coll << 8, &mine,
-                          rows);
-    } catch (const PeerGaveUp& e) {
-      return rendezvous_failed(e, true, scope.cur_dev);
-    } catch (const std::exception& e) {
-      return rendezvous_failed(e, false, scope.cur_dev);
-    }
-    if (d == PeerBuffers::kWindowPeer) {
-      fprintf(stderr, "[Mini-NCCL] rank %d: a peer ran this call on registered windows where this rank called %s; "
-              "communicator is no longer usable\n", rank_, name);
-      sticky_ = ncclInvalidUsage;
-      abort_peers();
-      return leave(sticky_);
-    }
-    if (d == PeerBuffers::kMismatch) {
-      fprintf(stderr, "[Mini-NCCL] rank %d: %s: some rank's sendcounts[q] differs from rank q's recvcounts for it, or the "
-              "ranks called different collectives / datatypes / rowcounts / schedules (mncclCommSetAlgo)\n", rank_, name);
-      return leave(ncclInvalidUsage);
-    }
-  } else if (!gather_rows(mine, dtype, rows, coll) || varblock_matrix_mismatch(n, rows) != 0 ||
-             varblock_rowcounts_differ(n, rows)) {
-    fprintf(stderr, "[Mini-NCCL] rank %d: %s: some rank's sendcounts[q] differs from rank q's recvcounts for it, or the "
-            "ranks passed different datatypes / rowcounts\n", rank_, name);
-    return leave(ncclInvalidUsage);
-  }
-  const size_t M = (size_t)combine_max_rows(n, rows) * rb;  // the longest output: the same everywhere
-  if (M == 0) return leave(ncclSuccess);                     // nobody has a row to write
+  VarMeet rv;
+  if (!var_meet({name, coll, dtype, 0, 0, false, " / rowcounts"}, send, recv, mine, scope.cur_dev, &rv)) return rv.rc;
+  const PeerBuffers::Decision d = rv.d;
+  const char* const* const psend = rv.psend;
+  const char* const* const precv = rv.precv;
+  const VarRow* const rows = rv.rows;
+  const void* const rsend = rv.rsend;
+  void* const rrecv = rv.rrecv;
+  const size_t M = (size_t)combine_max_rows(n, rows) * rb;     // the longest output: the same everywhere
+  if (M == 0) return leave(scope.cur_dev, ncclSuccess);        // nobody has a row to write
   const size_t Mb = (size_t)varblock_max_count(n, rows) * sb;  // the largest block
   if (Mb == 0) {
     // nobody sends anything: the rows are zero-filled by the local kernel alone, no protocol
-    if (nrows == 0) return leave(ncclSuccess);
+    if (nrows == 0) return leave(scope.cur_dev, ncclSuccess);
     if (out_via) ensure_stage(out_bytes, stream);
     fold_local(nullptr, none, 0);
     return end_call(scope, stream, 0);
   }
-  if (d != PeerBuffers::kRead && varblock_any_capturing(n, rows)) {
-    fprintf(stderr, "[Mini-NCCL] rank %d: %s: this call runs the padded ring, whose stage cannot be allocated inside a "
-            "HIP graph capture (some rank's stream is capturing)\n", rank_, name);
-    return leave(ncclInvalidUsage);
-  }
-  uint32_t seq = ++call_seq_;
-  if (seq == 0) seq = ++call_seq_;
+  if (d != PeerBuffers::kRead && varblock_any_capturing(n, rows)) return ring_in_capture(name, scope.cur_dev);
+  const uint32_t seq = next_seq();
   if (d == PeerBuffers::kRead) {
     const void* send_of[kMaxRanks];
     uint64_t peer_sdispl[kMaxRanks];
@@ -1710,11 +1703,11 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
     }
     CombineArgs v;
     // (a rank without rows passes a stand-in list: never read)
-    fill_args(&v, n, esz, rrecv, nrows, rowstride, nrows ? kslot : (const int32_t*)rsend, nrows ? kw : nullptr, topk,
-              recvcounts, rdispls, rowcount, send_of, peer_sdispl);
+    f->fill_args(&v, n, esz, rrecv, nrows, rowstride, nrows ? kslot : (const int32_t*)rsend, nrows ? kw : nullptr, topk,
+                 recvcounts, rdispls, rowcount, send_of, peer_sdispl);
     int A = 0;
     const CollParams p = make_params(2, rsend, rrecv, M, seq, psend, precv, 0, 0, coll, 0, 0, &A);
-    hip_check(launch_fold(dtype, A / geo_.waves, cfg_.threads, p, v, stream), "kernel launch");
+    hip_check(f->fold(dtype, A / geo_.waves, cfg_.threads, p, v, stream), "kernel launch");
     last_algo_ = 2;
   } else {
     const size_t Mpad = (Mb + 15) & ~(size_t)15;
@@ -1746,9 +1739,8 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
 
 // mncclAllGatherv / mncclReduceScatterv.  all_to_all_v's call path with one row of counts and
 // displacements that every rank must pass alike: the caller's local errors first (vhalves.h: nothing
-// launched, nothing negotiated); then every rank's arrays reach every rank -- through the read
-// schedule's rendezvous wherever the board exists, whatever the schedule, else over the bootstrap --
-// and are compared for equality, with the collective, datatype, op, scalar bits and schedule choice.
+// launched, nothing negotiated); then every rank's arrays reach every rank (var_meet) and are compared
+// for equality, with the collective, datatype, op, scalar bits and schedule choice.
 // The geometry follows M, the largest block in bytes.  On the read schedule: kernels.hip vhalf_push /
 // vhalf_fold with this rank's base and length, the one-block buffer's pointer shifted by -base as
 // Comm::make_params shifts the uniform halves' by -rank * chunk; the 16-byte path is this rank's own
@@ -1756,9 +1748,8 @@ ncclResult_t Comm::combine(const void* send, const size_t* sendcounts, const siz
 // an n * Mpad stage and the in-place layout: the all-gather packs its own block into chunk `rank`,
 // runs the ring all-gather and unpacks the n blocks; the reduce-scatter packs the n blocks, runs the
 // ring reduce-scatter with Mpad / esz elements and copies its block out of chunk `rank`.  The padding
-// is never initialised: its results are discarded.  The stage may have to be allocated, which a graph
-// capture cannot do: if the decision is the fallback and ANY rank is capturing, every rank returns
-// ncclInvalidUsage.  A rank whose own count is 0 still takes part in the rendezvous and the protocol.
+// is never initialised: its results are discarded.  The fallback is refused while any rank is capturing
+// (ring_in_capture).  A rank whose own count is 0 still takes part in the rendezvous and the protocol.
 ncclResult_t Comm::vhalf(int coll, void* array_buf, const size_t* counts, const size_t* displs, void* one_buf,
                          size_t one_count, int dtype, int op, hipStream_t stream, uint64_t scalar) {
   if (sticky_ != ncclSuccess) return sticky_;
@@ -1790,11 +1781,7 @@ ncclResult_t Comm::vhalf(int coll, void* array_buf, const size_t* counts, const 
     return end_call(scope, stream, 0);
   }
   const CallScope scope = begin_call(stream);
-  auto leave = [&](ncclResult_t rc) {
-    if (scope.cur_dev != device_) hipSetDevice(scope.cur_dev);
-    return rc;
-  };
-  VarRow row, rows[kMaxRanks];
+  VarRow row;
   memset(&row, 0, sizeof row);
   for (int q = 0; q < n; ++q) {
     row.sendcounts[q] = counts[q];
@@ -1803,76 +1790,22 @@ ncclResult_t Comm::vhalf(int coll, void* array_buf, const size_t* counts, const 
   row.flags = (uint32_t)kVarSameRows | (scope.capturing() ? (uint32_t)kVarCapturing : 0u);
   const uint64_t sbits = op == kPreMulSum ? scalar : 0;
 
-  PeerBuffers::Decision d = PeerBuffers::kFallback;
-  const char* psend[kMaxRanks] = {};
-  const char* precv[kMaxRanks] = {};
-  bool vec_all = false;
-  // a buffer this rank does not use (its counts zero: it may be NULL) is stood in for by the other
-  // one, as the rooted collectives do; a rank with neither by the communicator's stub
-  const void* const send = gather ? one : arr;
-  void* const recv = gather ? arr : one;
-  const void* rsend = send ? send : recv;
-  void* rrecv = recv ? recv : const_cast<void*>(send);
-  if (pbuf_.available()) {
-    const bool read_ok = ((algo_ == 2 || algo_ == 4) && (!auto_ || topo_read_)) || (algo_ == 3 && topo_read_);
-    if (!rsend && read_ok) {
-      if (!var_stub_ && hipMalloc((void**)&var_stub_, 256) != hipSuccess) {
-        (void)hipGetLastError();
-        var_stub_ = nullptr;
-      }
-      rsend = rrecv = var_stub_;
-    }
-    bool eligible = false;
-    if (read_ok && rsend) {
-      pbuf_.reap(rsend, rrecv);
-      bool local_s = false, local_r = false;
-      const void* ks = rsend;
-      const void* kr = rrecv;
-      const bool dev_s = pbuf_.known(rsend) ? (local_s = true) : reach(rsend, &ks, &local_s) == Reach::kDevice;
-      const bool dev_r = pbuf_.known(rrecv) ? (local_r = true) : reach(rrecv, &kr, &local_r) == Reach::kDevice;
-      eligible = dev_s && dev_r && local_s && local_r;
-    }
-    try {
-      d = pbuf_.negotiate(rsend, rrecv, eligible, 0, dtype, op, cfg_.timeout_ms / 1000.0 + 2.0,
-                          [this] { wait_previous_call(); }, psend, precv, &vec_all, (auto_ ? 0xff : algo_) | coll << 8,
-                          &row, rows, sbits);
-    } catch (const PeerGaveUp& e) {
-      return rendezvous_failed(e, true, scope.cur_dev);
-    } catch (const std::exception& e) {
-      return rendezvous_failed(e, false, scope.cur_dev);
-    }
-    if (d == PeerBuffers::kWindowPeer) {
-      fprintf(stderr, "[Mini-NCCL] rank %d: a peer ran this call on registered windows where this rank called %s; "
-              "communicator is no longer usable\n", rank_, name);
-      sticky_ = ncclInvalidUsage;
-      abort_peers();
-      return leave(sticky_);
-    }
-    if (d == PeerBuffers::kMismatch) {
-      fprintf(stderr, "[Mini-NCCL] rank %d: %s: the ranks passed different counts or displacements, or called different "
-              "collectives / datatypes / ops (or scalars) / schedules (mncclCommSetAlgo)\n", rank_, name);
-      return leave(ncclInvalidUsage);
-    }
-  } else if (!gather_rows(row, dtype, rows, coll, op, sbits) || vhalf_rows_differ(n, rows) != 0) {
-    fprintf(stderr, "[Mini-NCCL] rank %d: %s: the ranks passed different counts or displacements, or called different "
-            "collectives / datatypes / ops (or scalars)\n", rank_, name);
-    return leave(ncclInvalidUsage);
-  }
+  VarMeet rv;
+  if (!var_meet({name, coll, dtype, op, sbits, true, ""}, gather ? one : arr, gather ? arr : one, row, scope.cur_dev, &rv))
+    return rv.rc;
+  const PeerBuffers::Decision d = rv.d;
+  const bool vec_all = rv.vec_all;
+  const VarRow* const rows = rv.rows;
   const size_t M = (size_t)vhalf_max_count(n, rows[0]) * (size_t)esz;  // the largest block: the same everywhere
-  if (M == 0) return leave(ncclSuccess);  // every count is 0 on every rank: nothing launched
-  if (d != PeerBuffers::kRead && varblock_any_capturing(n, rows)) {
-    fprintf(stderr, "[Mini-NCCL] rank %d: %s: this call runs the padded ring, whose stage cannot be allocated inside a "
-            "HIP graph capture (some rank's stream is capturing)\n", rank_, name);
-    return leave(ncclInvalidUsage);
-  }
-  uint32_t seq = ++call_seq_;
-  if (seq == 0) seq = ++call_seq_;
+  if (M == 0) return leave(scope.cur_dev, ncclSuccess);  // every count is 0 on every rank: nothing launched
+  if (d != PeerBuffers::kRead && varblock_any_capturing(n, rows)) return ring_in_capture(name, scope.cur_dev);
+  const uint32_t seq = next_seq();
   if (d == PeerBuffers::kRead) {
     VHalfArgs v;
     v.base = base;
     v.bytes = mine;
     int A = 0;
-    CollParams p = make_params(2, rsend, rrecv, M, seq, psend, precv, 0, 0, coll, 0, 0, &A);
+    CollParams p = make_params(2, rv.rsend, rv.rrecv, M, seq, rv.psend, rv.precv, 0, 0, coll, 0, 0, &A);
     p.scale = sbits;
     // the one-block buffer, shifted so that this rank's block of it is the buffer itself (never
     // dereferenced below the buffer: every slice starts at v.base)
@@ -1981,8 +1914,7 @@ ncclResult_t Comm::p2p_group(const P2pGroup& g, hipStream_t stream) {
     p2p_direct_recvs_ += direct;
   }
   const CallScope scope = begin_call(stream);
-  uint32_t seq = ++call_seq_;
-  if (seq == 0) seq = ++call_seq_;
+  const uint32_t seq = next_seq();
   int A = 0;
   const CollParams p = make_params(0, nullptr, nullptr, 0, seq, nullptr, nullptr, 0, 0, kCollAllReduce, 0, 0, &A);
   hip_check(windowed ? launch_p2p_window(p, wa, stream) : launch_p2p(p, a, stream), "kernel launch");

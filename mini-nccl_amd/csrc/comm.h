@@ -130,43 +130,21 @@ class Comm {
                             const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream) {
     return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, nullptr);
   }
-  // The same with the send blocks gathered by row index (mncclAllToAllvRows, mini_nccl_ext.h; counts
-  // and displacements in rows): the block for rank q is the rows rowidx[sdispls[q] + i] of the
-  // nrows x rowstride matrix at `send`, rowcount elements each.  all_to_all_v's call path with the
-  // rules of rowblock.h: kernels.hip rows_push on the read schedule; else rows_pack gathers the blocks
-  // into the padded ring's stage where ncclAllToAllv copies them there.
+  // The same with the send blocks gathered by row index (mncclAllToAllvRows and its quantising forms,
+  // mini_nccl_ext.h; counts and displacements in rows): the block for rank q is the rows
+  // rowidx[sdispls[q] + i] of the nrows x rowstride matrix at `send`, rowcount elements each.
+  // fmt: what a delivered row is -- the row itself (rowblock.h's rules), or its MXFP8 / MXFP4 record
+  // (mncclAllToAllvRowsMxfp8 / Mxfp4, mxblock.h), or its e4m3 record with an f32 scale per 128
+  // (mncclAllToAllvRowsFp8Block128, fp8block.h); for a record dtype is the matrix's, kBF16 or kF16, and
+  // the receive side counts records.  all_to_all_v's call path, the format's kernels from comm.cpp's
+  // table: its push kernel on the read schedule; else its pack kernel gathers (and quantises) the
+  // blocks into the padded ring's stage where ncclAllToAllv copies them there.
+  enum RowsFormat { kRowsPlain, kRowsMxfp8, kRowsMxfp4, kRowsFp8Block128 };
   ncclResult_t all_to_all_v_rows(const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
                                  const size_t* sendcounts, const size_t* sdispls, void* recv, const size_t* recvcounts,
-                                 const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream) {
-    const RowsCall rows{nrows, rowstride, rowcount, rowidx};
-    return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
-  }
-
-  // The same again with every row quantised to an MXFP8 record on the way out (mncclAllToAllvRowsMxfp8,
-  // mini_nccl_ext.h; dtype is the matrix's, kBF16 or kF16; the receive side counts records of
-  // rowcount + rowcount / 32 bytes).  The rules of mxblock.h: kernels.hip rowsmx_push on the read
-  // schedule; else rowsmx_pack quantises into the padded ring's stage.
-  ncclResult_t all_to_all_v_rows_mx(const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
-                                    const size_t* sendcounts, const size_t* sdispls, void* recv, const size_t* recvcounts,
-                                    const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream) {
-    const RowsCall rows{nrows, rowstride, rowcount, rowidx, kRowsMxfp8};
-    return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
-  }
-  // And with MXFP4 records (mncclAllToAllvRowsMxfp4: rowcount / 2 + rowcount / 32 bytes, mxblock.h's mx4_
-  // rules): kernels.hip rowsmx4_push on the read schedule; else rowsmx4_pack into the padded ring's stage.
-  ncclResult_t all_to_all_v_rows_mx4(const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
-                                     const size_t* sendcounts, const size_t* sdispls, void* recv, const size_t* recvcounts,
-                                     const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream) {
-    const RowsCall rows{nrows, rowstride, rowcount, rowidx, kRowsMxfp4};
-    return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
-  }
-  // And with e4m3 elements and one f32 scale per 128 (mncclAllToAllvRowsFp8Block128: records of MXFP8's
-  // size, fp8block.h's rules): kernels.hip rowsfp8b_push on the read schedule; else rowsfp8b_pack into
-  // the padded ring's stage.
-  ncclResult_t all_to_all_v_rows_fp8b(const void* send, size_t nrows, size_t rowstride, const int32_t* rowidx,
-                                      const size_t* sendcounts, const size_t* sdispls, void* recv, const size_t* recvcounts,
-                                      const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream) {
-    const RowsCall rows{nrows, rowstride, rowcount, rowidx, kRowsFp8Block128};
+                                 const size_t* rdispls, size_t rowcount, int dtype, hipStream_t stream,
+                                 RowsFormat fmt = kRowsPlain) {
+    const RowsCall rows{nrows, rowstride, rowcount, rowidx, fmt};
     return var_exchange(send, sendcounts, sdispls, recv, recvcounts, rdispls, dtype, stream, &rows);
   }
 
@@ -308,15 +286,47 @@ class Comm {
   // (mncclAllGatherv / mncclReduceScatterv pass their collective, op and scalar bits: compared too)
   bool gather_rows(const VarRow& mine, int dtype, VarRow* rows, int coll = kCollAllToAllV, int op = 0,
                    uint64_t scalar = 0);
+  // The rendezvous of the calls with per-rank counts (var_exchange, combine, vhalf), from "this
+  // rank's VarRow is filled" to "the sequence number is taken": every rank's row reaches every rank --
+  // through the read schedule's rendezvous wherever the board exists, whatever the schedule (a rank
+  // the read schedule is closed to takes part as ineligible), else over the bootstrap -- and is
+  // checked.  VarCall: what differs between the callers.
+  struct VarCall {
+    const char* name;     // as the messages print it
+    int coll, dtype, op;  // ride in the rendezvous with `scalar`, compared between the ranks
+    uint64_t scalar;
+    bool same_rows;       // the halves: every rank's row must equal rank 0's (vhalves.h), and their
+                          // mismatch text; else the count matrix and the row lengths (varblock.h)
+    const char* also;     // " / rowcounts" where the ranks must pass one row length, else ""
+  };
+  struct VarMeet {
+    PeerBuffers::Decision d = PeerBuffers::kFallback;
+    const char* psend[kMaxRanks] = {};  // kRead: every rank's buffers mapped here
+    const char* precv[kMaxRanks] = {};
+    bool vec_all = false;
+    VarRow rows[kMaxRanks];             // every rank's row, whatever the decision
+    // a buffer this rank does not use (its counts zero: it may be NULL) is stood in for by the other
+    // one, as the rooted collectives do; a rank with neither by the communicator's stub
+    const void* rsend;
+    void* rrecv;
+    ncclResult_t rc = ncclSuccess;      // var_meet returned false: what the call returns
+  };
+  // false: the call ends with m->rc (a failed or refused rendezvous, a mismatch), the caller's device
+  // (cur_dev) restored
+  bool var_meet(const VarCall& c, const void* send, void* recv, const VarRow& mine, int cur_dev, VarMeet* m);
+  // the fallback of those calls while some rank's stream is capturing: refused on every rank
+  ncclResult_t ring_in_capture(const char* name, int cur_dev);
+  ncclResult_t leave(int cur_dev, ncclResult_t rc) {  // an early return after begin_call
+    if (cur_dev != device_) hipSetDevice(cur_dev);
+    return rc;
+  }
+  uint32_t next_seq() { return ++call_seq_ ? call_seq_ : ++call_seq_; }  // a launch's number; 0 = "no kernel" (wait_for)
   // the one call path of ncclAllToAllv (rows == nullptr: counts and displacements in elements of
   // `send`) and mncclAllToAllvRows (in rows of the matrix `rows` describes at `send`)
-  // what a delivered row is: the row itself, or its MXFP8 / MXFP4 record (mxblock.h), or its e4m3
-  // record with an f32 scale per 128 (fp8block.h)
-  enum RowsFormat { kRowsPlain, kRowsMxfp8, kRowsMxfp4, kRowsFp8Block128 };
   struct RowsCall {
     size_t nrows, rowstride, rowcount;
     const int32_t* rowidx;
-    RowsFormat fmt = kRowsPlain;
+    RowsFormat fmt;
   };
   ncclResult_t var_exchange(const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
                             const size_t* recvcounts, const size_t* rdispls, int dtype, hipStream_t stream,

@@ -97,3 +97,13 @@ def test_refusals_and_idle_ranks(dev, n):
         cases[-1:-1] = [dict(base, seed=114, over=dict(rowcount=301), want_rc=5),
                         dict(base, seed=115, over=dict(rc=[int(C[0, 1]) + 1] + [int(v) for v in C[1:, 1]]), want_rc=5)]
     _run(n, cases)
+
+
+@pytest.mark.parametrize("algo", [pytest.param(READ, id="read"), pytest.param(RING, id="ring")])
+def test_rank_with_neither_buffer_takes_part(dev, algo):
+    """n = 2: rank 1 sends nothing, has no output rows and passes NULL for sendbuff, recvbuff, slotidx and
+    weights; on the read schedule the communicator's stub stands in for its buffers in the rendezvous.
+    Rank 0 folds its own two rows of 128 bf16, exact; ncclSuccess and the same schedule on both ranks."""
+    case = dict(C=[[2, 0], [0, 0]], dtype="bf16", rowcount=128, topk=2, nrows=[2, 0], algo=algo, expect_algo=algo, seed=120,
+                over=dict(send=None, recv=None, idx=None, w=None))
+    _run(2, [case])
